@@ -24,11 +24,20 @@ torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --ma
 <same arguments>` as a CHILD process, forwards rank 0's single JSON line and exits with the child's status
 (a failing or killed rank ends the job non-zero); it never falls back to one rank.
 
-Timing: W warm-up steps, then blocks of exactly K steps, each bracketed by barrier + synchronize on both
-sides and reduced with MAX over ranks.  The first block is what a cold process gets (clocks still
-ramping, first touch of the pose arrays) and is reported as `cold`; `value` / `ms_per_step` are the
-MEDIAN block (all block times are listed), so a 20-step run reports the same steady-state number as a
-200-step one.
+Timing: W warm-up steps, then ONE block of exactly K steps (--steps), bracketed by barrier + synchronize on
+both sides and reduced with MAX over ranks: `value` / `ms_per_step` are that block.
+
+A plain run does only that: set-up, warm-up, the timed steps, --dump-outputs if given, the result line.
+Everything else this driver measures or checks runs with --full: further K-step blocks (cold / median /
+all block times, the form rounds 1-6 reported), the other sum exchanges at N > 1, the contracted-arithmetic
+Radon stack and its metric tie, pre-processing, the HIP-event pair-kernel pass, socket power, the
+record-reuse-off blocks, the roofline objects with their rocprofv3 --pmc passes, the cache-resident launches
+and the CPU baseline with its parity figures.
+
+--dump-outputs DIR: what the timed path returned in its last step -- the mean (ecc_mean.npy, float64) -- and
+that pose's n(n-1)/2 pair values in the order of ecc_metric_get_ij (pair_values.npy, float32, evaluated
+again after the timed block: the cost image a caller can ask for).  Inputs are synthetic and seeded, so two
+builds can be compared output for output.
 
 Prints ONE JSON line on rank 0.
 """
@@ -71,6 +80,21 @@ def emit(obj):
     out = _RESULT_STREAM or sys.stdout
     out.write(json.dumps(obj) + "\n")
     out.flush()
+
+
+def dump_outputs(directory, arrays, limit_bytes=64 << 20):
+    """--dump-outputs: every array as directory/<name>.npy in float32 or float64, at most limit_bytes in all."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    for k, v in arrays.items():
+        if v.dtype not in (np.float32, np.float64):
+            raise ValueError("%s: %s is neither float32 nor float64" % (k, v.dtype))
+    total = sum(v.nbytes for v in arrays.values())
+    if total > limit_bytes:
+        raise ValueError("outputs of %d bytes exceed the %d-byte limit" % (total, limit_bytes))
+    os.makedirs(directory, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(directory, k + ".npy"), v)
 
 
 class PowerSampler:
@@ -171,8 +195,13 @@ def parse():
                     help="N = 1: do not run the rocprofv3 --pmc pass of this same bench (a child process, ~15 s) that "
                          "measures the pair kernel's HBM bytes and vector instructions for the roofline objects; the "
                          "committed profiles/pmc_current.json is used instead")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: further timed blocks, other exchanges, Radon arithmetic modes, "
+                         "pre-processing, pair-kernel events, power, record reuse off, rooflines and PMC passes, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (ecc_mean, pair_values)")
     ap.add_argument("--blocks", type=int, default=0,
-                    help="number of timed K-step blocks (0 = automatic: 5 to 60, about 1.2 s in total)")
+                    help="--full: number of K-step blocks behind the headline's (0 = automatic: 5 to 60, about 1.2 s in total)")
     ap.add_argument("--single-device", action="store_true",
                     help="rehearsal: every rank uses cuda:0 (needs --backend gloo)")
     ap.add_argument("--cpu-sample-stride", type=int, default=1,
@@ -240,7 +269,7 @@ def load_pmc(kernel_prefix):
 
 
 def live_pmc(args, counters=("FETCH_SIZE", "SQ_INSTS_VALU", "SQ_INSTS_VMEM_RD")):
-    """One rocprofv3 --pmc pass over a short run of THIS bench (child process: python3 bench.py --steps 3 --no-live-pmc):
+    """One rocprofv3 --pmc pass over a short run of THIS bench (child process: python3 bench.py --full --steps 3 --no-live-pmc):
     per-launch averages of FETCH_SIZE, SQ_INSTS_VALU and SQ_INSTS_VMEM_RD of the pair kernel, measured on this box in
     this run.  FETCH_SIZE (TCC) and the SQ counters fit one pass; WRITE_SIZE cannot ride along (TCC slots,
     MI355X_MICROARCH.md) and is taken as the kernel's algorithmic 4 bytes per pair (the separate pass under profiles/
@@ -261,7 +290,7 @@ def live_pmc(args, counters=("FETCH_SIZE", "SQ_INSTS_VALU", "SQ_INSTS_VMEM_RD"))
     out_dir = tempfile.mkdtemp(prefix="ecc_pmc_", dir="/tmp")
     try:
         cmd = [exe, "--kernel-trace", "--pmc"] + list(counters) + ["--output-format", "csv",
-               "-d", out_dir, "--", sys.executable, os.path.abspath(__file__), "--steps", "3", "--warmup", "1", "--blocks", "3",
+               "-d", out_dir, "--", sys.executable, os.path.abspath(__file__), "--full", "--steps", "3", "--warmup", "1", "--blocks", "3",
                "--no-cpu-baseline", "--no-live-pmc", "--pmc-child", "--views", str(args.views), "--size", str(args.size), "--bins", str(args.bins)]
         env = dict(os.environ, TMPDIR="/tmp")
         subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=240, check=True)
@@ -666,17 +695,18 @@ def main():
     # untimed first call: the context allocates its scratch (transposed image copy, trig table), clocks ramp
     keep = E.RadonIntermediate.compute_into(ctx, imgs_all[:min(sub, hi - lo)], local[:min(sub, hi - lo)], B, B)
     ctx.synchronize()
-    power.start()
+    if args.full:
+        power.start()
     keep = E.RadonIntermediate.compute_into(ctx, imgs_all, local[:hi - lo], B, B)
     ctx.synchronize()
-    power_radon = power.stop(skip_s=0.05)
+    power_radon = power.stop(skip_s=0.05)  # (None unless started)
     radon_ms = ctx.last_kernel_ms("radon")
     ms_per_radon = radon_ms / max(hi - lo, 1)
     # the same stack in the contracted arithmetic (ecc_radon_set_arithmetic(ECC_RADON_FMA): positions fmaf(t, d, o), lerps
     # as one fma each; bit-identical to the oracle's contracted variant, tests/test_gpu_radon_fma.py).  The metric below is
     # evaluated on the EXACT stack; at N = 1 it is evaluated on this one too and the two means are compared.
     slabs_fma, ms_per_radon_fma = None, 0.0
-    if not args.pmc_child:
+    if args.full and not args.pmc_child:
         slabs_fma = torch.zeros((hi - lo, slab), dtype=torch.float32, device=dev)
         ctx.setRadonArithmetic("fma")
         keep = E.RadonIntermediate.compute_into(ctx, imgs_all, slabs_fma, B, B)
@@ -688,13 +718,15 @@ def main():
         slabs_fma = None
     # pre-processing (the step in front of the Radon intermediate) on one sub-batch, device
     # resident in and out, reference defaults + cosine weighting: HBM-bound, 8 B per pixel algorithmic
-    imgs = synthetic.projections_torch(Ps[lo:min(lo + sub, hi)], S, S, phantom, dev)
-    pre_out = torch.empty_like(imgs)
-    pp = E.PreProccess()
-    for _ in range(2):
-        pp.process(ctx, imgs, Ps[lo:min(lo + sub, hi)], out=pre_out)
-    ms_per_preprocess = ctx.last_kernel_ms("preprocess") / imgs.shape[0]
-    del imgs, pre_out
+    ms_per_preprocess = None
+    if args.full:
+        imgs = synthetic.projections_torch(Ps[lo:min(lo + sub, hi)], S, S, phantom, dev)
+        pre_out = torch.empty_like(imgs)
+        pp = E.PreProccess()
+        for _ in range(2):
+            pp.process(ctx, imgs, Ps[lo:min(lo + sub, hi)], out=pre_out)
+        ms_per_preprocess = ctx.last_kernel_ms("preprocess") / imgs.shape[0]
+        del imgs, pre_out
     if grouped:
         if args.backend == "nccl":
             gathered = torch.empty_like(slabs_all)
@@ -832,28 +864,26 @@ def main():
             el = e.item()
         return el, last
 
-    def measure(mode):
-        """W warm-up steps, then blocks of K steps: the first is the cold number, the median the steady one."""
-        step = make_step(mode)
+    def measure(step):
+        """W warm-up steps, then the headline block of K steps.  --full: further K-step blocks behind it (the first block is
+        the cold number, the median of all the steady one: the headline of rounds 1-6)."""
         for k in range(args.warmup):
             step(k)
-        blocks, last = [], None
         el, last = timed_block(step, 0)
-        blocks.append(el)
-        # automatic: about 1.2 s of timed steps, 5 to 60 blocks -- the driver's 20-step blocks last 7 ms each and the clocks
-        # of a box that idled through the host-side set-up take a few tenths of a second to settle (round 4: blocks 1-5
-        # 0.40-0.45 ms per step, 6-9 0.364-0.370; round 5, one box: eight 67-ms blocks falling from 0.333 to 0.312 ms per step,
-        # the median of nine on the ramp); every block's time is in timing.blocks_ms_per_step
-        n_blocks = args.blocks if args.blocks > 0 else int(min(60, max(5, 1.2 / max(el, 1e-6))))
-        if grouped:  # every rank must run the same number of blocks
-            nb = torch.tensor([n_blocks], dtype=torch.int64, device=dev if args.backend == "nccl" else "cpu")
-            dist.broadcast(nb, 0)
-            n_blocks = int(nb.item())
-        for b in range(1, n_blocks):
-            el, last = timed_block(step, b * args.steps)
-            blocks.append(el)
-        steady = sorted(blocks)[len(blocks) // 2]
-        return dict(cold=blocks[0], steady=steady, blocks=blocks, last=last, step=step)
+        blocks = [el]
+        if args.full:
+            # automatic: about 1.2 s of timed steps, 5 to 60 blocks -- the driver's 20-step blocks last 7 ms each and the clocks
+            # of a box that idled through the host-side set-up take a few tenths of a second to settle (round 4: blocks 1-5
+            # 0.40-0.45 ms per step, 6-9 0.364-0.370; round 5, one box: eight 67-ms blocks falling from 0.333 to 0.312 ms per step,
+            # the median of nine on the ramp); every block's time is in timing.blocks_ms_per_step
+            n_blocks = args.blocks if args.blocks > 0 else int(min(60, max(5, 1.2 / max(el, 1e-6))))
+            if grouped:  # every rank must run the same number of blocks
+                nb = torch.tensor([n_blocks], dtype=torch.int64, device=dev if args.backend == "nccl" else "cpu")
+                dist.broadcast(nb, 0)
+                n_blocks = int(nb.item())
+            for b in range(1, n_blocks):
+                blocks.append(timed_block(step, b * args.steps)[0])
+        return dict(headline=el, cold=blocks[0], steady=sorted(blocks)[len(blocks) // 2], blocks=blocks, last=last, step=step)
 
     ctx.enable_timing(False)  # no event records inside the timed region (they break back-to-back dispatch)
     if not grouped:
@@ -866,227 +896,234 @@ def main():
         modes = ["rccl"]
     else:
         modes = ["collective"]
-    results = {m: measure(m) for m in modes}
     # N > 1: the headline is the step with the all-reduce of the partial sums (RCCL with --backend nccl), the exchange
-    # north_star names; the shared-memory exchange is reported next to it under timing.other_exchange
-    # the headline is the RCCL all-reduce: issued by the library where its communicator exists (one call per step, everything
-    # stream-ordered), else through torch.distributed
+    # north_star names; with --full the shared-memory exchange is timed next to it and reported under timing.other_exchange
     # Which exchange is the headline.  The library-issued RCCL all-reduce (one call per step, everything stream-ordered) when its
     # communicator exists on every rank -- but only after THIS run has shown, below, that it returns what torch.distributed's
     # all-reduce and the shared-memory exchange return for the same step (round 5's advisor: it had only ever run with one
     # rank; the ranks now agree on its availability first, its creation is under a watchdog, and a disagreement ends the run).
     best = "rccl" if "rccl" in modes else ("collective" if "collective" in modes else modes[0])
-    same_step = {m: [results[m]["step"](k) for k in (3, 4, 11)] for m in modes}  # the same poses through every exchange (every rank, the same order)
+    steps = {m: make_step(m) for m in modes}
+    results = {m: measure(steps[m]) for m in (modes if args.full else [best])}
+    same_step = {m: [steps[m](k) for k in (3, 4, 11)] for m in modes}  # the same poses through every exchange (every rank, the same order)
     for m in modes:
         for x, y in zip(same_step[m], same_step[modes[0]]):
             if not abs(x - y) <= 1e-12 * abs(y):
                 raise SystemExit("the exchanges disagree on the same step: %r" % (same_step,))
     res = results[best]
-    elapsed, last, step = res["steady"], res["last"], res["step"]
-    # pair-kernel duration: HIP events on the context's stream around the pair kernel alone, averaged over a
-    # second, untimed pass over the same steps (at most 50)
-    ctx.enable_timing(True)
-    pair_ms, n_timed = 0.0, max(1, min(args.steps, 50))
-    for k in range(n_timed):
-        step(k)
-        pair_ms += ctx.last_kernel_ms("pairs")
-    fence()
-    pair_ms /= n_timed
-    pair_s = pair_ms * 1e-3
-    # socket power and engine clock while the same steps run back to back (untimed, ~1.5 s; the first 0.5 s dropped: the
-    # reading is a moving average and the controller takes about a second to settle at the cap)
-    ctx.enable_timing(False)
-    n_power = 0 if (args.no_power or args.pmc_child) else int(min(20000, max(200, 1.5 / max(elapsed / args.steps, 1e-6))))  # (elapsed is the MAX over ranks: the same count everywhere)
-    fence()
-    power.start()
-    t_p = time.perf_counter()
-    for k in range(n_power):
-        step(k)
-    fence()
-    t_p = time.perf_counter() - t_p
-    power_steps = power.stop(skip_s=0.5) if n_power else (power.stop() and None)
-    if power_steps:
-        power_steps["ms_per_step_while_sampling"] = 1e3 * t_p / n_power
-        power_steps["steps"] = n_power
-    ctx.enable_timing(True)
-
-    # the same steps with the record reuse switched off (every step refits all pairs and launches e1_kernel): the
-    # results are bit-identical, only the fixed cost per step differs
-    ctx.enable_timing(False)
-    metric.setRecordReuse(False)
-    for k in range(args.warmup):
-        step(k)
-    off_blocks = []
-    for b in range(3):
-        el_off, last_off = timed_block(step, b * args.steps)
-        off_blocks.append(el_off)
-    v_off = [step(k) for k in (3, 4, 4, 11)]
-    metric.setRecordReuse(True)
-    v_on = [step(k) for k in (3, 4, 4, 11)]
-    reuse_off_s = sorted(off_blocks)[1]
-    if v_on != v_off:
-        raise SystemExit("record reuse changed the results: %r vs %r" % (v_on, v_off))
-
-    # ---- socket power and engine clock (hwmon) --------------------------------------------------------------------------
-    # Both kernels run INTO THE POWER CAP: the socket reads 1395-1399 W of its 1400 W while the steps run back to back and
-    # the engine clock settles near 2.2 GHz, below the 2.4 GHz every roof here is priced at.  At the cap a kernel's time
-    # follows the ENERGY of its instruction and data stream, not the issue slots of one pipe: cutting instructions returns
-    # well under its share (CHANGELOG.md 4.2 has five rounds of such cuts), and idle XCDs at the end of a launch cost
-    # nothing (the remaining ones clock up: CHANGELOG.md round 5, XCD schedule).  `frac_at_measured_clock` restates the two
-    # clock-bound roofs against the clock the chip actually ran at.
-    power_report = None
-    if power.dir and rank == 0:
-        cap, rated = power.cap_w(), power.rated_mhz()
-        power_report = {"source": "amdgpu hwmon power1_input / freq1_input, 2-ms samples, outside the timed blocks",
-                        "cap_w": cap, "sclk_rated_mhz": rated,
-                        "before_first_launch": {"w": power_first[0], "sclk_mhz": power_first[1]} if power_first else None,
-                        "pair_steps": power_steps, "radon_stack": power_radon,
-                        "radon_stack_note": "one call of about 0.2 s: the power reading (a moving average) is still rising when it ends"}
-        if power_steps and cap:
-            power_report["pair_steps"]["frac_of_cap"] = power_steps["avg_w"] / cap
-
+    elapsed, last, step = res["headline"], res["last"], res["step"]
+    if args.dump_outputs and rank == 0:
+        # the pose of the headline block's last step again, this time with its pair values (the cost image's entries)
+        metric.setProjectionMatrices(poses[(args.steps - 1) % len(poses)])
+        pair_sum, pair_values = metric.evaluate_range(0, n_pairs, want_pairs=True)
+        if not abs(pair_sum / n_pairs - last) <= 1e-9 * abs(last):
+            raise SystemExit("the pair values of the last step's pose do not add up to its mean: %r vs %r" % (pair_sum / n_pairs, last))
+        dump_outputs(args.dump_outputs, {"ecc_mean": np.array([last], np.float64), "pair_values": pair_values})
     n_kappa = n_kappa_auto(S, S, B)
-    bytes_per_pair = 64 * n_kappa + 68            # 2 views x 2 signs x 4 taps x 4 B + K01 + result
-    launch_bytes = bytes_per_pair * count         # one launch = this rank's shard of pairs
-    achieved = launch_bytes / pair_s / 1e9 if pair_ms > 0 else 0.0
     exch_name = {"single": "none", "shm": "host shared memory", "collective": "all-reduce (%s)" % args.backend,
                  "rccl": "all-reduce (RCCL, issued by the library: ecc_metric_evaluate_range_allreduce)"}
-
-    # ---- which roof bounds the pair kernel -------------------------------------------------------------------
-    # The gather is served on chip (measured HBM traffic << algorithmic bytes), so the algorithmic bytes are priced
-    # against the roof they actually cross -- the CU's vector L1 -- and the kernel's instruction stream against the
-    # vector-ALU issue rate; `bound` is the roof with the larger fraction.  Instruction counts and HBM bytes per
-    # launch are PMC measurements (separate rocprofv3 --pmc passes of this bench, profiles/pmc_current.json); they
-    # are used only at N = 1 on the workload they were taken on.
-    l1_peak = L1_BYTES_PER_CLK_CU * N_CU * ENGINE_CLOCK_GHZ  # GB/s
-    roofs = {"l1": {"achieved": achieved, "peak": l1_peak, "unit": "GB/s", "frac": achieved / l1_peak,
-                    "note": "algorithmic gather bytes through the vector L1: %.0f B/clk/CU x %d CUs x %.1f GHz"
-                            % (L1_BYTES_PER_CLK_CU, N_CU, ENGINE_CLOCK_GHZ)}}
-    pmc = load_pmc("pairs_kernel<true, false>") if (world == 1 and (n, S, B) == (400, 1024, 768)) else None
-    pmc_origin = "separate rocprofv3 --pmc passes of bench.py --steps 5, profiles/pmc_current.json (%s); not this run" % (pmc or {}).get("_tag")
-    live = live_pmc(args) if (world == 1 and rank == 0 and not args.no_live_pmc) else None
-    if live:
-        pmc = {"SQ_INSTS_VALU": live["SQ_INSTS_VALU"], "FETCH_SIZE": live["FETCH_SIZE"], "WRITE_SIZE": 4.0 * count / 1024.0,
-               "SQ_INSTS_VMEM_RD": live["SQ_INSTS_VMEM_RD"], "_tag": "live"}
-        pmc_origin = ("measured in this run: one rocprofv3 --kernel-trace --pmc FETCH_SIZE SQ_INSTS_VALU SQ_INSTS_VMEM_RD pass over "
-                      "a child run of this bench (--steps 3), %d launches averaged; WRITE_SIZE taken as 4 B per pair" % live["dispatches"])
-    traffic, traffic_src = None, None
-    if pmc and "SQ_INSTS_VALU" in pmc and pair_ms > 0:
-        valu_peak = N_CU * SIMD_PER_CU * ENGINE_CLOCK_GHZ / VALU_CYCLES_PER_WAVE_INSTR  # G wave-instructions/s
-        valu_ach = pmc["SQ_INSTS_VALU"] / pair_s / 1e9
-        roofs["valu"] = {"achieved": valu_ach, "peak": valu_peak, "unit": "G wave-instr/s", "frac": valu_ach / valu_peak,
-                         "note": "SQ_INSTS_VALU = %.4g per launch (PMC, %s) at %.0f cycles per wave64 instruction on %d SIMDs"
-                                 % (pmc["SQ_INSTS_VALU"], pmc["_tag"], VALU_CYCLES_PER_WAVE_INSTR, N_CU * SIMD_PER_CU)}
-        if "SQ_INSTS_VMEM_RD" in pmc:
-            roofs["l1"]["gathers_per_launch"] = pmc["SQ_INSTS_VMEM_RD"]
-    # L2 hit rate of the pair kernel: a second, separate pass (the TCC counters do not fit beside FETCH_SIZE)
-    live_tcc = live_pmc(args, ("TCC_HIT_sum", "TCC_MISS_sum")) if live else None
-    if pmc and "FETCH_SIZE" in pmc and "WRITE_SIZE" in pmc:
-        traffic = int(2 * pmc["FETCH_SIZE"] * 1024 + pmc["WRITE_SIZE"] * 1024)
-        traffic_src = "2 x FETCH_SIZE + WRITE_SIZE (KiB -> B; gfx950 counts 128-B fabric reads as 64 B); " + pmc_origin
-        roofs["hbm_measured"] = {"achieved": traffic / pair_s / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                 "frac": traffic / pair_s / 1e9 / HBM_PEAK_GBS,
-                                 "achievable": HBM_ACHIEVABLE_GBS,
-                                 "frac_of_achievable": traffic / pair_s / 1e9 / HBM_ACHIEVABLE_GBS,
-                                 "note": "bytes the launch moved through the fabric (PMC) per second; `achievable` = what a float4 copy "
-                                         "reaches on this part (the guide's measured 6.29 TB/s): the roof a kernel can actually touch"}
-    # SURVEY.md 8(d)'s compulsory figure: every Radon intermediate read once + the per-view geometry + one float per pair
-    hbm_compulsory = 4 * n * B * B + 64 * n + 4 * count
-    if power_report and power_report.get("pair_steps"):
-        scale = ENGINE_CLOCK_GHZ * 1e3 / power_report["pair_steps"]["sclk_mhz_avg"]
-        for r in ("l1", "valu"):
-            if r in roofs:
-                roofs[r]["frac_at_measured_clock"] = roofs[r]["frac"] * scale
-                roofs[r]["measured_clock_mhz"] = power_report["pair_steps"]["sclk_mhz_avg"]
-    # The binding roof: every roof priced against what can actually be reached -- the measured HBM bytes against the achievable
-    # bandwidth, not the spec sheet's (round 5's verdict: against 6.29 TB/s HBM is the tightest of the three).
-    bound_key = max(roofs, key=lambda r: roofs[r].get("frac_of_achievable", roofs[r]["frac"]))
-    bound = {"hbm_measured": "hbm"}.get(bound_key, bound_key)
-    # on-chip / off-chip split: the same 79 800 pair geometries sampling only EIGHT Radon intermediates (view v -> v mod 8: 39 MB of
-    # row-paired copies, resident in the Infinity Cache) -- the launch with its HBM misses taken away
-    cache_resident_ms, one_slab_ms = None, None
-    if world == 1 and rank == 0 and not args.pmc_child and n >= 16:
-        ii, jj = np.triu_indices(n, 1)
-        out8 = np.empty(len(ii), np.float32)
+    if args.full:
+        # pair-kernel duration: HIP events on the context's stream around the pair kernel alone, averaged over a
+        # second, untimed pass over the same steps (at most 50)
         ctx.enable_timing(True)
-        res_ms = {}
-        for alias in (8, 1):
-            m8 = E.MetricRadonIntermediate(ctx, Ps, dtrs[:alias])
-            idx8 = np.ascontiguousarray(np.stack([ii, jj, ii % alias, jj % alias], axis=1).astype(np.int32))
-            ts = []
-            for rep in range(6):
-                m8.evaluate(idx8, out8)
-                ts.append(ctx.last_kernel_ms("pairs"))
-            res_ms[alias] = float(np.median(ts[1:]))
-            m8.close()
-        cache_resident_ms, one_slab_ms = res_ms[8], res_ms[1]
-    roofline = {"bound": bound, "bound_roof": bound_key, "achieved": roofs[bound_key]["achieved"], "peak": roofs[bound_key]["peak"],
-                "unit": roofs[bound_key]["unit"], "frac": roofs[bound_key]["frac"],
-                "frac_of_achievable": roofs[bound_key].get("frac_of_achievable"), "traffic": traffic,
-                "kernel_ms_cache_resident": cache_resident_ms, "kernel_ms_one_slab": one_slab_ms,
-                "kernel_ms_cache_resident_note": "pairs_kernel over the same pair geometries with every view's Radon intermediate aliased to "
-                                                 "one of 8 (index list i, j, i mod 8, j mod 8; 39 MB of row-paired copies: Infinity-Cache resident) -- what the launch takes when "
-                                                 "nothing misses to HBM; kernel_ms_one_slab: all views aliased to ONE (4.9 MB: mostly L2 resident)",
-                "traffic_source": traffic_src, "kernel": "pairs_kernel<true, false>", "kernel_ms": pair_ms,
-                "algorithmic_bytes_per_launch": launch_bytes, "roofs": roofs,
-                "hbm_compulsory_bytes": hbm_compulsory,
-                "traffic_over_compulsory": (traffic / hbm_compulsory) if traffic else None,
-                "l2_hit_rate": (live_tcc["TCC_HIT_sum"] / (live_tcc["TCC_HIT_sum"] + live_tcc["TCC_MISS_sum"]))
-                if (live_tcc and live_tcc["TCC_HIT_sum"] + live_tcc["TCC_MISS_sum"] > 0) else None,
-                "l2_hit_rate_source": ("measured in this run: a second rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum pass over a child run "
-                                       "of this bench, %d launches averaged" % live_tcc["dispatches"]) if live_tcc else None,
-                # SURVEY.md 8(d)'s figure against HBM peak: > 1 means the gather's reuse is captured on chip
-                "hbm_algorithmic": {"achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                    "reuse_factor_vs_hbm_peak": achieved / HBM_PEAK_GBS}}
+        pair_ms, n_timed = 0.0, max(1, min(args.steps, 50))
+        for k in range(n_timed):
+            step(k)
+            pair_ms += ctx.last_kernel_ms("pairs")
+        fence()
+        pair_ms /= n_timed
+        pair_s = pair_ms * 1e-3
+        # socket power and engine clock while the same steps run back to back (untimed, ~1.5 s; the first 0.5 s dropped: the
+        # reading is a moving average and the controller takes about a second to settle at the cap)
+        ctx.enable_timing(False)
+        n_power = 0 if (args.no_power or args.pmc_child) else int(min(20000, max(200, 1.5 / max(elapsed / args.steps, 1e-6))))  # (elapsed is the MAX over ranks: the same count everywhere)
+        fence()
+        power.start()
+        t_p = time.perf_counter()
+        for k in range(n_power):
+            step(k)
+        fence()
+        t_p = time.perf_counter() - t_p
+        power_steps = power.stop(skip_s=0.5) if n_power else (power.stop() and None)
+        if power_steps:
+            power_steps["ms_per_step_while_sampling"] = 1e3 * t_p / n_power
+            power_steps["steps"] = n_power
+        ctx.enable_timing(True)
 
-    # ---- second headline metric: ms per Radon intermediate ---------------------------------------------------
-    # The Radon kernel reads its bilinear footprints from an LDS tile of texel pairs with ds_read_b64 (2 per fetch,
-    # 16 B); since round 3 its binding roof is vector-ALU issue, not the LDS pipe.  `frac` is the binding roof's
-    # fraction; the algorithmic LDS bytes are priced against both LDS rates for continuity with rounds 1-2.
-    fetches = radon_fetches_per_image(S, S, B, B)
-    lds_peak_b32 = LDS_READ2_B32_BYTES_PER_CLK_CU * N_CU * ENGINE_CLOCK_GHZ
-    lds_peak_b64 = LDS_READ_B64_BYTES_PER_CLK_CU * N_CU * ENGINE_CLOCK_GHZ
-    lds_ach = 16.0 * fetches / (ms_per_radon * 1e-3) / 1e9 if ms_per_radon > 0 else 0.0
-    roofs_r = {"lds_algorithmic_b64": {"achieved": lds_ach, "peak": lds_peak_b64, "unit": "GB/s", "frac": lds_ach / lds_peak_b64,
-                                       "note": "16 B per bilinear fetch (2 x ds_read_b64) against %.0f B/clk/CU x %d CUs x %.1f GHz"
-                                               % (LDS_READ_B64_BYTES_PER_CLK_CU, N_CU, ENGINE_CLOCK_GHZ)},
-               "lds_algorithmic_b32": {"achieved": lds_ach, "peak": lds_peak_b32, "unit": "GB/s", "frac": lds_ach / lds_peak_b32,
-                                       "note": "the same bytes against the ds_read2_b32 rate (128 B/clk/CU) rounds 1-2 were priced on"}}
-    roofline_radon = {"kernel": "radon_kernel<true, false> (derivative, exact arithmetic)", "kernel_ms_per_image": ms_per_radon,
-                      "algorithmic_bytes_per_image": 16 * fetches, "bilinear_fetches_per_image": fetches,
-                      "compulsory_hbm_bytes_per_image": 4 * (S * S + B * B)}
-    rp = load_pmc("radon_kernel<true, false>") if (S, B) == (1024, 768) else None
-    if rp and rp.get("SQ_LDS_IDX_ACTIVE"):
-        roofline_radon["lds_bank_conflict_ratio"] = rp["SQ_LDS_BANK_CONFLICT"] / rp["SQ_LDS_IDX_ACTIVE"]
-        roofline_radon["pmc_source"] = ("SQ_LDS_BANK_CONFLICT, SQ_LDS_IDX_ACTIVE, SQ_INSTS_VALU per 50-image launch: separate rocprofv3 --pmc "
-                                        "passes, profiles/pmc_current.json (%s); not this run" % rp["_tag"])
-        # the committed passes (scripts/pmc_radon.sh on scripts/bench_radon.py) profile launches of 50 images each
-        img_s = ms_per_radon * 1e-3
-        roofs_r["lds_pipe_active"] = {"frac": rp["SQ_LDS_IDX_ACTIVE"] / sub / (N_CU * ENGINE_CLOCK_GHZ * 1e9 * img_s),
-                                      "note": "SQ_LDS_IDX_ACTIVE cycles per image / (256 CUs x 2.4 GHz x seconds per image): bank "
-                                              "conflicts included"}
-        if rp.get("SQ_INSTS_VALU"):
+        # the same steps with the record reuse switched off (every step refits all pairs and launches e1_kernel): the
+        # results are bit-identical, only the fixed cost per step differs
+        ctx.enable_timing(False)
+        metric.setRecordReuse(False)
+        for k in range(args.warmup):
+            step(k)
+        off_blocks = []
+        for b in range(3):
+            el_off, last_off = timed_block(step, b * args.steps)
+            off_blocks.append(el_off)
+        v_off = [step(k) for k in (3, 4, 4, 11)]
+        metric.setRecordReuse(True)
+        v_on = [step(k) for k in (3, 4, 4, 11)]
+        reuse_off_s = sorted(off_blocks)[1]
+        if v_on != v_off:
+            raise SystemExit("record reuse changed the results: %r vs %r" % (v_on, v_off))
+
+        # ---- socket power and engine clock (hwmon) --------------------------------------------------------------------------
+        # Both kernels run INTO THE POWER CAP: the socket reads 1395-1399 W of its 1400 W while the steps run back to back and
+        # the engine clock settles near 2.2 GHz, below the 2.4 GHz every roof here is priced at.  At the cap a kernel's time
+        # follows the ENERGY of its instruction and data stream, not the issue slots of one pipe: cutting instructions returns
+        # well under its share (CHANGELOG.md 4.2 has five rounds of such cuts), and idle XCDs at the end of a launch cost
+        # nothing (the remaining ones clock up: CHANGELOG.md round 5, XCD schedule).  `frac_at_measured_clock` restates the two
+        # clock-bound roofs against the clock the chip actually ran at.
+        power_report = None
+        if power.dir and rank == 0:
+            cap, rated = power.cap_w(), power.rated_mhz()
+            power_report = {"source": "amdgpu hwmon power1_input / freq1_input, 2-ms samples, outside the timed blocks",
+                            "cap_w": cap, "sclk_rated_mhz": rated,
+                            "before_first_launch": {"w": power_first[0], "sclk_mhz": power_first[1]} if power_first else None,
+                            "pair_steps": power_steps, "radon_stack": power_radon,
+                            "radon_stack_note": "one call of about 0.2 s: the power reading (a moving average) is still rising when it ends"}
+            if power_steps and cap:
+                power_report["pair_steps"]["frac_of_cap"] = power_steps["avg_w"] / cap
+
+        bytes_per_pair = 64 * n_kappa + 68            # 2 views x 2 signs x 4 taps x 4 B + K01 + result
+        launch_bytes = bytes_per_pair * count         # one launch = this rank's shard of pairs
+        achieved = launch_bytes / pair_s / 1e9 if pair_ms > 0 else 0.0
+
+        # ---- which roof bounds the pair kernel -------------------------------------------------------------------
+        # The gather is served on chip (measured HBM traffic << algorithmic bytes), so the algorithmic bytes are priced
+        # against the roof they actually cross -- the CU's vector L1 -- and the kernel's instruction stream against the
+        # vector-ALU issue rate; `bound` is the roof with the larger fraction.  Instruction counts and HBM bytes per
+        # launch are PMC measurements (separate rocprofv3 --pmc passes of this bench, profiles/pmc_current.json); they
+        # are used only at N = 1 on the workload they were taken on.
+        l1_peak = L1_BYTES_PER_CLK_CU * N_CU * ENGINE_CLOCK_GHZ  # GB/s
+        roofs = {"l1": {"achieved": achieved, "peak": l1_peak, "unit": "GB/s", "frac": achieved / l1_peak,
+                        "note": "algorithmic gather bytes through the vector L1: %.0f B/clk/CU x %d CUs x %.1f GHz"
+                                % (L1_BYTES_PER_CLK_CU, N_CU, ENGINE_CLOCK_GHZ)}}
+        pmc = load_pmc("pairs_kernel<true, false>") if (world == 1 and (n, S, B) == (400, 1024, 768)) else None
+        pmc_origin = "separate rocprofv3 --pmc passes of bench.py --steps 5, profiles/pmc_current.json (%s); not this run" % (pmc or {}).get("_tag")
+        live = live_pmc(args) if (world == 1 and rank == 0 and not args.no_live_pmc) else None
+        if live:
+            pmc = {"SQ_INSTS_VALU": live["SQ_INSTS_VALU"], "FETCH_SIZE": live["FETCH_SIZE"], "WRITE_SIZE": 4.0 * count / 1024.0,
+                   "SQ_INSTS_VMEM_RD": live["SQ_INSTS_VMEM_RD"], "_tag": "live"}
+            pmc_origin = ("measured in this run: one rocprofv3 --kernel-trace --pmc FETCH_SIZE SQ_INSTS_VALU SQ_INSTS_VMEM_RD pass over "
+                          "a child run of this bench (--steps 3), %d launches averaged; WRITE_SIZE taken as 4 B per pair" % live["dispatches"])
+        traffic, traffic_src = None, None
+        if pmc and "SQ_INSTS_VALU" in pmc and pair_ms > 0:
             valu_peak = N_CU * SIMD_PER_CU * ENGINE_CLOCK_GHZ / VALU_CYCLES_PER_WAVE_INSTR  # G wave-instructions/s
-            valu_ach = rp["SQ_INSTS_VALU"] / sub / img_s / 1e9
-            roofs_r["valu"] = {"achieved": valu_ach, "peak": valu_peak, "unit": "G wave-instr/s", "frac": valu_ach / valu_peak,
-                               "note": "SQ_INSTS_VALU = %.4g per image at 2 cycles per wave64 instruction on 1024 SIMDs (the 4-cycle "
-                                       "v_floor_f32 count as 2: a lower bound of the pipe's occupancy)" % (rp["SQ_INSTS_VALU"] / sub)}
-    # the contracted-arithmetic mode (ecc_radon_set_arithmetic(ECC_RADON_FMA)) against the same two roofs, from its own PMC pass
-    rf = load_pmc("radon_kernel<true, true>") if (S, B) == (1024, 768) else None
-    if rf and rf.get("SQ_INSTS_VALU") and rf.get("SQ_LDS_IDX_ACTIVE") and ms_per_radon_fma > 0:
-        img_f = ms_per_radon_fma * 1e-3
-        roofline_radon["fma_mode"] = {
-            "kernel": "radon_kernel<true, true>", "kernel_ms_per_image": ms_per_radon_fma,
-            "valu_frac": rf["SQ_INSTS_VALU"] / sub / img_f / 1e9 / (N_CU * SIMD_PER_CU * ENGINE_CLOCK_GHZ / VALU_CYCLES_PER_WAVE_INSTR),
-            "lds_pipe_active_frac": rf["SQ_LDS_IDX_ACTIVE"] / sub / (N_CU * ENGINE_CLOCK_GHZ * 1e9 * img_f),
-            "wave_instructions_per_image": rf["SQ_INSTS_VALU"] / sub,
-            "note": "both pipes are 0.6-0.7 busy: the contracted loop (40 instead of 52 vector instructions per step) is no longer "
-                    "bound by vector issue alone"}
-    binding = max(roofs_r, key=lambda r: roofs_r[r]["frac"] if r != "lds_algorithmic_b32" else -1.0)
-    roofline_radon.update({"bound": {"valu": "valu", "lds_pipe_active": "lds"}.get(binding, "lds"), "binding": binding,
-                           "achieved": roofs_r[binding].get("achieved"), "peak": roofs_r[binding].get("peak"),
-                           "unit": roofs_r[binding].get("unit"), "frac": roofs_r[binding]["frac"], "traffic": None,
-                           "roofs": roofs_r})
+            valu_ach = pmc["SQ_INSTS_VALU"] / pair_s / 1e9
+            roofs["valu"] = {"achieved": valu_ach, "peak": valu_peak, "unit": "G wave-instr/s", "frac": valu_ach / valu_peak,
+                             "note": "SQ_INSTS_VALU = %.4g per launch (PMC, %s) at %.0f cycles per wave64 instruction on %d SIMDs"
+                                     % (pmc["SQ_INSTS_VALU"], pmc["_tag"], VALU_CYCLES_PER_WAVE_INSTR, N_CU * SIMD_PER_CU)}
+            if "SQ_INSTS_VMEM_RD" in pmc:
+                roofs["l1"]["gathers_per_launch"] = pmc["SQ_INSTS_VMEM_RD"]
+        # L2 hit rate of the pair kernel: a second, separate pass (the TCC counters do not fit beside FETCH_SIZE)
+        live_tcc = live_pmc(args, ("TCC_HIT_sum", "TCC_MISS_sum")) if live else None
+        if pmc and "FETCH_SIZE" in pmc and "WRITE_SIZE" in pmc:
+            traffic = int(2 * pmc["FETCH_SIZE"] * 1024 + pmc["WRITE_SIZE"] * 1024)
+            traffic_src = "2 x FETCH_SIZE + WRITE_SIZE (KiB -> B; gfx950 counts 128-B fabric reads as 64 B); " + pmc_origin
+            roofs["hbm_measured"] = {"achieved": traffic / pair_s / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                     "frac": traffic / pair_s / 1e9 / HBM_PEAK_GBS,
+                                     "achievable": HBM_ACHIEVABLE_GBS,
+                                     "frac_of_achievable": traffic / pair_s / 1e9 / HBM_ACHIEVABLE_GBS,
+                                     "note": "bytes the launch moved through the fabric (PMC) per second; `achievable` = what a float4 copy "
+                                             "reaches on this part (the guide's measured 6.29 TB/s): the roof a kernel can actually touch"}
+        # SURVEY.md 8(d)'s compulsory figure: every Radon intermediate read once + the per-view geometry + one float per pair
+        hbm_compulsory = 4 * n * B * B + 64 * n + 4 * count
+        if power_report and power_report.get("pair_steps"):
+            scale = ENGINE_CLOCK_GHZ * 1e3 / power_report["pair_steps"]["sclk_mhz_avg"]
+            for r in ("l1", "valu"):
+                if r in roofs:
+                    roofs[r]["frac_at_measured_clock"] = roofs[r]["frac"] * scale
+                    roofs[r]["measured_clock_mhz"] = power_report["pair_steps"]["sclk_mhz_avg"]
+        # The binding roof: every roof priced against what can actually be reached -- the measured HBM bytes against the achievable
+        # bandwidth, not the spec sheet's (round 5's verdict: against 6.29 TB/s HBM is the tightest of the three).
+        bound_key = max(roofs, key=lambda r: roofs[r].get("frac_of_achievable", roofs[r]["frac"]))
+        bound = {"hbm_measured": "hbm"}.get(bound_key, bound_key)
+        # on-chip / off-chip split: the same 79 800 pair geometries sampling only EIGHT Radon intermediates (view v -> v mod 8: 39 MB of
+        # row-paired copies, resident in the Infinity Cache) -- the launch with its HBM misses taken away
+        cache_resident_ms, one_slab_ms = None, None
+        if world == 1 and rank == 0 and not args.pmc_child and n >= 16:
+            ii, jj = np.triu_indices(n, 1)
+            out8 = np.empty(len(ii), np.float32)
+            ctx.enable_timing(True)
+            res_ms = {}
+            for alias in (8, 1):
+                m8 = E.MetricRadonIntermediate(ctx, Ps, dtrs[:alias])
+                idx8 = np.ascontiguousarray(np.stack([ii, jj, ii % alias, jj % alias], axis=1).astype(np.int32))
+                ts = []
+                for rep in range(6):
+                    m8.evaluate(idx8, out8)
+                    ts.append(ctx.last_kernel_ms("pairs"))
+                res_ms[alias] = float(np.median(ts[1:]))
+                m8.close()
+            cache_resident_ms, one_slab_ms = res_ms[8], res_ms[1]
+        roofline = {"bound": bound, "bound_roof": bound_key, "achieved": roofs[bound_key]["achieved"], "peak": roofs[bound_key]["peak"],
+                    "unit": roofs[bound_key]["unit"], "frac": roofs[bound_key]["frac"],
+                    "frac_of_achievable": roofs[bound_key].get("frac_of_achievable"), "traffic": traffic,
+                    "kernel_ms_cache_resident": cache_resident_ms, "kernel_ms_one_slab": one_slab_ms,
+                    "kernel_ms_cache_resident_note": "pairs_kernel over the same pair geometries with every view's Radon intermediate aliased to "
+                                                     "one of 8 (index list i, j, i mod 8, j mod 8; 39 MB of row-paired copies: Infinity-Cache resident) -- what the launch takes when "
+                                                     "nothing misses to HBM; kernel_ms_one_slab: all views aliased to ONE (4.9 MB: mostly L2 resident)",
+                    "traffic_source": traffic_src, "kernel": "pairs_kernel<true, false>", "kernel_ms": pair_ms,
+                    "algorithmic_bytes_per_launch": launch_bytes, "roofs": roofs,
+                    "hbm_compulsory_bytes": hbm_compulsory,
+                    "traffic_over_compulsory": (traffic / hbm_compulsory) if traffic else None,
+                    "l2_hit_rate": (live_tcc["TCC_HIT_sum"] / (live_tcc["TCC_HIT_sum"] + live_tcc["TCC_MISS_sum"]))
+                    if (live_tcc and live_tcc["TCC_HIT_sum"] + live_tcc["TCC_MISS_sum"] > 0) else None,
+                    "l2_hit_rate_source": ("measured in this run: a second rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum pass over a child run "
+                                           "of this bench, %d launches averaged" % live_tcc["dispatches"]) if live_tcc else None,
+                    # SURVEY.md 8(d)'s figure against HBM peak: > 1 means the gather's reuse is captured on chip
+                    "hbm_algorithmic": {"achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                        "reuse_factor_vs_hbm_peak": achieved / HBM_PEAK_GBS}}
+
+        # ---- second headline metric: ms per Radon intermediate ---------------------------------------------------
+        # The Radon kernel reads its bilinear footprints from an LDS tile of texel pairs with ds_read_b64 (2 per fetch,
+        # 16 B); since round 3 its binding roof is vector-ALU issue, not the LDS pipe.  `frac` is the binding roof's
+        # fraction; the algorithmic LDS bytes are priced against both LDS rates for continuity with rounds 1-2.
+        fetches = radon_fetches_per_image(S, S, B, B)
+        lds_peak_b32 = LDS_READ2_B32_BYTES_PER_CLK_CU * N_CU * ENGINE_CLOCK_GHZ
+        lds_peak_b64 = LDS_READ_B64_BYTES_PER_CLK_CU * N_CU * ENGINE_CLOCK_GHZ
+        lds_ach = 16.0 * fetches / (ms_per_radon * 1e-3) / 1e9 if ms_per_radon > 0 else 0.0
+        roofs_r = {"lds_algorithmic_b64": {"achieved": lds_ach, "peak": lds_peak_b64, "unit": "GB/s", "frac": lds_ach / lds_peak_b64,
+                                           "note": "16 B per bilinear fetch (2 x ds_read_b64) against %.0f B/clk/CU x %d CUs x %.1f GHz"
+                                                   % (LDS_READ_B64_BYTES_PER_CLK_CU, N_CU, ENGINE_CLOCK_GHZ)},
+                   "lds_algorithmic_b32": {"achieved": lds_ach, "peak": lds_peak_b32, "unit": "GB/s", "frac": lds_ach / lds_peak_b32,
+                                           "note": "the same bytes against the ds_read2_b32 rate (128 B/clk/CU) rounds 1-2 were priced on"}}
+        roofline_radon = {"kernel": "radon_kernel<true, false> (derivative, exact arithmetic)", "kernel_ms_per_image": ms_per_radon,
+                          "algorithmic_bytes_per_image": 16 * fetches, "bilinear_fetches_per_image": fetches,
+                          "compulsory_hbm_bytes_per_image": 4 * (S * S + B * B)}
+        rp = load_pmc("radon_kernel<true, false>") if (S, B) == (1024, 768) else None
+        if rp and rp.get("SQ_LDS_IDX_ACTIVE"):
+            roofline_radon["lds_bank_conflict_ratio"] = rp["SQ_LDS_BANK_CONFLICT"] / rp["SQ_LDS_IDX_ACTIVE"]
+            roofline_radon["pmc_source"] = ("SQ_LDS_BANK_CONFLICT, SQ_LDS_IDX_ACTIVE, SQ_INSTS_VALU per 50-image launch: separate rocprofv3 --pmc "
+                                            "passes, profiles/pmc_current.json (%s); not this run" % rp["_tag"])
+            # the committed passes (scripts/pmc_radon.sh on scripts/bench_radon.py) profile launches of 50 images each
+            img_s = ms_per_radon * 1e-3
+            roofs_r["lds_pipe_active"] = {"frac": rp["SQ_LDS_IDX_ACTIVE"] / sub / (N_CU * ENGINE_CLOCK_GHZ * 1e9 * img_s),
+                                          "note": "SQ_LDS_IDX_ACTIVE cycles per image / (256 CUs x 2.4 GHz x seconds per image): bank "
+                                                  "conflicts included"}
+            if rp.get("SQ_INSTS_VALU"):
+                valu_peak = N_CU * SIMD_PER_CU * ENGINE_CLOCK_GHZ / VALU_CYCLES_PER_WAVE_INSTR  # G wave-instructions/s
+                valu_ach = rp["SQ_INSTS_VALU"] / sub / img_s / 1e9
+                roofs_r["valu"] = {"achieved": valu_ach, "peak": valu_peak, "unit": "G wave-instr/s", "frac": valu_ach / valu_peak,
+                                   "note": "SQ_INSTS_VALU = %.4g per image at 2 cycles per wave64 instruction on 1024 SIMDs (the 4-cycle "
+                                           "v_floor_f32 count as 2: a lower bound of the pipe's occupancy)" % (rp["SQ_INSTS_VALU"] / sub)}
+        # the contracted-arithmetic mode (ecc_radon_set_arithmetic(ECC_RADON_FMA)) against the same two roofs, from its own PMC pass
+        rf = load_pmc("radon_kernel<true, true>") if (S, B) == (1024, 768) else None
+        if rf and rf.get("SQ_INSTS_VALU") and rf.get("SQ_LDS_IDX_ACTIVE") and ms_per_radon_fma > 0:
+            img_f = ms_per_radon_fma * 1e-3
+            roofline_radon["fma_mode"] = {
+                "kernel": "radon_kernel<true, true>", "kernel_ms_per_image": ms_per_radon_fma,
+                "valu_frac": rf["SQ_INSTS_VALU"] / sub / img_f / 1e9 / (N_CU * SIMD_PER_CU * ENGINE_CLOCK_GHZ / VALU_CYCLES_PER_WAVE_INSTR),
+                "lds_pipe_active_frac": rf["SQ_LDS_IDX_ACTIVE"] / sub / (N_CU * ENGINE_CLOCK_GHZ * 1e9 * img_f),
+                "wave_instructions_per_image": rf["SQ_INSTS_VALU"] / sub,
+                "note": "both pipes are 0.6-0.7 busy: the contracted loop (40 instead of 52 vector instructions per step) is no longer "
+                        "bound by vector issue alone"}
+        binding = max(roofs_r, key=lambda r: roofs_r[r]["frac"] if r != "lds_algorithmic_b32" else -1.0)
+        roofline_radon.update({"bound": {"valu": "valu", "lds_pipe_active": "lds"}.get(binding, "lds"), "binding": binding,
+                               "achieved": roofs_r[binding].get("achieved"), "peak": roofs_r[binding].get("peak"),
+                               "unit": roofs_r[binding].get("unit"), "frac": roofs_r[binding]["frac"], "traffic": None,
+                               "roofs": roofs_r})
 
     out = {
         "metric": "ECC evaluations/sec (N=%d, %d^2 projections)" % (n, S),
@@ -1115,51 +1152,56 @@ def main():
                    # library default: the per-pair geometry records of pairs whose two matrices did not change since the
                    # last step are kept (one view moves per step: 399 of 79 800 pairs are refitted, E1 of the moved view
                    # on the host, no e1_kernel launch); every pair is sampled; bit-identical results
-                   "k01_record_reuse": "on (library default); the same run with it off under timing.record_reuse_off",
+                   "k01_record_reuse": "on (library default); with --full the same steps with it off under timing.record_reuse_off",
                    "ranks_seen_by_collective_backend": ranks_seen, "devices": devices_seen,
-                   "force_collective": bool(args.force_collective)},
-        "timing": {"value_is": "median of %d blocks of %d steps" % (len(res["blocks"]), args.steps),
-                   # round 1's definition of the headline: all timed steps of the run over all their time
-                   "whole_run": {"ms_per_step": 1e3 * sum(res["blocks"]) / (args.steps * len(res["blocks"])),
-                                 "value": args.steps * len(res["blocks"]) / sum(res["blocks"])},
-                   "blocks_ms_per_step": [1e3 * b / args.steps for b in res["blocks"]],
-                   "cold": {"ms_per_step": 1e3 * res["cold"] / args.steps, "value": args.steps / res["cold"],
-                            "note": "first block after the %d warm-up steps" % args.warmup},
-                   "record_reuse_off": {"ms_per_step": 1e3 * reuse_off_s / args.steps, "value": args.steps / reuse_off_s,
-                                        "non_pair_kernel_us_per_step": 1e3 * (1e3 * reuse_off_s / args.steps - pair_ms),
-                                        "note": "median of 3 blocks with ecc_metric_set_record_reuse(0): e1_kernel + k01_kernel "
-                                                "over all pairs every step; same result bits"}},
-        "roofline": roofline,
-        "roofline_radon": roofline_radon,
-        "power": power_report,
+                   "force_collective": bool(args.force_collective), "full": bool(args.full)},
+        "timing": {"value_is": "one block of %d steps after %d warm-up steps" % (args.steps, args.warmup)},
         "ms_per_radon_intermediate": ms_per_radon,
-        "ms_per_radon_intermediate_by_arithmetic": {
-            "exact": ms_per_radon, "fma": ms_per_radon_fma,
-            "headline_mode": "exact (library default: unfused fp32, bit-identical to the oracle's normative variant); fma = "
-                             "ecc_radon_set_arithmetic(ECC_RADON_FMA), bit-identical to the oracle's contracted variant",
-            "metric_tie": radon_tie},
-        "ms_per_preprocess": ms_per_preprocess,
-        "preprocess_hbm_GBs": 8.0 * S * S / (ms_per_preprocess * 1e-3) / 1e9 if ms_per_preprocess > 0 else 0.0,
         "pairs_per_s": n_pairs * args.steps / elapsed,
         "kappa_samples_per_s": n_pairs * n_kappa * args.steps / elapsed,
-        "non_pair_kernel_us_per_step": 1e3 * (1e3 * elapsed / args.steps - pair_ms),
         "pairs_evaluated_last_step": metric.last_evaluated_pairs(),  # the library's own count: this rank's whole shard
         "last_value": last,
     }
-    others = [{"sum_exchange": exch_name[m], "ms_per_step": 1e3 * results[m]["steady"] / args.steps,
-               "value": args.steps / results[m]["steady"], "cold_ms_per_step": 1e3 * results[m]["cold"] / args.steps}
-              for m in modes if m != best]
-    out["timing"]["other_exchange"] = others  # always a list (advisor, round 5: one schema whatever the number of modes)
+    if args.full:
+        out["timing"].update({
+            # rounds 1-6's headline: the median of the K-step blocks, the headline's block first
+            "median_block": {"ms_per_step": 1e3 * res["steady"] / args.steps, "value": args.steps / res["steady"],
+                             "note": "median of %d blocks of %d steps" % (len(res["blocks"]), args.steps)},
+            # round 1's definition of the headline: all timed steps of the run over all their time
+            "whole_run": {"ms_per_step": 1e3 * sum(res["blocks"]) / (args.steps * len(res["blocks"])),
+                          "value": args.steps * len(res["blocks"]) / sum(res["blocks"])},
+            "blocks_ms_per_step": [1e3 * b / args.steps for b in res["blocks"]],
+            "cold": {"ms_per_step": 1e3 * res["cold"] / args.steps, "value": args.steps / res["cold"],
+                     "note": "first block after the %d warm-up steps" % args.warmup},
+            "record_reuse_off": {"ms_per_step": 1e3 * reuse_off_s / args.steps, "value": args.steps / reuse_off_s,
+                                 "non_pair_kernel_us_per_step": 1e3 * (1e3 * reuse_off_s / args.steps - pair_ms),
+                                 "note": "median of 3 blocks with ecc_metric_set_record_reuse(0): e1_kernel + k01_kernel "
+                                         "over all pairs every step; same result bits"},
+            "other_exchange": [{"sum_exchange": exch_name[m], "ms_per_step": 1e3 * results[m]["steady"] / args.steps,
+                                "value": args.steps / results[m]["steady"], "cold_ms_per_step": 1e3 * results[m]["cold"] / args.steps}
+                               for m in modes if m != best]})  # always a list (advisor, round 5: one schema whatever the number of modes)
+        out.update({
+            "roofline": roofline,
+            "roofline_radon": roofline_radon,
+            "power": power_report,
+            "ms_per_radon_intermediate_by_arithmetic": {
+                "exact": ms_per_radon, "fma": ms_per_radon_fma,
+                "headline_mode": "exact (library default: unfused fp32, bit-identical to the oracle's normative variant); fma = "
+                                 "ecc_radon_set_arithmetic(ECC_RADON_FMA), bit-identical to the oracle's contracted variant",
+                "metric_tie": radon_tie},
+            "ms_per_preprocess": ms_per_preprocess,
+            "preprocess_hbm_GBs": 8.0 * S * S / (ms_per_preprocess * 1e-3) / 1e9 if ms_per_preprocess > 0 else 0.0,
+            "non_pair_kernel_us_per_step": 1e3 * (1e3 * elapsed / args.steps - pair_ms)})
     if grouped:
         # what every rank actually used: the exchanges it timed, the one behind `value`, and how its ncclCommInitRank went
-        mine_status = {"rank": rank, "exchanges_timed": [exch_name[m] for m in modes], "value_is": exch_name[best],
+        mine_status = {"rank": rank, "exchanges_timed": [exch_name[m] for m in results], "value_is": exch_name[best],
                        "ecc_comm_create": comm_status}
         statuses = [None] * world
         dist.all_gather_object(statuses, mine_status)
         out["config"]["exchange_per_rank"] = statuses
 
     # ---- CPU baseline: the oracle timed on this box's host cores (rank 0, N = 1 only) -----------
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         import oracle
         oracle.build(native=True)
         cpu = host_cpu_info()

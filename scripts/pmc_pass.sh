@@ -2,10 +2,12 @@
 # usage: scripts/pmc_pass.sh <tag> <counters...>   (GPU box; one rocprofv3 --pmc pass, kernel-trace only)
 set -e
 tag=$1; shift
+R=$(cd "$(dirname "$0")/.." && pwd)
+OUT=${OUT:-$R/bench_out}; export OUT; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-out=$GRAFT_REPO_ROOT/gpurun_out/pmc_$tag
+out=$OUT/pmc_$tag
 rm -rf $out
-timeout -k 10 400 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $out -- python3 $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-live-pmc --no-power > $GRAFT_REPO_ROOT/gpurun_out/pmc_$tag.log 2>&1
+timeout -k 10 400 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $out -- python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-live-pmc --no-power > $OUT/pmc_$tag.log 2>&1
 python3 - <<PY
 import csv, glob, collections, re
 rows=[]
@@ -26,7 +28,7 @@ for r in rows:
         per[(m.group(1), r["Dispatch_Id"], r["Counter_Name"])] += float(r["Counter_Value"])
 acc=collections.defaultdict(lambda: collections.defaultdict(list))
 for (name, d, c), v in per.items(): acc[name][c].append(v)
-with open("$GRAFT_REPO_ROOT/gpurun_out/pmc_$tag.summary.txt","w") as f:
+with open("$OUT/pmc_$tag.summary.txt","w") as f:
     for k,v in sorted(acc.items()):
         line = k + " " + ", ".join("%s=%.6g (n=%d)" % (c, sum(x)/len(x), len(x)) for c,x in sorted(v.items()))
         print(line); f.write(line+"\n")

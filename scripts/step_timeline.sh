@@ -2,12 +2,13 @@
 # usage (GPU box): scripts/step_timeline.sh [env assignments...]  -- kernel start/end timestamps of the optimiser steps of
 # bench.py (rocprofv3 --kernel-trace): median duration of every kernel of a step and of the gaps between them
 # (BENCH_ARGS="--views 64 --size 512" as an env assignment: another workload)
+R=$(cd "$(dirname "$0")/.." && pwd)
+OUT=${OUT:-$R/bench_out}; export OUT; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
 for a in "$@"; do export "$a"; done
-out=$R/gpurun_out/timeline
+out=$OUT/timeline
 rm -rf $out
-timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $out -- python3 $R/bench.py --steps 20 --warmup 5 --blocks 3 --no-cpu-baseline --no-live-pmc $BENCH_ARGS > $R/gpurun_out/timeline.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $out -- python3 $R/bench.py --full --steps 20 --warmup 5 --blocks 3 --no-cpu-baseline --no-live-pmc $BENCH_ARGS > $OUT/timeline.log 2>&1
 python3 - <<PY
 import csv, glob, collections, statistics as st
 f = glob.glob("$out/**/*kernel_trace.csv", recursive=True)[0]

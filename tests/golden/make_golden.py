@@ -18,6 +18,9 @@ container that has /root/reference):
   variants_128.npz      SURVEY.md 8c (a) and (d): every Radon filter / post-process on one 128x96 image at 96x80
                         bins; index-list, subset and user-parameter variants of the metric on the 8-view set.
 
+  reference_pins.npz, proj000_header.nrrd  what the reference's own headers return for the inputs of
+                        tests/test_oracle_pins.py, and the example file's header (see reference_pins()).
+
   radon_contract.npz    round 4: the CONTRACTED arithmetic variant of the Radon intermediate (eccor_set_radon_contract(1),
                         what ecc_radon_set_arithmetic(ECC_RADON_FMA) is held to bit for bit) on the three data sets above:
                         dtr checksums, sparse samples, and the metric evaluated on those dtrs next to the exact variant's.
@@ -195,13 +198,85 @@ def radon_contract():
     print("radon_contract: synthetic8 mean %.9g" % res["mean"])
 
 
+def reference_pins():
+    """reference_pins.npz: the inputs of tests/test_oracle_pins.py and what the reference's own headers (oracle/_ref/libecc_ref.so,
+    built by oracle/Makefile where the reference tree lies) return for them -- E1/E2 geometry, get_ij, computeK01 and the line
+    mapping (platform float libm), the weighting, the NRRD low-pass and image-view interpolation.  proj000_header.nrrd: the
+    header of config/example_data/proj000.nrrd; with the image of example_pair_native.npz it restores that file byte for byte."""
+    from test_oracle_pins import P000, P040, _random_Ps
+    r = oracle.ref()
+    assert r is not None, "oracle/_ref/libecc_ref.so is needed"
+    out = {}
+    Ps = np.stack([P000, P040] + _random_Ps(40))
+    out["e1_Ps"] = Ps
+    out["e1_pinvT"] = np.stack([oracle.pinvT(P, use_ref=True) for P in Ps])
+    out["e1_source_position"] = np.stack([oracle.source_position(P, use_ref=True) for P in Ps])
+    for n in (2, 3, 4, 5, 17, 64):
+        out["get_ij_%d" % n] = np.array([oracle.get_ij(ij, n, use_ref=True) for ij in range(n * (n - 1) // 2)], np.int32)
+    oracle.set_variant(2)  # the oracle's inputs to computeK01 as the test computes them (same libm as the reference headers)
+    try:
+        Ps = np.stack([P000, P040] + _random_Ps(12, seed=3))
+        rng = np.random.default_rng(1)
+        K, lines, mapped, moved = [], [], [], []
+        for a in range(0, len(Ps), 2):
+            P0, P1 = Ps[a], Ps[a + 1]
+            args = (512.0, 380.0, oracle.source_position(P0), oracle.source_position(P1),
+                    oracle.pinvT(P0), oracle.pinvT(P1), np.float32(106.75), np.float32(2550.4))
+            K.append([oracle.computeK01(*args, dk, use_ref=True) for dk in (0.0, 0.003)])
+            ls = [rng.normal(size=3).astype(np.float32) * np.float32([1, 1, 500]) for _ in range(200)]
+            res = [oracle.line_to_sample_dtr(line, 1275.2, use_ref=True) for line in ls]
+            lines.append(ls)
+            mapped.append([m for m, _ in res])
+            moved.append([v for _, v in res])
+    finally:
+        oracle.set_variant(0)
+    out.update(k01_Ps=Ps, k01_K=np.array(K, np.float32), line_in=np.array(lines, np.float32),
+               line_out=np.array(mapped, np.float32), line_moved=np.array(moved, bool))
+    xs = np.array([-2.0, -1.0, -0.5, 0.0, 0.3, 1.0, 1.5])
+    out["weighting_x"], out["weighting"] = xs, np.array([r.ref_weighting(x) for x in xs], np.float32)
+    gauss = ((1.84, 5), (1.0, 2), (0.7, 1), (3.3, 9), (2.5, 12), (10.0, 3))
+    out["gauss_params"] = np.array(gauss)
+    for i, (sigma, k) in enumerate(gauss):
+        g = np.zeros(2 * k + 1, np.float64)
+        r.ref_gaussian_kernel(sigma, k, g)
+        out["gauss_%d" % i] = g
+    rng = np.random.default_rng(21)
+    lowpass = (((50, 70), 1.84, 5), ((33, 17), 1.0, 2), ((7, 9), 2.5, 6), ((64, 64), 0.8, 3), ((5, 40), 1.84, 5))
+    out["lowpass_params"] = np.array([(s, k) for _, s, k in lowpass])
+    for i, ((h, w), sigma, k) in enumerate(lowpass):
+        img = rng.uniform(0, 100, (h, w)).astype(np.float32)
+        img[rng.integers(0, h, 3), rng.integers(0, w, 3)] = 1e4  # isolated peaks: every tap position matters
+        want = img.copy()
+        r.ref_lowpass2D(want, w, h, sigma, k)
+        out["lowpass_in_%d" % i], out["lowpass_out_%d" % i] = img, want
+    rng = np.random.default_rng(4)
+    h, w = 13, 17
+    img = rng.integers(-500, 500, (h, w)).astype(np.float32)
+    xy = np.array([(x8 / 8.0, y8 / 8.0) for y8 in range(0, 8 * (h - 1) + 1, 3) for x8 in range(0, 8 * (w - 1) + 1, 5)])
+    out["view_img"], out["view_xy"] = img, xy
+    out["view_at"] = np.array([r.ref_image_view_at(img, w, h, x, y) for x, y in xy])
+    out["view_centres"] = np.array([(i, j, r.ref_image_view_at(img, w, h, float(i), float(j)))
+                                    for i, j in ((0, 0), (w - 1, h - 1), (3, 7), (w - 1, 0))])
+    np.savez_compressed(os.path.join(HERE, "reference_pins.npz"), **out)
+    with open(os.path.join(REF, "proj000.nrrd"), "rb") as f:
+        raw = f.read()
+    header = raw[:raw.index(b"\n\n") + 2]  # (NRRD: the raw data follows the first empty line)
+    with open(os.path.join(HERE, "proj000_header.nrrd"), "wb") as f:
+        f.write(header)
+    print("reference pins: %d arrays; proj000 header %d bytes" % (len(out), len(header)))
+
+
 if __name__ == "__main__":
     if "--only-contract" in sys.argv:
         radon_contract()
         sys.exit(0)
+    if "--only-reference-pins" in sys.argv:
+        reference_pins()
+        sys.exit(0)
     if os.path.isdir(REF):
         example_pair()
         example_pair_native()
+        reference_pins()
     synthetic8()
     widened_rows()
     variants()

@@ -1,17 +1,21 @@
 """Pins the CPU oracle (oracle/ecc_oracle.c) before anything trusts it:
   * against the reference's own host-compilable headers (oracle/_ref/libecc_ref.so, built by
-    oracle/Makefile from /root/reference/code/LibEpipolarConsistency/EpipolarConsistencyCommon.hxx and
-    LibUtilsCuda/culaut/*.hxx) -- E1/E2 geometry, bit for bit in float32;
+    oracle/Makefile from the reference tree's LibEpipolarConsistency/EpipolarConsistencyCommon.hxx and
+    LibUtilsCuda/culaut/*.hxx) -- E1/E2 geometry, bit for bit in float32.  What those headers return for the
+    inputs below is stored in tests/golden/reference_pins.npz (tests/golden/make_golden.py, run where the
+    reference tree lies), so the pins hold on every machine;
   * against the known-answer scalars of the example pair recorded in SURVEY.md 8c;
   * against residual KATs in the style of the reference's disabled TestCudaUtils.cpp:39-57.
   * the pre-processing low-pass (Gaussian taps and the separable convolution with its dropped last tap) and the host
     image interpolation against the reference's header-only NRRD library (nrrd_lowpass.hxx, nrrd_image_view.hxx),
-    compiled into the same oracle/_ref/libecc_ref.so -- bit for bit;
+    compiled into the same oracle/_ref/libecc_ref.so -- bit for bit (stored in the same file);
   * the NORMATIVE variant 0 of the oracle (what every GPU test is held to) against the PINNED variant 2 at the level
     of the metric (64-view short scan): the two differ only by the rounding of four elementary functions.
 The kernel bodies R1/E3 have no reference vectors (parity unpinned, see oracle header): they are
 covered by property tests (test_oracle_properties.py) and committed goldens (test_golden.py).
 """
+import os
+
 import numpy as np
 import pytest
 
@@ -20,11 +24,13 @@ P040 = np.array([[-1975.44, -0, 2972.49, 376726], [286.441, -3532.97, 255.749, 2
                  [0.745941, -0, 0.666012, 744.3]])  # ref: config/example_data/proj0{00,40}.nrrd "Projection Matrix"
 
 
-def _need_ref(oracle_mod):
-    r = oracle_mod.ref()
-    if r is None:
-        pytest.skip("oracle/_ref/libecc_ref.so not built and /root/reference absent")
-    return r
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_pins.npz")
+
+
+@pytest.fixture(scope="module")
+def ref_out():
+    """The reference headers' outputs for this module's inputs (tests/golden/make_golden.py: reference_pins)."""
+    return np.load(GOLDEN)
 
 
 @pytest.fixture
@@ -48,45 +54,43 @@ def _random_Ps(k, seed=0):
     return out
 
 
-def test_e1_matches_reference_headers_bitwise(oracle_mod):
-    _need_ref(oracle_mod)
-    for P in [P000, P040] + _random_Ps(40):
-        a, b = oracle_mod.pinvT(P), oracle_mod.pinvT(P, use_ref=True)
+def test_e1_matches_reference_headers_bitwise(oracle_mod, ref_out):
+    assert len(ref_out["e1_Ps"]) == 42
+    for P, b, d in zip(ref_out["e1_Ps"], ref_out["e1_pinvT"], ref_out["e1_source_position"]):
+        a = oracle_mod.pinvT(P)
         assert np.array_equal(a, b), (a, b)
-        c, d = oracle_mod.source_position(P), oracle_mod.source_position(P, use_ref=True)
+        c = oracle_mod.source_position(P)
         assert np.array_equal(c, d), (c, d)
 
 
-def test_get_ij_matches_reference(oracle_mod):
-    _need_ref(oracle_mod)
+def test_get_ij_matches_reference(oracle_mod, ref_out):
     for n in (2, 3, 4, 5, 17, 64):
         seen = set()
+        want = ref_out["get_ij_%d" % n]
+        assert len(want) == n * (n - 1) // 2
         for ij in range(n * (n - 1) // 2):
             a = oracle_mod.get_ij(ij, n)
-            assert a == oracle_mod.get_ij(ij, n, use_ref=True)
+            assert a == tuple(int(v) for v in want[ij])
             assert a[0] < a[1] < n
             seen.add(a)
         assert len(seen) == n * (n - 1) // 2
     assert oracle_mod.get_ij(5, 4) == (2, 3)
 
 
-def test_computeK01_and_line_mapping_match_reference(oracle_mod, libm_variant):
-    _need_ref(oracle_mod)
-    Ps = [P000, P040] + _random_Ps(12, seed=3)
-    rng = np.random.default_rng(1)
+def test_computeK01_and_line_mapping_match_reference(oracle_mod, libm_variant, ref_out):
+    Ps = ref_out["k01_Ps"]
+    assert len(Ps) == 14 and ref_out["line_in"].shape == (7, 200, 3)
     for a in range(0, len(Ps), 2):
         P0, P1 = Ps[a], Ps[a + 1]
         args = (512.0, 380.0, oracle_mod.source_position(P0), oracle_mod.source_position(P1),
                 oracle_mod.pinvT(P0), oracle_mod.pinvT(P1), np.float32(106.75), np.float32(2550.4))
-        for dk in (0.0, 0.003):
+        for t, dk in enumerate((0.0, 0.003)):
             K0, K1 = oracle_mod.computeK01(*args, dk)
-            R0, R1 = oracle_mod.computeK01(*args, dk, use_ref=True)
+            R0, R1 = ref_out["k01_K"][a // 2, t]
             assert np.array_equal(K0, R0) and np.array_equal(K1, R1)
-        for _ in range(200):
-            line = rng.normal(size=3).astype(np.float32) * np.float32([1, 1, 500])
-            (la, ma), (lb, mb) = oracle_mod.line_to_sample_dtr(line, 1275.2), \
-                oracle_mod.line_to_sample_dtr(line, 1275.2, use_ref=True)
-            assert ma == mb and np.array_equal(la, lb)
+        for line, lb, mb in zip(ref_out["line_in"][a // 2], ref_out["line_out"][a // 2], ref_out["line_moved"][a // 2]):
+            la, ma = oracle_mod.line_to_sample_dtr(line, 1275.2)
+            assert ma == bool(mb) and np.array_equal(la, lb)
 
 
 def test_example_pair_known_answers(oracle_mod):
@@ -119,12 +123,12 @@ def test_residual_kats(oracle_mod):
         assert np.linalg.norm(P @ PinvT.T - np.eye(3)) < 1e-4
 
 
-def test_weighting_matches_reference(oracle_mod):
-    r = _need_ref(oracle_mod)
-    for x in (-2.0, -1.0, -0.5, 0.0, 0.3, 1.0, 1.5):
+def test_weighting_matches_reference(ref_out):
+    assert list(ref_out["weighting_x"]) == [-2.0, -1.0, -0.5, 0.0, 0.3, 1.0, 1.5]
+    for x, got in zip(ref_out["weighting_x"], ref_out["weighting"]):
         xx = np.float32(x) * np.float32(x)
         want = 0.0 if abs(x) > 1 else float(np.float32(1) - 2 * xx + xx * xx)
-        assert abs(r.ref_weighting(x) - want) < 1e-6
+        assert abs(got - want) < 1e-6
 
 
 def test_normative_variant_differs_only_by_elementary_function_rounding(oracle_mod):
@@ -143,55 +147,56 @@ def test_normative_variant_differs_only_by_elementary_function_rounding(oracle_m
     np.testing.assert_allclose(K1[6:], L1[6:], rtol=2e-7)
 
 
-def test_gaussian_kernel_matches_reference_bitwise(oracle_mod):
+def test_gaussian_kernel_matches_reference_bitwise(oracle_mod, ref_out):
     """eccor_gaussian_kernel vs NRRD::gaussianKernel (ref: HeaderOnly/NRRD/nrrd_lowpass.hxx:19-34)."""
-    r = _need_ref(oracle_mod)
-    for sigma, k in ((1.84, 5), (1.0, 2), (0.7, 1), (3.3, 9), (2.5, 12), (10.0, 3)):
-        want = np.zeros(2 * k + 1, np.float64)
-        r.ref_gaussian_kernel(sigma, k, want)
+    params = [(float(s), int(k)) for s, k in ref_out["gauss_params"]]
+    assert params == [(1.84, 5), (1.0, 2), (0.7, 1), (3.3, 9), (2.5, 12), (10.0, 3)]
+    for i, (sigma, k) in enumerate(params):
+        want = ref_out["gauss_%d" % i]
         got = oracle_mod.gaussian_kernel(sigma, k)
         assert np.array_equal(got, want), (sigma, k)
         assert abs(want.sum() - 1.0) < 1e-15
 
 
-def test_lowpass_stage_matches_reference_bitwise(oracle_mod):
+def test_lowpass_stage_matches_reference_bitwise(oracle_mod, ref_out):
     """The low-pass stage of eccor_preprocess vs NRRD::lowpass2D (ref: nrrd_lowpass.hxx:183-190 -> convolve2D :45-79:
     both passes run o = -k .. k-1 -- the last tap is dropped --, both use kernelx, float64 sums rounded to float per
     pass, clamp addressing).  Every other stage of the pre-processing is switched off; images are non-negative so the
     intensity stage (x * 1 + 0, negatives to zero) is the identity."""
-    r = _need_ref(oracle_mod)
-    rng = np.random.default_rng(21)
-    for (h, w), sigma, k in (((50, 70), 1.84, 5), ((33, 17), 1.0, 2), ((7, 9), 2.5, 6), ((64, 64), 0.8, 3), ((5, 40), 1.84, 5)):
-        img = rng.uniform(0, 100, (h, w)).astype(np.float32)
-        img[rng.integers(0, h, 3), rng.integers(0, w, 3)] = 1e4  # isolated peaks: every tap position matters
-        want = img.copy()
-        r.ref_lowpass2D(want, w, h, sigma, k)
+    shapes = [(50, 70), (33, 17), (7, 9), (64, 64), (5, 40)]
+    assert [tuple(p) for p in ref_out["lowpass_params"]] == [(1.84, 5), (1.0, 2), (2.5, 6), (0.8, 3), (1.84, 5)]
+    for i, (sigma, k) in enumerate(ref_out["lowpass_params"]):
+        # inputs: uniform texels with three isolated 1e4 peaks each (every tap position matters)
+        img, want = ref_out["lowpass_in_%d" % i], ref_out["lowpass_out_%d" % i]
+        h, w = img.shape
+        assert (h, w) == shapes[i] and (img == 1e4).any()
+        sigma, k = float(sigma), int(k)
         got = oracle_mod.preprocess(img, gaussian_sigma=sigma, half_kernel_width=k, zero=(0,) * 4, feather=(0,) * 4)
         assert np.array_equal(got, want), (h, w, sigma, k)
         assert not np.array_equal(got, img)
 
 
-def test_tex2d_matches_reference_image_view_where_the_rules_coincide(oracle_mod):
+def test_tex2d_matches_reference_image_view_where_the_rules_coincide(oracle_mod, ref_out):
     """eccor_tex2d (texel centres at i + 0.5, float32) vs NRRD::ImageView::operator()(x, y) (texel centres at integers,
     float64; ref: HeaderOnly/NRRD/nrrd_image_view.hxx:189-210) at coordinates where both are exact: integer-valued
     texels, fractions that are multiples of 1/8, positions inside [0, n - 1] (the reference truncates negative
     coordinates towards zero and extrapolates there; the texture rule clamps)."""
-    r = _need_ref(oracle_mod)
-    rng = np.random.default_rng(4)
-    h, w = 13, 17
-    img = rng.integers(-500, 500, (h, w)).astype(np.float32)
+    img = ref_out["view_img"]
+    h, w = img.shape
+    assert (h, w) == (13, 17) and np.array_equal(img, np.round(img))
     n = 0
-    for y8 in range(0, 8 * (h - 1) + 1, 3):
-        for x8 in range(0, 8 * (w - 1) + 1, 5):
-            x, y = x8 / 8.0, y8 / 8.0
-            want = r.ref_image_view_at(img, w, h, x, y)
-            got = oracle_mod.tex2d(img, x + 0.5, y + 0.5)
-            assert float(got) == want, (x, y, got, want)
-            n += 1
+    for (x, y), want in zip(ref_out["view_xy"], ref_out["view_at"]):
+        assert (8 * x) % 5 == 0 and (8 * y) % 3 == 0 and 0 <= x <= w - 1 and 0 <= y <= h - 1
+        got = oracle_mod.tex2d(img, x + 0.5, y + 0.5)
+        assert float(got) == want, (x, y, got, want)
+        n += 1
     assert n > 500
     # on the texel centres themselves both return the texel
-    for (i, j) in ((0, 0), (w - 1, h - 1), (3, 7), (w - 1, 0)):
-        assert oracle_mod.tex2d(img, i + 0.5, j + 0.5) == img[j, i] == r.ref_image_view_at(img, w, h, float(i), float(j))
+    centres = ref_out["view_centres"]
+    assert [(int(i), int(j)) for i, j, _ in centres] == [(0, 0), (w - 1, h - 1), (3, 7), (w - 1, 0)]
+    for i, j, want in centres:
+        i, j = int(i), int(j)
+        assert oracle_mod.tex2d(img, i + 0.5, j + 0.5) == img[j, i] == want
 
 
 def test_normative_and_pinned_variant_agree_on_the_metric(oracle_mod):

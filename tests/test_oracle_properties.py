@@ -105,11 +105,19 @@ def test_nrrd_roundtrip(tmp_path):
     assert np.allclose(nrrd.parse_matrix(meta["Projection Matrix"]), P)
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/config/example_data/proj000.nrrd"),
-                    reason="reference example data not present on this box")
-def test_reads_reference_example_data():
+def test_reads_reference_example_data(tmp_path):
+    """The reference's config/example_data/proj000.nrrd, restored byte for byte from tests/golden/ (its header and, in
+    example_pair_native.npz, its image)."""
+    import hashlib
     from epipolarconsistency_amd import nrrd
-    img, fields, meta = nrrd.read("/root/reference/config/example_data/proj000.nrrd")
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    with open(os.path.join(golden, "proj000_header.nrrd"), "rb") as f:
+        raw = f.read() + np.ascontiguousarray(np.load(os.path.join(golden, "example_pair_native.npz"))["images"][0], "<f4").tobytes()
+    assert hashlib.sha256(raw).hexdigest() == "e14e7be41c929dff9d46a46c7d299487313b21dc5814c7f5ae9b8799ee944ee4"
+    path = os.path.join(tmp_path, "proj000.nrrd")
+    with open(path, "wb") as f:
+        f.write(raw)
+    img, fields, meta = nrrd.read(path)
     assert img.shape == (760, 1024) and img.dtype == np.float32
     assert abs(float(img.max()) - 233.07385) < 1e-3 and float(img.min()) == 0.0
     P = nrrd.parse_matrix(meta["Projection Matrix"])
