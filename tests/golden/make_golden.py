@@ -198,6 +198,32 @@ def radon_contract():
     print("radon_contract: synthetic8 mean %.9g" % res["mean"])
 
 
+def geo_pins(r):
+    """E1 (pinvT, source_position) of 24 catalogue matrices and computeK01 of 32 pairs of them (dkappa 0 and 0.002), from the
+    reference headers; computeK01's inputs are the oracle's E1 in the headers' libm variant, as test_oracle_pins computes them."""
+    import geometry_catalog
+    ang = geometry_catalog.angulated(12)[0]
+    mir = geometry_catalog.mirrored(12)[0]
+    Ps = np.stack(ang[:8] + mir[:12] + [-ang[3], ang[5] * 1e-3, ang[7] * 1e3, -mir[1]])
+    out = {"geo_Ps": Ps}
+    out["geo_pinvT"] = np.stack([oracle.pinvT(P, use_ref=True) for P in Ps])
+    out["geo_source_position"] = np.stack([oracle.source_position(P, use_ref=True) for P in Ps])
+    Cs = geometry_catalog.source_positions(Ps)
+    cand = [(a, b) for a in range(len(Ps)) for b in range(a + 1, len(Ps)) if np.linalg.norm(Cs[a] - Cs[b]) > 1.0]
+    pairs = np.array(cand, np.int32)[np.random.default_rng(8).choice(len(cand), 32, replace=False)]  # (no pair of one source)
+    oracle.set_variant(2)
+    try:
+        K = []
+        for a, b in pairs:
+            args = (320.0, 240.0, oracle.source_position(Ps[a]), oracle.source_position(Ps[b]),
+                    oracle.pinvT(Ps[a]), oracle.pinvT(Ps[b]), np.float32(60.0), np.float32(1600.0))
+            K.append([oracle.computeK01(*args, dk, use_ref=True) for dk in (0.0, 0.002)])
+    finally:
+        oracle.set_variant(0)
+    out.update(geo_pairs=pairs, geo_k01_K=np.array(K, np.float32))
+    return out
+
+
 def reference_pins():
     """reference_pins.npz: the inputs of tests/test_oracle_pins.py and what the reference's own headers (oracle/_ref/libecc_ref.so,
     built by oracle/Makefile where the reference tree lies) return for them -- E1/E2 geometry, get_ij, computeK01 and the line
@@ -232,6 +258,9 @@ def reference_pins():
         oracle.set_variant(0)
     out.update(k01_Ps=Ps, k01_K=np.array(K, np.float32), line_in=np.array(lines, np.float32),
                line_out=np.array(mapped, np.float32), line_moved=np.array(moved, bool))
+    # catalogue matrices (tests/geometry_catalog.py): mirrored u axis (det M < 0), negated, scaled by 1e-3 and 1e3, angulated
+    # with an off-centre principal point -- E1 and computeK01 of 32 pairs of them
+    out.update(geo_pins(r))
     xs = np.array([-2.0, -1.0, -0.5, 0.0, 0.3, 1.0, 1.5])
     out["weighting_x"], out["weighting"] = xs, np.array([r.ref_weighting(x) for x in xs], np.float32)
     gauss = ((1.84, 5), (1.0, 2), (0.7, 1), (3.3, 9), (2.5, 12), (10.0, 3))

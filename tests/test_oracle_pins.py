@@ -220,3 +220,31 @@ def test_normative_and_pinned_variant_agree_on_the_metric(oracle_mod):
     assert a["mean"] != b["mean"] or np.array_equal(a["pairs"], b["pairs"])
     np.testing.assert_allclose(a["pairs"], b["pairs"], rtol=2e-3)
     assert np.median(np.abs(a["pairs"] - b["pairs"]) / np.abs(a["pairs"])) < 5e-5
+
+
+def test_e1_and_k01_on_catalogue_matrices_match_reference_headers_bitwise(oracle_mod, libm_variant, ref_out):
+    """E1 and computeK01 on matrices of the geometry catalogue (tests/geometry_catalog.py) that the other pins do not reach:
+    the u axis mirrored (det M < 0), negated, scaled by 1e-3 and 1e3, an angulated orbit with an off-centre principal point.
+    The reference's arithmetic depends on the sign and the scale of P; the oracle must follow it bit for bit."""
+    import geometry_catalog
+    Ps = ref_out["geo_Ps"]
+    assert Ps.shape == (24, 3, 4)
+    ang, mir = geometry_catalog.angulated(12)[0], geometry_catalog.mirrored(12)[0]
+    assert np.array_equal(Ps[:20], np.stack(ang[:8] + mir[:12]))  # the catalogue has not moved under the pins
+    dets = np.linalg.det(Ps[:, :, :3])
+    assert (dets < 0).sum() >= 6 and (dets > 0).sum() >= 6
+    scales = {float(np.round(np.linalg.norm(P[2, :3]), 9)) for P in Ps}
+    assert {1e-3, 1.0, 1e3} <= scales
+    for P, b, d in zip(Ps, ref_out["geo_pinvT"], ref_out["geo_source_position"]):
+        a = oracle_mod.pinvT(P)
+        assert np.array_equal(a, b), (a, b)
+        c = oracle_mod.source_position(P)
+        assert np.array_equal(c, d), (c, d)
+    pairs = ref_out["geo_pairs"]
+    assert len(pairs) == 32 and np.isfinite(ref_out["geo_k01_K"]).all()
+    for (a, b), want in zip(pairs, ref_out["geo_k01_K"]):
+        args = (320.0, 240.0, oracle_mod.source_position(Ps[a]), oracle_mod.source_position(Ps[b]),
+                oracle_mod.pinvT(Ps[a]), oracle_mod.pinvT(Ps[b]), np.float32(60.0), np.float32(1600.0))
+        for t, dk in enumerate((0.0, 0.002)):
+            K0, K1 = oracle_mod.computeK01(*args, dk)
+            assert np.array_equal(K0, want[t][0]) and np.array_equal(K1, want[t][1]), (a, b, dk)
