@@ -73,7 +73,7 @@ void arm_result(ecc_metric* m)
         (void)hipStreamSynchronize(m->ctx->stream);
         m->small_pending_count = 0;
     }
-    reinterpret_cast<volatile uint64_t*>(m->sum_h)[0] = ECC_RESULT_PENDING;
+    reinterpret_cast<volatile uint64_t*>(m->sum_h.host)[0] = ECC_RESULT_PENDING;
     std::atomic_thread_fence(std::memory_order_seq_cst);
 }
 
@@ -81,10 +81,10 @@ hipError_t wait_result(ecc_metric* m, hipStream_t stream, double* value)
 {
     if (!result_polling_enabled()) {
         const hipError_t e = wait_stream_spin(stream);
-        std::memcpy(value, m->sum_h, sizeof(double));
+        std::memcpy(value, m->sum_h.host, sizeof(double));
         return e;
     }
-    const volatile uint64_t* slot = reinterpret_cast<const volatile uint64_t*>(m->sum_h);
+    const volatile uint64_t* slot = reinterpret_cast<const volatile uint64_t*>(m->sum_h.host);
     double t0 = 0.0;
     for (unsigned spins = 0;; ++spins) {
         const uint64_t bits = *slot;

@@ -23,6 +23,7 @@
 #include "../../include/ecc_hip.h"
 #include "ecc_host_geometry.h"
 #include "ecc_layout.h"
+#include "ecc_view_changes.h"
 
 extern "C" hipError_t ecc_launch_radon(const EccRadonParams* p, int derivative, hipStream_t stream);
 extern "C" hipError_t ecc_launch_dtr_border(float* slabs, int64_t slab_stride, int n_img, int n_alpha, int n_t,
@@ -128,7 +129,135 @@ struct ecc_dtr {
     int n_alpha = 0, n_t = 0, n_u = 0, n_v = 0, filter = 0, pitch = 0;
 };
 
+namespace ecc_internal {
+hipError_t wait_stream_spin(hipStream_t stream);
+
+// A device array the metric owns: grown on demand, freed with the metric (ecc_metric_destroy makes its device current first).
+template <class T>
+struct DeviceArray {
+    T* ptr = nullptr;
+    int64_t cap = 0;  // elements
+    DeviceArray() = default;
+    DeviceArray(const DeviceArray&) = delete;
+    DeviceArray& operator=(const DeviceArray&) = delete;
+    ~DeviceArray() { reset(); }
+    void reset()
+    {
+        if (ptr) (void)hipFree((void*)ptr);
+        ptr = nullptr;
+        cap = 0;
+    }
+    // room for `need` elements: exactly that many, after the stream has drained when a smaller array is replaced
+    int ensure(int64_t need, hipStream_t stream)
+    {
+        if (cap >= need && ptr) return ECC_OK;
+        if (ptr) {
+            HIP_TRY(hipStreamSynchronize(stream));
+            HIP_TRY(hipFree((void*)ptr));
+            ptr = nullptr;
+            cap = 0;
+        }
+        HIP_TRY(alloc(need));
+        return ECC_OK;
+    }
+    // the first allocation, for callers that report a failure themselves
+    hipError_t alloc(int64_t n)
+    {
+        const hipError_t e = hipMalloc((void**)&ptr, (size_t)n * sizeof(T));
+        if (e != hipSuccess) ptr = nullptr;
+        cap = e == hipSuccess ? n : 0;
+        return e;
+    }
+    int64_t bytes() const { return cap * (int64_t)sizeof(T); }
+};
+
+// A pinned host array mapped into the device's address space (zero-copy staging): host and device address of the same memory.
+template <class T>
+struct PinnedArray {
+    T* host = nullptr;
+    T* dev = nullptr;
+    int64_t cap = 0;  // elements
+    unsigned flags;
+    explicit PinnedArray(unsigned alloc_flags = hipHostMallocMapped) : flags(alloc_flags) {}
+    PinnedArray(const PinnedArray&) = delete;
+    PinnedArray& operator=(const PinnedArray&) = delete;
+    ~PinnedArray()
+    {
+        if (host) (void)hipHostFree(host);
+    }
+    // room for `need` elements: max(2 need, floor) of them, after the stream has drained when a smaller array is replaced
+    // (a launch may still be reading it)
+    int ensure(int64_t need, int64_t floor, hipStream_t stream)
+    {
+        if (cap >= need) return ECC_OK;
+        if (host) {
+            HIP_TRY(wait_stream_spin(stream));
+            HIP_TRY(hipHostFree(host));
+            host = dev = nullptr;
+            cap = 0;
+        }
+        HIP_TRY(alloc(std::max<int64_t>(2 * need, floor)));
+        return ECC_OK;
+    }
+    // the first allocation, for callers that report a failure themselves
+    hipError_t alloc(int64_t n)
+    {
+        hipError_t e = hipHostMalloc((void**)&host, sizeof(T) * (size_t)n, flags);
+        if (e != hipSuccess) host = nullptr;
+        else e = hipHostGetDevicePointer((void**)&dev, host, 0);
+        if (e == hipSuccess) cap = n;
+        return e;
+    }
+};
+
+// What an evaluation keeps for the next one of the same pair range: the range, the parameters it depends on (Key) and the
+// matrices it was made from.  `valid` is set by the caller once everything that made it is enqueued.
+template <class Key>
+struct Kept {
+    bool valid = false;
+    int64_t first = 0, count = 0;
+    int n_views = 0;
+    Key key{};
+    std::vector<double> Ps;
+    bool matches(int64_t f, int64_t c, int n, const Key& k) const
+    {
+        return valid && first == f && count == c && n_views == n && key == k && (int64_t)Ps.size() == 12 * (int64_t)n;
+    }
+    void take(int64_t f, int64_t c, int n, const Key& k, const double* Pcur)
+    {
+        Ps.assign(Pcur, Pcur + 12 * (size_t)n);
+        first = f;
+        count = c;
+        n_views = n;
+        key = k;
+    }
+    void update(const std::vector<int>& views, const double* Pcur)
+    {
+        for (int v : views) std::memcpy(Ps.data() + 12 * (size_t)v, Pcur + 12 * (size_t)v, sizeof(double) * 12);
+    }
+};
+// the kept records: the resolved sampling mode and the launch's float parameters
+struct RecordKey {
+    int mode;
+    float radius, dkappa, tol;
+    bool operator==(const RecordKey& o) const { return mode == o.mode && radius == o.radius && dkappa == o.dkappa && tol == o.tol; }
+};
+// the kept pair values: the metric's settings
+struct ValueKey {
+    int use_corr, sampling;
+    double radius, dkappa;
+    bool operator==(const ValueKey& o) const
+    {
+        return use_corr == o.use_corr && sampling == o.sampling && radius == o.radius && dkappa == o.dkappa;
+    }
+};
+}  // namespace ecc_internal
+
 struct ecc_metric {
+    template <class T>
+    using DeviceArray = ecc_internal::DeviceArray<T>;
+    template <class T>
+    using PinnedArray = ecc_internal::PinnedArray<T>;
     ecc_ctx* ctx = nullptr;
     std::vector<ecc_dtr*> dtrs;
     int n_alpha = 0, n_t = 0, n_u = 0, n_v = 0, pitch = 0;
@@ -142,57 +271,42 @@ struct ecc_metric {
     int n_views = 0;
     std::vector<double> P_first;  // first projection matrix (object radius estimate)
     // device state
-    const float** dtr_table_d = nullptr;     // the dtrs' slabs (borrowed)
-    float* paired_d = nullptr;               // row-paired copies of all dtrs (owned; what the pair kernel samples)
-    const float** paired_table_d = nullptr;  // per dtr: base of its paired copy
-    float* quads_d = nullptr;                // row-quad copies of all dtrs (owned; sampled by the pairs with kappa_max > pi/4), or null
-    const float** quads_table_d = nullptr;
+    DeviceArray<const float*> dtr_table_d;     // the dtrs' slabs (borrowed)
+    DeviceArray<float> paired_d;               // row-paired copies of all dtrs (owned; what the pair kernel samples)
+    DeviceArray<const float*> paired_table_d;  // per dtr: base of its paired copy
+    DeviceArray<float> quads_d;                // row-quad copies of all dtrs (owned; sampled by the pairs with kappa_max > pi/4), or none
+    DeviceArray<const float*> quads_table_d;
     int64_t quad_floats = 0;                 // floats per row-quad copy
     std::vector<const float*> quads_table_h; // host image of quads_table_d
     bool quads_possible = false;             // offsets into a row-quad copy fit 32 bits
     bool quads_decided = true;               // ECC_QUAD_COPIES_AUTO: false until the first large evaluation has looked at the matrices
-    float* Cs_d = nullptr;
-    float* PinvTs_d = nullptr;
-    int geom_capacity = 0;
-    float* pair_values_d = nullptr;
-    int64_t pair_capacity = 0;
-    float* cost_d = nullptr;
-    int cost_capacity = 0;
-    int32_t* indices_d = nullptr;
-    int64_t indices_capacity = 0;
-    float* K01_d = nullptr;
-    int64_t K01_capacity = 0;
-    EccPairRecord* records_d = nullptr;  // per-pair geometry between k01_kernel and pairs_kernel
-    int64_t records_capacity = 0;
-    double* sum_d = nullptr;
-    void* sum_scratch_d = nullptr;  // partials + ticket of the multi-workgroup sum (zeroed; pairs_kernel.hip)
-    double* Ps_d = nullptr;   // n x 12 float64 as handed over by the caller
+    DeviceArray<float> Cs_d;                 // 4 per view
+    DeviceArray<float> PinvTs_d;             // 12 per view
+    int geom_capacity = 0;                   // views Cs_d, PinvTs_d and Ps_h have room for
+    DeviceArray<float> pair_values_d;
+    DeviceArray<float> cost_d;
+    DeviceArray<int32_t> indices_d;
+    DeviceArray<float> K01_d;
+    DeviceArray<EccPairRecord> records_d;  // per-pair geometry between k01_kernel and pairs_kernel
+    DeviceArray<double> sum_d;
+    DeviceArray<char> sum_scratch_d;  // partials + ticket of the multi-workgroup sum (zeroed; pairs_kernel.hip)
     // pinned host staging, mapped into the device's address space (zero-copy: the 38 KB of matrices and the 8-byte
     // result cross PCIe inside the kernels, no copy commands).  Two matrix buffers, used alternately: an evaluate
     // call returns only after the stream has executed everything up to its result, so the buffer of the call before
     // the previous one is free without asking the stream (set_generation / done_generation below).
-    double* Ps_h[2] = {nullptr, nullptr};
-    double* Ps_h_dev[2] = {nullptr, nullptr};
+    PinnedArray<double> Ps_h[2];
     uint64_t set_generation = 0;   // number of e1 launches so far; launch g reads Ps_h[g & 1]
     uint64_t done_generation = 0;  // every e1 launch up to this one is known to have completed
-    double* sum_h = nullptr;       // 64-byte slot; [0] = the result, written by sum_pairs_kernel with a system-scope store
-    double* sum_h_dev = nullptr;
+    // 64-byte slot; [0] = the result, written by sum_pairs_kernel with a system-scope store
+    PinnedArray<double> sum_h{hipHostMallocMapped | hipHostMallocCoherent};
     // ecc_metric_set_incremental: the pair values of the last evaluation of one pair range, the matrices and parameters
     // they belong to, and a pinned, device-mapped list buffer (4 indices + 1 slot per re-evaluated pair)
     int incremental = 0;
-    bool cache_valid = false;
-    int64_t cache_first = 0, cache_count = 0;
-    int cache_n_views = 0, cache_use_corr = 0, cache_sampling = 0;
-    double cache_radius = 0, cache_dkappa = 0;
-    std::vector<double> cache_Ps;
-    float* cache_values_d = nullptr;
-    int64_t cache_capacity = 0;
-    int32_t* list_h = nullptr;
-    int32_t* list_h_dev = nullptr;
-    int64_t list_capacity = 0;  // pairs
+    ecc_internal::Kept<ecc_internal::ValueKey> cache;
+    DeviceArray<float> cache_values_d;
+    PinnedArray<int32_t> list_h;
     std::vector<int> scratch_changed;        // reused between evaluations (no heap traffic on the optimiser's path)
-    std::vector<char> scratch_is_changed;
-    std::vector<int32_t> scratch_idx, scratch_slots;
+    ecc_view_changes::PairList scratch_pairs;
     int64_t last_evaluated_pairs = 0;
     // ecc_metric_set_record_reuse: the per-pair records (k01_kernel's output) of the last all-pairs / range evaluation
     // stay in records_d together with the matrices and parameters they belong to; the next evaluation of the same range
@@ -208,22 +322,15 @@ struct ecc_metric {
     mutable double radius_cache_P[12] = {0};
     mutable bool radius_cache_valid = false;
     bool eager_e1 = false;     // the last range was too small for record reuse: set_projections launches e1_kernel itself
-    bool rec_valid = false;
-    int64_t rec_first = 0, rec_count = 0;
-    int rec_n_views = 0, rec_mode = 0;
-    float rec_radius = 0, rec_dkappa = 0, rec_tol = 0;
-    std::vector<double> rec_Ps;
+    ecc_internal::Kept<ecc_internal::RecordKey> rec;
     // pinned, device-mapped lists of the reuse path, two used alternately: per pair 4 indices + slot + 2 patch refs,
     // per changed view 16 floats + its index
-    int32_t* reuse_h[2] = {nullptr, nullptr};
-    int32_t* reuse_h_dev[2] = {nullptr, nullptr};
-    int64_t reuse_words[2] = {0, 0};
+    PinnedArray<int32_t> reuse_h[2];
     hipEvent_t reuse_ev[2] = {nullptr, nullptr};  // recorded after the k01 launch that read list b (asynchronous callers)
     bool reuse_ev_used[2] = {false, false};
     uint64_t reuse_gen = 0;
     std::vector<int> scratch_patched;
-    std::vector<int> scratch_stale;     // small_eval_patches: views whose geometry on the device is behind
-    std::vector<int32_t> scratch_refs;
+    std::vector<int> scratch_stale;     // views whose geometry on the device is behind the current matrices
     std::vector<int32_t> scratch_patch_of;
     // second stream of the reuse path: refit + list launch of the changed pairs run there while the all-pairs launch
     // (which skips them) already runs on the context's stream
@@ -246,36 +353,23 @@ struct ecc_metric {
     int small_eval = 1;
     int64_t small_max_pairs = -1;  // ecc_debug_set_small_eval_bound: >= 0 replaces the one-launch path's own size bound
     float economise_tol = ECC_POLY_ECONOMISE_TOL_BINS;  // ecc_debug_set_poly_tolerance
-    int32_t* sidx_h = nullptr;    // index list of a fused index-list evaluation (pinned, device-mapped)
-    int32_t* sidx_h_dev = nullptr;
-    int64_t sidx_capacity = 0;    // pairs
-    float* svals_h = nullptr;     // pair values a caller wants on the host (pinned, device-mapped)
-    float* svals_h_dev = nullptr;
-    int64_t svals_capacity = 0;
-    unsigned* small_ticket_d = nullptr;
+    PinnedArray<int32_t> sidx_h;  // index list of a fused index-list evaluation (4 per pair)
+    PinnedArray<float> svals_h;   // pair values a caller wants on the host
+    DeviceArray<unsigned> small_ticket_d;
     int64_t small_pending_count = 0;  // > 0: the result slot will receive the "done" word of a one-launch evaluation of that many pairs
     // ecc_metric_evaluate_pose_deltas (ecc_poses.hip): K poses as ONE record launch, ONE pair launch and ONE segmented sum.
     // Everything below is scratch of that path, grown on demand: the extended geometry (the base views, then one entry per
     // moved view of every pose), the pose-major x partner-major index grid, its records and values, the slice sums, and one
     // pinned, device-mapped block (extended matrices, the lists, the results).
     int pose_batching = 1;  // ecc_metric_set_pose_batching
-    char* pose_h = nullptr;
-    char* pose_h_dev = nullptr;
-    int64_t pose_h_bytes = 0;
-    float* pose_PinvTs_d = nullptr;
-    int64_t pose_PinvTs_capacity = 0;  // floats
-    float* pose_Cs_d = nullptr;
-    int64_t pose_Cs_capacity = 0;      // floats
-    int32_t* pose_idx_d = nullptr;
-    int64_t pose_idx_capacity = 0;     // ints
-    EccPairRecord* pose_records_d = nullptr;
-    int64_t pose_records_capacity = 0;
-    float* pose_values_d = nullptr;
-    int64_t pose_values_capacity = 0;
-    double* pose_partial_d = nullptr;
-    int64_t pose_partial_capacity = 0;
-    int32_t* pose_lists_d = nullptr;
-    int64_t pose_lists_capacity = 0;   // ints
+    PinnedArray<char> pose_h;
+    DeviceArray<float> pose_PinvTs_d;
+    DeviceArray<float> pose_Cs_d;
+    DeviceArray<int32_t> pose_idx_d;
+    DeviceArray<EccPairRecord> pose_records_d;
+    DeviceArray<float> pose_values_d;
+    DeviceArray<double> pose_partial_d;
+    DeviceArray<int32_t> pose_lists_d;
     int64_t last_batched_poses = 0;    // poses the last ecc_metric_evaluate_poses* call took through the batch (ecc_metric_last_batched_poses)
     // ecc_debug_step_stamps: host clock (seconds, steady) at fixed points of the last set_projections / synchronous evaluation
     double stamps[ECC_STEP_STAMPS] = {0};
@@ -294,7 +388,6 @@ inline void ecc_stamp(ecc_metric* m, int k)
 
 namespace ecc_internal {
 
-hipError_t wait_stream_spin(hipStream_t stream);
 void arm_result(ecc_metric* m);
 hipError_t wait_result(ecc_metric* m, hipStream_t stream, double* value);
 int set_device(const ecc_ctx* ctx);
@@ -307,19 +400,18 @@ int launch_range(ecc_metric* m, int64_t first, int64_t count, float* pair_values
                  bool synchronous = false);
 int evaluate_cached(ecc_metric* m, int64_t first, int64_t count, double* sum_d, float** vals_out);
 
-template <class T>
-int ensure_capacity(T** ptr, int64_t* cap, int64_t need, hipStream_t stream)
+// The pair launch p -- or, with x, the one-launch evaluation -- on the context's stream between its timing events (ecc_ctx_enable_timing).
+inline hipError_t launch_pairs_timed(ecc_ctx* ctx, const EccPairParams* p, const EccSmallEval* x = nullptr)
 {
-    if (*cap >= need && *ptr) return ECC_OK;
-    if (*ptr) {
-        HIP_TRY(hipStreamSynchronize(stream));
-        HIP_TRY(hipFree(*ptr));
-        *ptr = nullptr;
-        *cap = 0;
+    if (ctx->timing) {
+        const hipError_t e = hipEventRecord(ctx->ev[0], ctx->stream);
+        if (e != hipSuccess) return e;
     }
-    HIP_TRY(hipMalloc((void**)ptr, (size_t)need * sizeof(T)));
-    *cap = need;
-    return ECC_OK;
+    const hipError_t e = x ? ecc_launch_small_eval(p, x, ctx->stream) : ecc_launch_pairs(p, ctx->stream);
+    if (e != hipSuccess || !ctx->timing) return e;
+    const hipError_t e1 = hipEventRecord(ctx->ev[1], ctx->stream);
+    if (e1 == hipSuccess) ctx->ev_valid[0] = true;
+    return e1;
 }
 
 }  // namespace ecc_internal

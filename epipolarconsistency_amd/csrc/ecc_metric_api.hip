@@ -17,17 +17,15 @@ hipError_t build_quad_copies(ecc_metric* m)
     const int n_dtrs = (int)m->dtrs.size();
     std::vector<const float*>& qtable = m->quads_table_h;  // (lives with the metric: the asynchronous upload below may read it after this returns)
     qtable.assign((size_t)n_dtrs, nullptr);
-    hipError_t e = hipMalloc((void**)&m->quads_table_d, sizeof(float*) * n_dtrs);
-    if (e == hipSuccess) e = hipMalloc((void**)&m->quads_d, sizeof(float) * (size_t)m->quad_floats * n_dtrs);
-    for (int k = 0; k < n_dtrs && e == hipSuccess; ++k) qtable[k] = m->quads_d + (size_t)m->quad_floats * k;
-    if (e == hipSuccess) e = hipMemcpyAsync(m->quads_table_d, qtable.data(), sizeof(float*) * n_dtrs, hipMemcpyHostToDevice, m->ctx->stream);
-    if (e == hipSuccess) e = ecc_launch_build_quad(m->dtr_table_d, m->quads_d, m->quad_floats, n_dtrs, m->n_alpha + 1, m->pitch, m->ctx->stream);
+    hipError_t e = m->quads_table_d.alloc(n_dtrs);
+    if (e == hipSuccess) e = m->quads_d.alloc(m->quad_floats * n_dtrs);
+    for (int k = 0; k < n_dtrs && e == hipSuccess; ++k) qtable[k] = m->quads_d.ptr + (size_t)m->quad_floats * k;
+    if (e == hipSuccess) e = hipMemcpyAsync(m->quads_table_d.ptr, qtable.data(), sizeof(float*) * n_dtrs, hipMemcpyHostToDevice, m->ctx->stream);
+    if (e == hipSuccess) e = ecc_launch_build_quad(m->dtr_table_d.ptr, m->quads_d.ptr, m->quad_floats, n_dtrs, m->n_alpha + 1, m->pitch, m->ctx->stream);
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        if (m->quads_d) (void)hipFree(m->quads_d);
-        if (m->quads_table_d) (void)hipFree((void*)m->quads_table_d);
-        m->quads_d = nullptr;
-        m->quads_table_d = nullptr;
+        m->quads_d.reset();
+        m->quads_table_d.reset();
     }
     return e;
 }
@@ -48,7 +46,7 @@ void decide_quad_copies(ecc_metric* m)
     if (n < 2 || (int64_t)m->dtrs.size() < n) return;
     double radius = 0;
     ecc_metric_get_object_radius(m, &radius);
-    const double* Ps = m->Ps_h[m->set_generation & 1];
+    const double* Ps = m->Ps_h[m->set_generation & 1].host;
     std::vector<double> C(4 * (size_t)n);
     for (int64_t v = 0; v < n; ++v) {
         float c4[4];
@@ -122,30 +120,29 @@ ECC_EXPORT int ecc_metric_create(ecc_ctx* ctx, int n_dtrs, ecc_dtr* const* dtrs,
         return fail(ECC_ERR_UNSUPPORTED, "Radon intermediates above 4 GB per row-paired copy are not supported");
     }
     std::vector<const float*> ptable(n_dtrs);
-    hipError_t e = hipMalloc((void**)&m->dtr_table_d, sizeof(float*) * n_dtrs);
-    if (e == hipSuccess) e = hipMalloc((void**)&m->paired_table_d, sizeof(float*) * n_dtrs);
-    if (e == hipSuccess) e = hipMalloc((void**)&m->paired_d, sizeof(float) * (size_t)paired_floats * n_dtrs);
-    for (int k = 0; k < n_dtrs && e == hipSuccess; ++k) ptable[k] = m->paired_d + (size_t)paired_floats * k;
+    hipError_t e = m->dtr_table_d.alloc(n_dtrs);
+    if (e == hipSuccess) e = m->paired_table_d.alloc(n_dtrs);
+    if (e == hipSuccess) e = m->paired_d.alloc(paired_floats * n_dtrs);
+    for (int k = 0; k < n_dtrs && e == hipSuccess; ++k) ptable[k] = m->paired_d.ptr + (size_t)paired_floats * k;
     if (e == hipSuccess)
-        e = hipMemcpyAsync(m->paired_table_d, ptable.data(), sizeof(float*) * n_dtrs, hipMemcpyHostToDevice, ctx->stream);
+        e = hipMemcpyAsync(m->paired_table_d.ptr, ptable.data(), sizeof(float*) * n_dtrs, hipMemcpyHostToDevice, ctx->stream);
     // row-quad copies (ecc_ctx_set_quad_copies; 4x the slab memory, see pair_accumulate): offsets must fit 32 bits.
     // ECC_QUAD_COPIES_ON: built here.  ECC_QUAD_COPIES_AUTO (default): decided by the first large evaluation, when the matrices
     // say whether the scan has pairs that read them at all (ecc_internal::decide_quad_copies); _OFF: never.
     m->quad_floats = (int64_t)((m->n_alpha + 1 + 3) / 4) * m->pitch * 16;
     m->quads_possible = m->quad_floats * 4 < ((int64_t)1 << 32);
     m->quads_decided = !(m->quads_possible && ctx->quad_copies == ECC_QUAD_COPIES_AUTO);
-    if (e == hipSuccess) e = hipMalloc((void**)&m->sum_d, sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&m->sum_scratch_d, ecc_sum_scratch_bytes());
-    if (e == hipSuccess) e = hipMemsetAsync(m->sum_scratch_d, 0, ecc_sum_scratch_bytes(), ctx->stream);
+    if (e == hipSuccess) e = m->sum_d.alloc(1);
+    if (e == hipSuccess) e = m->sum_scratch_d.alloc((int64_t)ecc_sum_scratch_bytes());
+    if (e == hipSuccess) e = hipMemsetAsync(m->sum_scratch_d.ptr, 0, ecc_sum_scratch_bytes(), ctx->stream);
 
-    if (e == hipSuccess) e = hipHostMalloc((void**)&m->sum_h, 64, hipHostMallocMapped | hipHostMallocCoherent);
-    if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&m->sum_h_dev, m->sum_h, 0);
+    if (e == hipSuccess) e = m->sum_h.alloc(8);  // 64 bytes
     if (e == hipSuccess)
-        e = hipMemcpyAsync(m->dtr_table_d, table.data(), sizeof(float*) * n_dtrs, hipMemcpyHostToDevice, ctx->stream);
+        e = hipMemcpyAsync(m->dtr_table_d.ptr, table.data(), sizeof(float*) * n_dtrs, hipMemcpyHostToDevice, ctx->stream);
     // the metric borrows the dtrs and they must not change during its lifetime (ref: ...RadonIntermediate.h:45), so
     // the paired copies are built once, here
     if (e == hipSuccess)
-        e = ecc_launch_build_paired(m->dtr_table_d, m->paired_d, paired_floats, n_dtrs, m->n_alpha + 1, m->pitch, ctx->stream);
+        e = ecc_launch_build_paired(m->dtr_table_d.ptr, m->paired_d.ptr, paired_floats, n_dtrs, m->n_alpha + 1, m->pitch, ctx->stream);
     if (e == hipSuccess && m->quads_possible && ctx->quad_copies == ECC_QUAD_COPIES_ON) e = build_quad_copies(m);  // (behind the table's upload)
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) {
@@ -163,15 +160,15 @@ ECC_EXPORT int ecc_metric_refresh_dtrs(ecc_metric* m, int first, int count)
     const int n = (int)m->dtrs.size();
     if (first < 0 || count < 0 || first > n || count > n - first) return fail(ECC_ERR_INVALID_ARGUMENT, "dtr range outside the metric's list");
     if (count == 0) return ECC_OK;
-    m->cache_valid = false;
+    m->cache.valid = false;
     int rc = set_device(m->ctx);
     if (rc) return rc;
     const int64_t paired_floats = (int64_t)(m->n_alpha + 1) * m->pitch * 2;
     // stream-ordered behind whatever produced the new slab contents on this stream, in front of the next evaluation
-    HIP_TRY(ecc_launch_build_paired(m->dtr_table_d + first, m->paired_d + (size_t)paired_floats * first, paired_floats, count,
+    HIP_TRY(ecc_launch_build_paired(m->dtr_table_d.ptr + first, m->paired_d.ptr + (size_t)paired_floats * first, paired_floats, count,
                                     m->n_alpha + 1, m->pitch, m->ctx->stream));
-    if (m->quads_d)
-        HIP_TRY(ecc_launch_build_quad(m->dtr_table_d + first, m->quads_d + (size_t)m->quad_floats * first, m->quad_floats, count,
+    if (m->quads_d.ptr)
+        HIP_TRY(ecc_launch_build_quad(m->dtr_table_d.ptr + first, m->quads_d.ptr + (size_t)m->quad_floats * first, m->quad_floats, count,
                                       m->n_alpha + 1, m->pitch, m->ctx->stream));
     return ECC_OK;
 }
@@ -185,20 +182,20 @@ int ensure_e1(ecc_metric* m)
     if (!m->e1_pending) return ECC_OK;
     const int slot = (int)(m->set_generation & 1);
     const size_t n12 = (size_t)12 * m->n_views;
-    if (m->dev_valid && m->dev_Ps.size() == n12 && std::memcmp(m->dev_Ps.data(), m->Ps_h[slot], sizeof(double) * n12) == 0) {
+    if (m->dev_valid && m->dev_Ps.size() == n12 && std::memcmp(m->dev_Ps.data(), m->Ps_h[slot].host, sizeof(double) * n12) == 0) {
         m->e1_pending = false;  // the device arrays already belong to these matrices (patched view by view, or set back)
         return ECC_OK;
     }
     ecc_mark_busy(m);
-    HIP_TRY(ecc_launch_e1(m->Ps_h_dev[slot], m->n_views, m->PinvTs_d, m->Cs_d, m->ctx->stream));
-    m->dev_Ps.assign(m->Ps_h[slot], m->Ps_h[slot] + n12);
+    HIP_TRY(ecc_launch_e1(m->Ps_h[slot].dev, m->n_views, m->PinvTs_d.ptr, m->Cs_d.ptr, m->ctx->stream));
+    m->dev_Ps.assign(m->Ps_h[slot].host, m->Ps_h[slot].host + n12);
     m->dev_valid = true;
     m->e1_pending = false;
-    // The reuse path of launch_range assumes PinvTs / Cs on the device are E1(rec_Ps) for every view it finds unchanged.
+    // The reuse path of launch_range assumes PinvTs / Cs on the device are E1(rec.Ps) for every view it finds unchanged.
     // This launch has just made them E1 of the CURRENT matrices for all views (an image-pair or debug call between two
     // evaluations gets here), so the kept records no longer describe the device geometry: the next evaluation refits
-    // everything.  (launch_range's own full refit comes through here too and sets rec_valid again when it is done.)
-    m->rec_valid = false;
+    // everything.  (launch_range's own full refit comes through here too and sets rec.valid again when it is done.)
+    m->rec.valid = false;
     return ECC_OK;
 }
 }  // namespace ecc_internal
@@ -207,7 +204,7 @@ ECC_EXPORT int ecc_metric_set_record_reuse(ecc_metric* m, int on)
 {
     if (!m) return fail(ECC_ERR_INVALID_ARGUMENT, "metric is null");
     m->record_reuse = on < 0 ? 0 : (on > 2 ? 2 : on);
-    m->rec_valid = false;
+    m->rec.valid = false;
     if (!m->record_reuse) m->eager_e1 = true;  // until an evaluation says otherwise
     return ECC_OK;
 }
@@ -222,49 +219,14 @@ ECC_EXPORT int ecc_metric_set_small_eval(ecc_metric* m, int on)
 ECC_EXPORT int ecc_metric_destroy(ecc_metric* m)
 {
     if (!m) return ECC_OK;
-    (void)hipSetDevice(m->ctx->device);
+    (void)hipSetDevice(m->ctx->device);  // the arrays are freed by their destructors, with the metric's device current
     (void)hipStreamSynchronize(m->ctx->stream);
-    if (m->dtr_table_d) (void)hipFree((void*)m->dtr_table_d);
-    if (m->paired_table_d) (void)hipFree((void*)m->paired_table_d);
-    if (m->paired_d) (void)hipFree(m->paired_d);
-    if (m->quads_table_d) (void)hipFree((void*)m->quads_table_d);
-    if (m->quads_d) (void)hipFree(m->quads_d);
-    if (m->Cs_d) (void)hipFree(m->Cs_d);
-    if (m->PinvTs_d) (void)hipFree(m->PinvTs_d);
-    if (m->pair_values_d) (void)hipFree(m->pair_values_d);
-    if (m->cost_d) (void)hipFree(m->cost_d);
-    if (m->indices_d) (void)hipFree(m->indices_d);
-    if (m->K01_d) (void)hipFree(m->K01_d);
-    if (m->records_d) (void)hipFree(m->records_d);
-    if (m->sum_d) (void)hipFree(m->sum_d);
-    if (m->sum_scratch_d) (void)hipFree(m->sum_scratch_d);
-    if (m->Ps_d) (void)hipFree(m->Ps_d);
-    for (double* b : m->Ps_h)
-        if (b) (void)hipHostFree(b);
-    if (m->sum_h) (void)hipHostFree(m->sum_h);
-    if (m->cache_values_d) (void)hipFree(m->cache_values_d);
-    if (m->list_h) (void)hipHostFree(m->list_h);
-    for (int b = 0; b < 2; ++b) {
-        if (m->reuse_h[b]) (void)hipHostFree(m->reuse_h[b]);
-        if (m->reuse_ev[b]) (void)hipEventDestroy(m->reuse_ev[b]);
-    }
     if (m->side_stream) {
         (void)hipStreamSynchronize(m->side_stream);
         (void)hipStreamDestroy(m->side_stream);
     }
-    if (m->fork_ev) (void)hipEventDestroy(m->fork_ev);
-    if (m->join_ev) (void)hipEventDestroy(m->join_ev);
-    if (m->sidx_h) (void)hipHostFree(m->sidx_h);
-    if (m->svals_h) (void)hipHostFree(m->svals_h);
-    if (m->small_ticket_d) (void)hipFree(m->small_ticket_d);
-    if (m->pose_h) (void)hipHostFree(m->pose_h);
-    if (m->pose_PinvTs_d) (void)hipFree(m->pose_PinvTs_d);
-    if (m->pose_Cs_d) (void)hipFree(m->pose_Cs_d);
-    if (m->pose_idx_d) (void)hipFree(m->pose_idx_d);
-    if (m->pose_records_d) (void)hipFree(m->pose_records_d);
-    if (m->pose_values_d) (void)hipFree(m->pose_values_d);
-    if (m->pose_partial_d) (void)hipFree(m->pose_partial_d);
-    if (m->pose_lists_d) (void)hipFree(m->pose_lists_d);
+    for (hipEvent_t ev : {m->fork_ev, m->join_ev, m->reuse_ev[0], m->reuse_ev[1]})
+        if (ev) (void)hipEventDestroy(ev);
     delete m;
     return ECC_OK;
 }
@@ -280,24 +242,12 @@ ECC_EXPORT int ecc_metric_set_projections(ecc_metric* m, const double* Ps, int n
     if (n_views > m->geom_capacity) {
         HIP_TRY(wait_stream_spin(ctx->stream));
         m->done_generation = m->set_generation;
-        if (m->Cs_d) HIP_TRY(hipFree(m->Cs_d));
-        if (m->PinvTs_d) HIP_TRY(hipFree(m->PinvTs_d));
-        if (m->Ps_d) HIP_TRY(hipFree(m->Ps_d));
-        for (double*& b : m->Ps_h) {
-            if (b) HIP_TRY(hipHostFree(b));
-            b = nullptr;
-        }
-        m->Cs_d = m->PinvTs_d = nullptr;
-        m->Ps_d = nullptr;
-        m->geom_capacity = 0;
         m->dev_valid = false;
-        HIP_TRY(hipMalloc((void**)&m->Cs_d, sizeof(float) * 4 * n_views));
-        HIP_TRY(hipMalloc((void**)&m->PinvTs_d, sizeof(float) * 12 * n_views));
-        HIP_TRY(hipMalloc((void**)&m->Ps_d, sizeof(double) * 12 * n_views));
-        for (int b = 0; b < 2; ++b) {
-            HIP_TRY(hipHostMalloc((void**)&m->Ps_h[b], sizeof(double) * 12 * n_views, hipHostMallocMapped));
-            HIP_TRY(hipHostGetDevicePointer((void**)&m->Ps_h_dev[b], m->Ps_h[b], 0));
-        }
+        m->geom_capacity = 0;  // until all of them have grown: a failed ensure may leave an array freed
+        rc = m->Cs_d.ensure(4 * (int64_t)n_views, ctx->stream);
+        if (!rc) rc = m->PinvTs_d.ensure(12 * (int64_t)n_views, ctx->stream);
+        for (int b = 0; b < 2 && !rc; ++b) rc = m->Ps_h[b].ensure(12 * (int64_t)n_views, 0, ctx->stream);
+        if (rc) return rc;
         m->geom_capacity = n_views;
     }
     // The staging buffer of this call was last read by the e1 launch two calls ago.  In the optimiser pattern
@@ -309,7 +259,7 @@ ECC_EXPORT int ecc_metric_set_projections(ecc_metric* m, const double* Ps, int n
         m->done_generation = m->set_generation;
     }
     const int slot = (int)(g & 1);
-    std::memcpy(m->Ps_h[slot], Ps, sizeof(double) * 12 * (size_t)n_views);
+    std::memcpy(m->Ps_h[slot].host, Ps, sizeof(double) * 12 * (size_t)n_views);
     m->set_generation = g;
     m->n_views = n_views;
     m->P_first.assign(Ps, Ps + 12);
@@ -332,8 +282,8 @@ ECC_EXPORT int ecc_metric_debug_geometry(ecc_metric* m, float* PinvTs, float* Cs
         const int rc1 = ensure_e1(m);
         if (rc1) return rc1;
     }
-    HIP_TRY(hipMemcpyAsync(PinvTs, m->PinvTs_d, sizeof(float) * 12 * m->n_views, hipMemcpyDeviceToHost, m->ctx->stream));
-    HIP_TRY(hipMemcpyAsync(Cs, m->Cs_d, sizeof(float) * 4 * m->n_views, hipMemcpyDeviceToHost, m->ctx->stream));
+    HIP_TRY(hipMemcpyAsync(PinvTs, m->PinvTs_d.ptr, sizeof(float) * 12 * m->n_views, hipMemcpyDeviceToHost, m->ctx->stream));
+    HIP_TRY(hipMemcpyAsync(Cs, m->Cs_d.ptr, sizeof(float) * 4 * m->n_views, hipMemcpyDeviceToHost, m->ctx->stream));
     HIP_TRY(hipStreamSynchronize(m->ctx->stream));
     return ECC_OK;
 }
@@ -344,7 +294,7 @@ ECC_EXPORT int ecc_metric_set_params(ecc_metric* m, double object_radius_mm, dou
     m->object_radius_mm = object_radius_mm;
     m->dkappa = dkappa;
     m->use_corr = use_corr;
-    m->cache_valid = false;
+    m->cache.valid = false;
     return ECC_OK;
 }
 
@@ -353,7 +303,7 @@ ECC_EXPORT int ecc_metric_set_sampling(ecc_metric* m, int mode)
     if (!m) return fail(ECC_ERR_INVALID_ARGUMENT, "metric is null");
     if (mode < ECC_SAMPLING_AUTO || mode > ECC_SAMPLING_REFERENCE) return fail(ECC_ERR_INVALID_ARGUMENT, "unknown sampling mode");
     m->sampling = mode;
-    m->cache_valid = false;
+    m->cache.valid = false;
     return ECC_OK;
 }
 
@@ -361,7 +311,7 @@ ECC_EXPORT int ecc_metric_set_incremental(ecc_metric* m, int enable)
 {
     if (!m) return fail(ECC_ERR_INVALID_ARGUMENT, "metric is null");
     m->incremental = enable ? 1 : 0;
-    m->cache_valid = false;
+    m->cache.valid = false;
     return ECC_OK;
 }
 
@@ -370,19 +320,13 @@ ECC_EXPORT int ecc_metric_set_incremental(ecc_metric* m, int enable)
 ECC_EXPORT int ecc_metric_device_bytes(const ecc_metric* m, int64_t* paired_bytes, int64_t* quad_bytes, int64_t* other_bytes)
 {
     if (!m) return fail(ECC_ERR_INVALID_ARGUMENT, "metric is null");
-    const int64_t n = (int64_t)m->dtrs.size();
-    const int64_t paired = m->paired_d ? (int64_t)(m->n_alpha + 1) * m->pitch * 2 * 4 * n : 0;
-    const int64_t quads = m->quads_d ? m->quad_floats * 4 * n : 0;
-    int64_t other = 0;
-    other += (int64_t)sizeof(float*) * n * (2 + (m->quads_table_d ? 1 : 0));
-    other += (int64_t)m->geom_capacity * (16 * (int64_t)sizeof(float) + 12 * (int64_t)sizeof(double));
-    other += m->pair_capacity * 4 + (int64_t)m->cost_capacity * 4 + m->indices_capacity * 4 + m->K01_capacity * 4;
-    other += m->records_capacity * (int64_t)sizeof(EccPairRecord) + m->cache_capacity * 4;
-    other += m->pose_PinvTs_capacity * 4 + m->pose_Cs_capacity * 4 + m->pose_idx_capacity * 4 + m->pose_values_capacity * 4;
-    other += m->pose_records_capacity * (int64_t)sizeof(EccPairRecord) + m->pose_partial_capacity * 8 + m->pose_lists_capacity * 4;
-    other += (int64_t)ecc_sum_scratch_bytes() + 8;
-    if (paired_bytes) *paired_bytes = paired;
-    if (quad_bytes) *quad_bytes = quads;
+    const int64_t other = m->dtr_table_d.bytes() + m->paired_table_d.bytes() + m->quads_table_d.bytes() + m->Cs_d.bytes() +
+                          m->PinvTs_d.bytes() + m->pair_values_d.bytes() + m->cost_d.bytes() + m->indices_d.bytes() + m->K01_d.bytes() +
+                          m->records_d.bytes() + m->cache_values_d.bytes() + m->pose_PinvTs_d.bytes() + m->pose_Cs_d.bytes() +
+                          m->pose_idx_d.bytes() + m->pose_values_d.bytes() + m->pose_records_d.bytes() + m->pose_partial_d.bytes() +
+                          m->pose_lists_d.bytes() + m->sum_scratch_d.bytes() + m->sum_d.bytes();
+    if (paired_bytes) *paired_bytes = m->paired_d.bytes();
+    if (quad_bytes) *quad_bytes = m->quads_d.bytes();
     if (other_bytes) *other_bytes = other;
     return ECC_OK;
 }
@@ -455,8 +399,8 @@ ECC_EXPORT int ecc_metric_evaluate_for_image_pair(ecc_metric* m, int i, int j, i
         (void)hipFree(out_d);
         return rc;
     }
-    p.Cs = m->Cs_d;
-    p.PinvTs = m->PinvTs_d;
+    p.Cs = m->Cs_d.ptr;
+    p.PinvTs = m->PinvTs_d.ptr;
     p.out = out_d;
     p.K01_out = K01_d;
     p.n_out = n_d;
@@ -622,5 +566,5 @@ ECC_EXPORT int ecc_metric_balanced_shards(ecc_metric* m, int world, int64_t* bou
     double radius = 0;
     ecc_metric_get_object_radius(m, &radius);
     // the matrices of the last setProjectionMatrices are still in their pinned staging buffer
-    return ecc_pair_shards_balanced(m->Ps_h[m->set_generation & 1], m->n_views, radius, world, bounds);
+    return ecc_pair_shards_balanced(m->Ps_h[m->set_generation & 1].host, m->n_views, radius, world, bounds);
 }

@@ -197,20 +197,6 @@ constexpr uint64_t POSE_PENDING = 0x7ff8ecc0dead0002ull;  // the two-deep form's
 
 size_t align64(size_t x) { return (x + 63) & ~(size_t)63; }
 
-int ensure_pose_block(ecc_metric* m, size_t bytes)
-{
-    if ((size_t)m->pose_h_bytes >= bytes) return ECC_OK;
-    HIP_TRY(wait_stream_spin(m->ctx->stream));  // a launch may still be reading the old block
-    if (m->pose_h) HIP_TRY(hipHostFree(m->pose_h));
-    m->pose_h = m->pose_h_dev = nullptr;
-    m->pose_h_bytes = 0;
-    const size_t cap = std::max<size_t>(bytes + bytes / 2, 1 << 16);
-    HIP_TRY(hipHostMalloc((void**)&m->pose_h, cap, hipHostMallocMapped));
-    HIP_TRY(hipHostGetDevicePointer((void**)&m->pose_h_dev, m->pose_h, 0));
-    m->pose_h_bytes = (int64_t)cap;
-    return ECC_OK;
-}
-
 // One batch: poses with off[0] = 0 ... off[K] = Q columns, every pose at most ECC_POSE_BATCH_MAX_MOVED of them.
 // base: the matrices the poses are deltas of (n x 12); base_vals_d: the n (n - 1) / 2 pair values of the base on the device.
 // sums[k]: the float64 sum over all pair values of pose k.
@@ -224,62 +210,59 @@ int run_batch(ecc_metric* m, const double* base, const float* base_vals_d, int K
     // the pinned block: extended matrices | results | off | views
     const size_t b_Ps = 0, b_out = align64(sizeof(double) * 12 * (size_t)(n + Q)), b_off = b_out + align64(sizeof(double) * (size_t)K),
                  b_views = b_off + align64(sizeof(int32_t) * (size_t)(K + 1)), b_end = b_views + align64(sizeof(int32_t) * (size_t)std::max(Q, 1));
-    int rc = ensure_pose_block(m, b_end);
+    int rc = m->pose_h.ensure((int64_t)b_end, 1 << 16, ctx->stream);
     if (rc) return rc;
-    double* Ps_ext = reinterpret_cast<double*>(m->pose_h + b_Ps);
-    volatile uint64_t* out = reinterpret_cast<volatile uint64_t*>(m->pose_h + b_out);
+    char* const pose_h = m->pose_h.host;
+    const char* const pose_h_dev = m->pose_h.dev;
+    double* Ps_ext = reinterpret_cast<double*>(pose_h + b_Ps);
+    volatile uint64_t* out = reinterpret_cast<volatile uint64_t*>(pose_h + b_out);
     std::memcpy(Ps_ext, base, sizeof(double) * 12 * (size_t)n);
     if (Q > 0) std::memcpy(Ps_ext + 12 * (size_t)n, moved_Ps, sizeof(double) * 12 * (size_t)Q);
-    std::memcpy(m->pose_h + b_off, off, sizeof(int32_t) * (size_t)(K + 1));
-    if (Q > 0) std::memcpy(m->pose_h + b_views, views, sizeof(int32_t) * (size_t)Q);
+    std::memcpy(pose_h + b_off, off, sizeof(int32_t) * (size_t)(K + 1));
+    if (Q > 0) std::memcpy(pose_h + b_views, views, sizeof(int32_t) * (size_t)Q);
     for (int k = 0; k < K; ++k) out[k] = POSE_PENDING;
     std::atomic_thread_fence(std::memory_order_seq_cst);
 
-    rc = ensure_capacity(&m->pose_PinvTs_d, &m->pose_PinvTs_capacity, 12 * (n + Q), ctx->stream);
-    if (!rc) rc = ensure_capacity(&m->pose_Cs_d, &m->pose_Cs_capacity, 4 * (n + Q), ctx->stream);
-    if (!rc) rc = ensure_capacity(&m->pose_idx_d, &m->pose_idx_capacity, 4 * std::max<int64_t>(entries, 1), ctx->stream);
-    if (!rc) rc = ensure_capacity(&m->pose_records_d, &m->pose_records_capacity, std::max<int64_t>(entries, 1), ctx->stream);
-    if (!rc) rc = ensure_capacity(&m->pose_values_d, &m->pose_values_capacity, std::max<int64_t>(entries, 1), ctx->stream);
-    if (!rc) rc = ensure_capacity(&m->pose_partial_d, &m->pose_partial_capacity, (int64_t)K * SUM_SLICES, ctx->stream);
-    if (!rc) rc = ensure_capacity(&m->pose_lists_d, &m->pose_lists_capacity, (int64_t)K + 1 + std::max(Q, 1), ctx->stream);
+    rc = m->pose_PinvTs_d.ensure(12 * (n + Q), ctx->stream);
+    if (!rc) rc = m->pose_Cs_d.ensure(4 * (n + Q), ctx->stream);
+    if (!rc) rc = m->pose_idx_d.ensure(4 * std::max<int64_t>(entries, 1), ctx->stream);
+    if (!rc) rc = m->pose_records_d.ensure(std::max<int64_t>(entries, 1), ctx->stream);
+    if (!rc) rc = m->pose_values_d.ensure(std::max<int64_t>(entries, 1), ctx->stream);
+    if (!rc) rc = m->pose_partial_d.ensure((int64_t)K * SUM_SLICES, ctx->stream);
+    if (!rc) rc = m->pose_lists_d.ensure((int64_t)K + 1 + std::max(Q, 1), ctx->stream);
     if (rc) return rc;
 
     EccPairParams p;
     rc = fill_pair_params(m, &p, n_pairs, /*need_e1=*/false);  // the sampling mode of an all-pairs evaluation
     if (rc) return rc;
-    PoseLists in = {reinterpret_cast<const int32_t*>(m->pose_h_dev + b_off), reinterpret_cast<const int32_t*>(m->pose_h_dev + b_views)};
+    PoseLists in = {reinterpret_cast<const int32_t*>(pose_h_dev + b_off), reinterpret_cast<const int32_t*>(pose_h_dev + b_views)};
     // index tuples + lists (K workgroups) and E1 of the n + Q extended matrices (the workgroups behind them): one launch
     const unsigned e1_blocks = entries > 0 ? (unsigned)((n + Q + 63) / 64) : 0u;
-    hipLaunchKernelGGL(pose_list_kernel, dim3((unsigned)K + e1_blocks), dim3(256), 0, ctx->stream, in, (int)n, K, Q, m->pose_idx_d,
-                       m->pose_lists_d, reinterpret_cast<const double*>(m->pose_h_dev + b_Ps), m->pose_PinvTs_d, m->pose_Cs_d);
+    hipLaunchKernelGGL(pose_list_kernel, dim3((unsigned)K + e1_blocks), dim3(256), 0, ctx->stream, in, (int)n, K, Q, m->pose_idx_d.ptr,
+                       m->pose_lists_d.ptr, reinterpret_cast<const double*>(pose_h_dev + b_Ps), m->pose_PinvTs_d.ptr, m->pose_Cs_d.ptr);
     HIP_TRY(hipGetLastError());
     if (entries > 0) {
-        p.PinvTs = m->pose_PinvTs_d;
-        p.Cs = m->pose_Cs_d;
-        p.indices = m->pose_idx_d;
-        p.records = m->pose_records_d;
-        p.pair_values = m->pose_values_d;
+        p.PinvTs = m->pose_PinvTs_d.ptr;
+        p.Cs = m->pose_Cs_d.ptr;
+        p.indices = m->pose_idx_d.ptr;
+        p.records = m->pose_records_d.ptr;
+        p.pair_values = m->pose_values_d.ptr;
         p.first = 0;
         p.count = entries;
         HIP_TRY(ecc_launch_k01(&p, ctx->stream));
-        if (ctx->timing) HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
-        HIP_TRY(ecc_launch_pairs(&p, ctx->stream));
-        if (ctx->timing) {
-            HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
-            ctx->ev_valid[0] = true;
-        }
+        HIP_TRY(launch_pairs_timed(ctx, &p));
     }
     const int slices = n_pairs >= 32768 ? SUM_SLICES : 1;  // ecc_launch_sum_pairs (pairs_kernel.hip)
-    double* out_dev = reinterpret_cast<double*>(m->pose_h_dev + b_out);
+    double* out_dev = reinterpret_cast<double*>(m->pose_h.dev + b_out);
     if (slices == 1)
         hipLaunchKernelGGL(sum_poses_kernel<1>, dim3(1, (unsigned)K), dim3(SUM_THREADS), 0, ctx->stream, base_vals_d, (long long)n_pairs,
-                           (int)n, Q, m->pose_lists_d, K, m->pose_values_d, m->pose_partial_d, out_dev);
+                           (int)n, Q, m->pose_lists_d.ptr, K, m->pose_values_d.ptr, m->pose_partial_d.ptr, out_dev);
     else
         hipLaunchKernelGGL(sum_poses_kernel<SUM_SLICES>, dim3(SUM_SLICES, (unsigned)K), dim3(SUM_THREADS), 0, ctx->stream, base_vals_d,
-                           (long long)n_pairs, (int)n, Q, m->pose_lists_d, K, m->pose_values_d, m->pose_partial_d, out_dev);
+                           (long long)n_pairs, (int)n, Q, m->pose_lists_d.ptr, K, m->pose_values_d.ptr, m->pose_partial_d.ptr, out_dev);
     HIP_TRY(hipGetLastError());
     if (slices > 1) {
-        hipLaunchKernelGGL(finish_poses_kernel, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, ctx->stream, m->pose_partial_d, slices, K, out_dev);
+        hipLaunchKernelGGL(finish_poses_kernel, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, ctx->stream, m->pose_partial_d.ptr, slices, K, out_dev);
         HIP_TRY(hipGetLastError());
     }
     // the results arrive in pinned memory a few microseconds before the stream is reported idle: poll the last one, then the rest
@@ -322,7 +305,7 @@ int poses_two_deep(ecc_metric* m, const std::vector<int>& which, const double* P
     // one at a time: the pose-delta mode (it keeps the values of ONE previous evaluation), and evaluations small enough
     // for the one-launch path (its hand-over goes through result slot 0 and the host's sum; a few microseconds of device
     // work leave nothing to overlap anyway)
-    if (m->incremental || !m->sum_h || n_pairs <= ECC_SMALL_EVAL_MAX_PAIRS) {
+    if (m->incremental || !m->sum_h.host || n_pairs <= ECC_SMALL_EVAL_MAX_PAIRS) {
         for (int q = 0; q < count; ++q) {
             rc = ecc_metric_set_projections(m, Ps_batch + (size_t)12 * n * which[q], n_views);
             if (rc) return rc;
@@ -331,9 +314,9 @@ int poses_two_deep(ecc_metric* m, const std::vector<int>& which, const double* P
         }
         return ECC_OK;
     }
-    rc = ensure_capacity(&m->pair_values_d, &m->pair_capacity, n_pairs, ctx->stream);
+    rc = m->pair_values_d.ensure(n_pairs, ctx->stream);
     if (rc) return rc;
-    volatile uint64_t* slots = reinterpret_cast<volatile uint64_t*>(m->sum_h);
+    volatile uint64_t* slots = reinterpret_cast<volatile uint64_t*>(m->sum_h.host);
     uint64_t gen_of[2] = {0, 0};
     auto collect = [&](int q) -> int {  // waits for the q-th pose's sum in slot q & 1 (bounded spin, then the stream)
         const int sl = q & 1;
@@ -365,7 +348,7 @@ int poses_two_deep(ecc_metric* m, const std::vector<int>& which, const double* P
         std::atomic_thread_fence(std::memory_order_seq_cst);
         gen_of[sl] = m->set_generation;
         // (slot 1 is not the result slot of the synchronous calls: those launches never take the one-launch path)
-        rc = launch_range(m, 0, n_pairs, m->pair_values_d, nullptr, nullptr, m->sum_h_dev + sl, /*synchronous=*/false);
+        rc = launch_range(m, 0, n_pairs, m->pair_values_d.ptr, nullptr, nullptr, m->sum_h.dev + sl, /*synchronous=*/false);
         if (rc) return rc;
         m->small_pending_count = 0;
         if (q >= 1) {
@@ -395,7 +378,8 @@ int evaluate_deltas(ecc_metric* m, int n_poses, const int32_t* off, const int32_
     ecc_ctx* ctx = m->ctx;
     const int64_t n = m->n_views, n_pairs = n * (n - 1) / 2;
     ecc_mark_busy(m);
-    std::vector<double> base(m->Ps_h[m->set_generation & 1], m->Ps_h[m->set_generation & 1] + 12 * n);
+    const double* Pcur = m->Ps_h[m->set_generation & 1].host;
+    std::vector<double> base(Pcur, Pcur + 12 * n);
     double base_radius = 0.0;
     ecc_metric_get_object_radius(m, &base_radius);
     // the base's pair values: kept between calls (the pose-delta cache), only the pairs of views that changed since are redone
@@ -498,7 +482,8 @@ ECC_EXPORT int ecc_metric_evaluate_pose_deltas(ecc_metric* m, int n_poses, const
     if (rest.empty()) return ECC_OK;
     // what the batch does not take (more moved views than it handles, a changed automatic radius, batching off): the pose's
     // full matrices the sequential way, then the base again
-    const std::vector<double> base(m->Ps_h[m->set_generation & 1], m->Ps_h[m->set_generation & 1] + 12 * n);
+    const double* Pcur = m->Ps_h[m->set_generation & 1].host;
+    const std::vector<double> base(Pcur, Pcur + 12 * n);
     std::vector<double> full(base);
     for (int k : rest) {
         for (int q = moved_offsets[k]; q < moved_offsets[k + 1]; ++q)
@@ -540,7 +525,7 @@ ECC_EXPORT int ecc_metric_evaluate_poses_strided(ecc_metric* m, int n_poses, con
     std::vector<int>&batch_pose = d.batch_pose, &rest = d.rest;
     auto diff_against = [&](const double* base) { ecc_pose_diff::diff(Ps_batch, n_views, mine, base, ECC_POSE_BATCH_MAX_MOVED, 8, &d); };
     bool have_base = m->n_views == n_views && m->set_generation > 0 && (int)m->dtrs.size() >= n_views;
-    if (have_base) diff_against(m->Ps_h[m->set_generation & 1]);
+    if (have_base) diff_against(m->Ps_h[m->set_generation & 1].host);
     if (!have_base || 2 * batch_pose.size() < mine.size()) {
         if ((int)m->dtrs.size() < n_views) return fail(ECC_ERR_INVALID_ARGUMENT, "fewer Radon intermediates than projection matrices");
         diff_against(Ps_batch + pose_doubles * (size_t)mine[0]);

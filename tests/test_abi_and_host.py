@@ -140,3 +140,24 @@ def test_pose_diff_finds_the_moved_views_whatever_the_thread_count(tmp_path):
                     "-o", exe], check=True)
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0 and "ok" in r.stdout, r.stdout + r.stderr
+
+
+def test_view_changes_lists_the_pairs_of_the_changed_views(tmp_path):
+    """csrc/ecc_view_changes.h (host only): the change scan and the pair list of the record-reuse, pose-delta and one-launch
+    paths -- n from 2 to 600 views (past the 512-view skip mask), full, empty and shard ranges (the ones sharding.pair_range
+    cuts), 0, 1, 2 and n/4 changed views: every pair of the range with a changed view once, in its slot, in the order of the
+    loop the paths used before (a verbatim copy in the driver).  The same driver runs under ASan + UBSan in scripts/sanitize.sh."""
+    import subprocess
+    from epipolarconsistency_amd import sharding
+    exe = os.path.join(str(tmp_path), "view_changes")
+    subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", os.path.join(ROOT, "tests", "c", "view_changes.cpp"), "-o", exe],
+                   check=True)
+    ranges = os.path.join(str(tmp_path), "ranges.txt")
+    with open(ranges, "w") as f:
+        for n in (2, 5, 64, 257, 513, 600):
+            for world in (1, 2, 4, 7, 8):
+                for rank in range(world):
+                    first, count = sharding.pair_range(rank, world, n * (n - 1) // 2)
+                    f.write("%d %d %d\n" % (n, first, count))
+    r = subprocess.run([exe, ranges], capture_output=True, text=True)
+    assert r.returncode == 0 and "ok" in r.stdout and "132 extra ranges" in r.stdout, r.stdout + r.stderr
