@@ -247,15 +247,19 @@ def evaluate_all(Ps, dtrs, n_u, n_v, object_radius_mm=0.0, dkappa=0.0, is_deriva
 
 
 def evaluate_pairs(Ps, dtrs, n_u, n_v, idx4, object_radius_mm=0.0, dkappa=0.0, is_derivative=True,
-                   native=False):
+                   want_K01=False, native=False):
+    """Index-list ECC: idx4 rows (P0, P1, dtr0, dtr1).  Returns dict(mean, pairs, K01s) (K01s: (len(idx4), 16)
+    float32 or None)."""
     n_t, n_alpha = dtrs[0].shape
     keep, arr = _dtr_ptrs(dtrs)
     idx4 = np.ascontiguousarray(idx4, np.int32).reshape(-1, 4)
     out = np.zeros(len(idx4), np.float32)
+    K01s = np.zeros((len(idx4), 16), np.float32) if want_K01 else None
     mean = lib(native).eccor_evaluate_pairs(
         len(Ps), pack_Ps(Ps), len(dtrs), arr, n_u, n_v, n_alpha, n_t, float(object_radius_mm),
-        float(dkappa), 1 if is_derivative else 0, idx4.reshape(-1), len(idx4), out, None)
-    return dict(mean=mean, pairs=out)
+        float(dkappa), 1 if is_derivative else 0, idx4.reshape(-1), len(idx4), out,
+        K01s.ctypes.data if want_K01 else None)
+    return dict(mean=mean, pairs=out, K01s=K01s)
 
 
 def evaluate_for_image_pair(Ps, dtrs, i, j, n_u, n_v, object_radius_mm=0.0, dkappa=0.0, derivative=True):
@@ -385,6 +389,15 @@ def set_variant(v, native=False):
     L = lib(native)
     L.eccor_set_variant.argtypes = [C.c_int]
     L.eccor_set_variant(int(v))
+
+
+def set_probe(bits):
+    """eccor_set_probe: binary64 steps inside variant 1's sampling (diagnostics).  Bit 128: the texel position and the
+    bilinear weights in binary64 as well -- with variant 1, every sample coordinate exact (no fp32 rounding between the
+    matrices and the texels)."""
+    L = lib()
+    L.eccor_set_probe.argtypes = [C.c_int]
+    L.eccor_set_probe(int(bits))
 
 
 def set_use_corr(v):

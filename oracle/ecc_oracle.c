@@ -569,6 +569,22 @@ ECCOR_API void eccor_radon_bins(const float *img, int n_u, int n_v, int n_alpha,
 static int g_probe = 0;
 ECCOR_API void eccor_set_probe(int bits) { g_probe = bits; }
 
+/* eccor_tex2d's rule (clamp addressing, linear filter) at a binary64 position with binary64 weights (probe bit 128). */
+static double or_tex2d_f64(const float *img, int W, int H, double x, double y)
+{
+    double xb = x - 0.5, yb = y - 0.5;
+    double fi = floor(xb), fj = floor(yb);
+    double fx = xb - fi, fy = yb - fj;
+    int i = (int)fi, j = (int)fj;
+    int i0 = or_clampi(i, 0, W - 1), i1 = or_clampi(i + 1, 0, W - 1);
+    int j0 = or_clampi(j, 0, H - 1), j1 = or_clampi(j + 1, 0, H - 1);
+    double T00 = img[(size_t)j0 * W + i0], T10 = img[(size_t)j0 * W + i1];
+    double T01 = img[(size_t)j1 * W + i0], T11 = img[(size_t)j1 * W + i1];
+    double r0 = (1.0 - fx) * T00 + fx * T10;
+    double r1 = (1.0 - fx) * T01 + fx * T11;
+    return (1.0 - fy) * r0 + fy * r1;
+}
+
 static float or_redundancy_f64(const float *K, const float *dtr, int n_alpha, int n_t,
                                float range_t, double x0, double x1, int is_derivative)
 {
@@ -591,6 +607,10 @@ static float or_redundancy_f64(const float *K, const float *dtr, int n_alpha, in
     d = -(l2 / len) / (double)range_t + 0.5;
     if (g_probe & 64) d = (float)((float)(-(float)(l2 / len) / range_t) + 0.5f);
     if (a > 1) { a -= 1; d = 1 - d; moved = 1; }
+    if (g_probe & 128) { /* texel position and bilinear weights in binary64 too: no rounding of the sample coordinates */
+        double v = or_tex2d_f64(dtr, n_alpha, n_t, a * n_alpha, d * n_t);
+        return (float)(is_derivative && moved ? -v : v);
+    }
     if (is_derivative && moved) return -eccor_tex2d_norm(dtr, n_alpha, n_t, (float)a, (float)d);
     return +eccor_tex2d_norm(dtr, n_alpha, n_t, (float)a, (float)d);
 }

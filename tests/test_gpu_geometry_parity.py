@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import geometry_catalog as G
+import pose_response
 
 pytestmark = pytest.mark.gpu
 
@@ -158,20 +159,8 @@ def test_fitted_polynomials_on_every_geometry(gpu_ctx):
 # ---- pair values against the oracle -------------------------------------------------------------------------------------
 def _make_case(gpu_ctx, name, n_alpha, n_t, n=N_VIEWS):
     """Ps, n_u, n_v, device dtrs (aliasing the returned slabs) and their read-back copies."""
-    import torch
-    import epipolarconsistency_amd as E
-    from epipolarconsistency_amd import synthetic
     Ps, n_u, n_v = G.make(name, n)
-    dev = torch.device("cuda", gpu_ctx.device)
-    slabs = torch.zeros((n, E.slab_floats(n_alpha, n_t)), dtype=torch.float32, device=dev)
-    dtrs = []
-    for a in range(0, n, 64):
-        imgs = synthetic.projections_torch(Ps[a:a + 64], n_u, n_v, G.phantom(), dev)
-        torch.cuda.synchronize()
-        dtrs += E.RadonIntermediate.compute_into(gpu_ctx, imgs, slabs[a:a + 64], n_alpha, n_t)
-        gpu_ctx.synchronize()
-        del imgs
-    host = [d.readback() for d in dtrs]
+    slabs, dtrs, host = pose_response.device_case(gpu_ctx, Ps, n_u, n_v, n_alpha, n_t, G.phantom())
     return Ps, n_u, n_v, slabs, dtrs, host
 
 
