@@ -289,7 +289,7 @@ struct ecc_metric {
     DeviceArray<float> K01_d;
     DeviceArray<EccPairRecord> records_d;  // per-pair geometry between k01_kernel and pairs_kernel
     DeviceArray<double> sum_d;
-    DeviceArray<char> sum_scratch_d;  // partials + ticket of the multi-workgroup sum (zeroed; pairs_kernel.hip)
+    DeviceArray<char> sum_scratch_d;  // partials + ticket of the multi-workgroup sum (zeroed; sum_kernel.hip)
     // pinned host staging, mapped into the device's address space (zero-copy: the 38 KB of matrices and the 8-byte
     // result cross PCIe inside the kernels, no copy commands).  Two matrix buffers, used alternately: an evaluate
     // call returns only after the stream has executed everything up to its result, so the buffer of the call before

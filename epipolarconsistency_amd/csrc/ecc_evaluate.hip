@@ -7,6 +7,7 @@
 // (launch_range), the one launch for small evaluations (try_small_eval), the pose-delta path (evaluate_cached), and the
 // exported evaluate calls on top of them.
 #include "ecc_capi_internal.h"
+#include "ecc_sum_order.h"
 
 #include <iterator>
 
@@ -121,36 +122,6 @@ hipError_t wait_values(ecc_metric* m, int64_t count)
     return hipSuccess;
 }
 
-// The float64 sum of `count` <= 4096 pair values exactly as sum_pairs_kernel forms it (pairs_kernel.hip; ref:
-// ...RadonIntermediate.cpp:216-224): thread t of its 1024 holds ((0 + v[4t]) + (0 + v[4t+1])) + ((0 + v[4t+2]) + (0 + v[4t+3]))
-// (one float4 at most for such a count), thread 0 then adds the up to three values past the last float4, the 64 threads
-// of a wave are combined by the shuffle-down tree (offsets 32 ... 1), the 16 wave sums are added in order.  IEEE binary64
-// additions in the same order: the same bits.
-double small_sum_on_host(const float* v, int64_t count)
-{
-    const int64_t n4 = count >> 2;
-    double tot = 0.0;
-    for (int w = 0; w < 16; ++w) {
-        double a[64];
-        for (int l = 0; l < 64; ++l) {
-            const int64_t t = 64 * w + l;
-            double acc = 0.0;
-            if (t < n4) {
-                const double a0 = 0.0 + (double)v[4 * t], a1 = 0.0 + (double)v[4 * t + 1], a2 = 0.0 + (double)v[4 * t + 2],
-                             a3 = 0.0 + (double)v[4 * t + 3];
-                acc = (a0 + a1) + (a2 + a3);
-            }
-            if (t == 0)
-                for (int64_t k = n4 << 2; k < count; ++k) acc += (double)v[k];
-            a[l] = acc;
-        }
-        for (int off = 32; off > 0; off >>= 1)
-            for (int l = 0; l < off; ++l) a[l] += a[l + off];  // what lane 0 of __shfl_down's tree ends up with
-        tot += a[0];
-    }
-    return tot;
-}
-
 // Waits for the "done" word of the one-launch evaluation (the result slot, armed by the caller) and adds the values.
 hipError_t wait_small_eval(ecc_metric* m, int64_t count, double* sum)
 {
@@ -162,7 +133,8 @@ hipError_t wait_small_eval(ecc_metric* m, int64_t count, double* sum)
     if (bits != ECC_SMALL_DONE_TOKEN) return hipErrorUnknown;  // the kernel found its argument views inconsistent
     const hipError_t ev = wait_values(m, count);
     if (ev != hipSuccess) return ev;
-    *sum = small_sum_on_host(m->svals_h.host, count);
+    // (ecc_launch_sum_pairs' choice of slices; at most ECC_SMALL_EVAL_MAX_PAIRS values, under 2 us)
+    *sum = ecc_sum::sum_on_host(m->svals_h.host, count, ecc_sum::slices(count, m->sum_scratch_d.ptr != nullptr));
     return hipSuccess;
 }
 

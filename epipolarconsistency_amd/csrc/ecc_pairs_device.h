@@ -11,6 +11,7 @@
 #include <float.h>
 
 #include "ecc_layout.h"
+#include "ecc_sum_order.h"
 
 namespace {
 
@@ -1274,7 +1275,7 @@ __device__ float sample_line_plain(const float* K, float x0, float x1, GlobalFlo
 // EpipolarConsistencyCommon.hxx:152-171 as fp32 source expressions, sin / cos / atan2 through binary64 and rounded once,
 // exact fp32 bilinear rule with index clamps on the dtr's own slab); float64 partial sums of this thread.
 // STAGE: every sample's fp32 term(s) go to stage[k] (CORR: stage[k], stage[stage_stride + k], stage[2 * stage_stride + k])
-// instead of into the sums -- the wide forms (1024 threads per pair) add them afterwards with reference_resum in the
+// instead of into the sums -- the wide forms (1024 threads per pair) add them afterwards with resum_staged in the
 // order of a 256-thread workgroup.
 template <bool CORR, bool STAGE = false>
 __device__ __forceinline__ void reference_loop(const EccPairParams& p, const float (&K0)[8], const float (&K1)[8],
@@ -1320,14 +1321,16 @@ __device__ __forceinline__ void reference_loop(const EccPairParams& p, const flo
     }
 }
 
-// The staged terms of reference_loop<CORR, true>, added the way thread T of a 256-thread workgroup accumulates them
-// (k = T, T + 256, ... while kappa < kappa_max): the bits of pairs_reference_kernel<CORR, 4>'s per-thread sums.
+// The staged per-sample terms of a pair (pair_accumulate<.., WPP>'s stage[k]; reference_loop<CORR, true>'s) added the way the
+// thread that starts at first_k accumulates them when `stride` threads share the pair: k = first_k, first_k + stride, ... while
+// kappa < kappa_max.  stride = 64: the order of ONE wave, i.e. pairs_kernel's per-lane sums -- this loop is why the
+// several-waves-per-pair forms have its bits; stride = 256: pairs_reference_kernel<CORR, 4>'s per-thread sums.
 template <bool CORR>
-__device__ __forceinline__ void reference_resum(const EccPairParams& p, float dkappa, float kappa_max, int T, const float* stage,
-                                                int stage_stride, double& acc, double& mom2, double& mom3, double& mom4)
+__device__ __forceinline__ void resum_staged(const EccPairParams& p, float dkappa, float kappa_max, int first_k, int stride,
+                                             const float* stage, int stage_stride, double& acc, double& mom2, double& mom3, double& mom4)
 {
-    for (int k = T; k < p.k_limit; k += 256) {
-        const float kappa = dkappa * 0.5f + dkappa * k;  // the fp32 operations of reference_loop
+    for (int k = first_k; k < p.k_limit; k += stride) {
+        const float kappa = dkappa * 0.5f + dkappa * k;  // ref: ...RadonIntermediate.cu:259 (same fp32 ops)
         if (kappa >= kappa_max) break;
         if (!CORR) {
             acc += (double)stage[k];
@@ -1339,6 +1342,66 @@ __device__ __forceinline__ void reference_resum(const EccPairParams& p, float dk
     }
 }
 
+// ---- epilogues of the pair kernels: from a thread's float64 sums to the stored pair value ----
+
+// The sum (CORR: the three moments) of a wave's 64 lanes, in lane 0.
+template <bool CORR>
+__device__ __forceinline__ void wave_sum_pair(double& acc, double& mom2, double& mom3, double& mom4)
+{
+    if (!CORR) {
+        ecc_sum::wave_sum(acc);
+    } else {  // one interleaved tree (as three calls of wave_sum the compiler allocates the CORR kernels differently)
+        for (int off = 32; off > 0; off >>= 1) {
+            mom2 += __shfl_down(mom2, off);
+            mom3 += __shfl_down(mom3, off);
+            mom4 += __shfl_down(mom4, off);
+        }
+    }
+}
+
+// Several waves per pair, reference forms: every wave's lane 0 leaves its sums in part[.][wave] (LDS; a barrier follows) ...
+template <bool CORR, int NW>
+__device__ __forceinline__ void put_wave_partials(double (*part)[NW], int wave, double acc, double mom2, double mom3, double mom4)
+{
+    part[0][wave] = CORR ? mom2 : acc;
+    if (CORR) part[1][wave] = mom3, part[2][wave] = mom4;
+}
+
+// ... and they are added in wave order.
+template <bool CORR, int NW>
+__device__ __forceinline__ void add_wave_partials(const double (*part)[NW], double& acc, double& mom2, double& mom3, double& mom4)
+{
+    const auto in_wave_order = [part](int row) {
+        double sum = part[row][0];
+#pragma unroll
+        for (int w = 1; w < NW; ++w) sum += part[row][w];
+        return sum;
+    };
+    acc = mom2 = in_wave_order(0);
+    if (CORR) mom3 = in_wave_order(1), mom4 = in_wave_order(2);
+}
+
+// The pair's value from its sums.  CORR: the host epilogue of the reference, cc = xy / (sqrt(xx) sqrt(yy)),
+// cost = (1 - cc) * weight(= 1) (ref: ...RadonIntermediate.cpp:127-131,199-210); mom2, mom3, mom4 = sums of x*x, y*y, x*y.
+template <bool CORR>
+__device__ __forceinline__ float pair_value(double acc, double mom2, double mom3, double mom4)
+{
+    if (!CORR) return (float)acc;
+    const float xx = (float)mom2, yy = (float)mom3, xy = (float)mom4;
+    const float corr = (float)((double)xy / (sqrt((double)xx) * sqrt((double)yy)));
+    return (1.0f - corr) * 1.0f;
+}
+
+// By lane 0 of the pair's (first) wave: the value into the values array (at its slot, if the launch has value_slots) and,
+// unless the launch is an index list, into the cost image.  ci, cj are references so that a caller may name fields of the
+// record: they are read only if the cost image is written.
+// (small_eval_kernel writes its own three lines: it has no value_slots, and with this helper inlined the compiler allocates
+// the whole kernel differently -- two scalar spills more or less per instantiation.)
+__device__ __forceinline__ void store_pair_value(const EccPairParams& p, long long local, const int& ci, const int& cj, float val)
+{
+    if (p.pair_values) p.pair_values[p.value_slots ? (long long)p.value_slots[local] : local] = val;
+    if (p.cost && !p.indices) p.cost[(size_t)ci + (size_t)cj * p.n_views] = val;
+}
 
 }  // namespace
 

@@ -15,13 +15,14 @@
 //   pairs_kernel  ONE launch over it (partner-major: neighbours in the launch sample the same two Radon intermediates under
 //                 slightly different geometries -- their lines are shared in the L1 / L2)
 //   sum_poses     ONE launch: per pose, the float64 sum over ALL n (n - 1) / 2 values -- the base's with the pose's own
-//                 substituted -- in exactly the order sum_pairs_kernel / sum_pairs_split_kernel add them
+//                 substituted -- in the order of ecc_sum_order.h
 //   finish_poses  the slice sums of a pose added in slice order, stored to pinned host memory
 // A pair value depends on its two matrices, its two Radon intermediates and the parameters only, the sampling mode is the one
 // an evaluation of n (n - 1) / 2 pairs resolves to, and the sum's order is reproduced: every mean has the bits of
 // ecc_metric_set_projections + ecc_metric_evaluate_all for that pose (tests/test_gpu_pose_batch.py).
 #include "ecc_capi_internal.h"
 #include "ecc_pose_diff.h"
+#include "ecc_sum_order.h"
 
 using namespace ecc_internal;
 
@@ -34,9 +35,11 @@ using namespace ecc_internal;
 
 namespace {
 
-constexpr int SUM_THREADS = 1024;   // sum_pairs_kernel / sum_pairs_split_kernel (pairs_kernel.hip): the order below is theirs
-constexpr int SUM_SLICES = 16;      // SUM_BLOCKS of sum_pairs_split_kernel
+constexpr int SUM_THREADS = ecc_sum::THREADS, SUM_SLICES = ecc_sum::SLICES;
 constexpr int STAGE_F4 = 2 * SUM_THREADS;  // float4 per staged chunk: every thread's k, k + 1024 -- its own order is kept across chunks
+// poses per batch: the sum's grid is slices x poses, half a million workgroups at most
+constexpr size_t POSE_BATCH_MAX_POSES = (1 << 19) / SUM_SLICES;
+static_assert(POSE_BATCH_MAX_POSES < 65536, "poses are the y dimension of sum_poses_kernel's grid");
 
 struct PoseLists {
     const int32_t* off;    // n_poses + 1: first column of each pose (off[0] = 0, off[n_poses] = Q)
@@ -105,12 +108,9 @@ __global__ __launch_bounds__(256) void pose_list_kernel(PoseLists in, int n, int
 }
 
 // The float64 sum of a pose's `count` pair values = base[0 .. count) with the pose's own values substituted, in the order of
-// sum_pairs_kernel (SLICES = 1: counts below 32 768) or sum_pairs_split_kernel (SLICES = 16) -- pairs_kernel.hip, ref:
-// ...RadonIntermediate.cpp:216-224: slice s covers the float4 [s * per, min(n4, (s + 1) * per)); thread t of 1024 adds the
-// components of its float4 k = lo + t, lo + t + 1024, ... into four accumulators, (a0 + a1) + (a2 + a3), thread 0 of the last
-// slice then the up to three values past the last float4, the shuffle-down tree over a wave, the 16 wave sums in order.
+// ecc_sum_order.h for SLICES slices (run_batch takes ecc_sum::slices, as the sum of one evaluation does).
 // Workgroup (slice, pose): the slice is staged through LDS in chunks of 2048 float4, the pose's values that fall into the chunk
-// are scattered over the base's, and the threads add from LDS.  IEEE binary64 additions in the same order: the same bits.
+// are scattered over the base's, and the threads add from LDS.
 template <int SLICES>
 __global__ __launch_bounds__(SUM_THREADS) void sum_poses_kernel(const float* __restrict__ base, long long count, int n, int Q,
                                                                 const int32_t* __restrict__ lists_d, int n_poses,
@@ -125,11 +125,11 @@ __global__ __launch_bounds__(SUM_THREADS) void sum_poses_kernel(const float* __r
     const int o0 = lists_d[k], c = lists_d[k + 1] - o0;
     if (t < c) M[t] = lists_d[n_poses + 1 + o0 + t];
     const long long n4 = count >> 2;
-    const long long per = (n4 + SLICES - 1) / SLICES;
-    const long long lo = (long long)slice * per, hi = min(n4, lo + per);
+    long long lo, hi;
+    ecc_sum::slice_bounds(n4, SLICES, slice, &lo, &hi);
     const bool owns_tail = slice == SLICES - 1;
     const float4* __restrict__ b4 = reinterpret_cast<const float4*>(base);
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    ecc_sum::Acc4 a;
     if (owns_tail && t < 4) tail[t] = (n4 << 2) + t < count ? base[(n4 << 2) + t] : 0.f;
     bool first_chunk = true;
     for (long long c0 = lo; c0 < hi || first_chunk; c0 += STAGE_F4) {
@@ -153,33 +153,23 @@ __global__ __launch_bounds__(SUM_THREADS) void sum_poses_kernel(const float* __r
             }
         }
         __syncthreads();
-        for (long long kk = c0 + t; kk < ce; kk += SUM_THREADS) {
-            const float4 v = reinterpret_cast<const float4*>(stage)[kk - c0];
-            a0 += (double)v.x;
-            a1 += (double)v.y;
-            a2 += (double)v.z;
-            a3 += (double)v.w;
-        }
+        for (long long kk = c0 + t; kk < ce; kk += SUM_THREADS) ecc_sum::add(a, reinterpret_cast<const float4*>(stage)[kk - c0]);
         __syncthreads();  // before the next chunk overwrites the stage
         first_chunk = false;
     }
-    double acc = (a0 + a1) + (a2 + a3);
-    if (owns_tail && t == 0)
-        for (long long q = n4 << 2; q < count; ++q) acc += (double)tail[q - (n4 << 2)];
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
-    if ((t & 63) == 0) s[t >> 6] = acc;
-    __syncthreads();
+    double acc = ecc_sum::combine(a);
+    if (owns_tail && t == 0) ecc_sum::add_tail(acc, tail, n4, count);
+    ecc_sum::stage_wave_sums(acc, s);
     if (t == 0) {
-        double part = 0.0;
-        for (int w = 0; w < SUM_THREADS / 64; w++) part += s[w];
-        if (SLICES == 1)  // sum_pairs_kernel's own last step: this IS the result (no finish_poses_kernel launch)
+        const double part = ecc_sum::waves_in_order(s);
+        if (SLICES == 1)  // one slice: this IS the result (no finish_poses_kernel launch)
             __hip_atomic_store(reinterpret_cast<unsigned long long*>(out_host) + k, (unsigned long long)__double_as_longlong(part),
                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         else partial[(size_t)k * SLICES + slice] = part;
     }
 }
 
-// Pose k's slice sums in slice order (sum_pairs_split_kernel's last arriver; with one slice: 0.0 + the sum, the same number)
+// Pose k's slice sums added in slice order, as sum_pairs_split_kernel's last arriver does (ecc_sum_order.h)
 // -> the pinned result array (system-scope store: visible to the host before the stream is reported idle).
 __global__ __launch_bounds__(256) void finish_poses_kernel(const double* __restrict__ partial, int slices, int n_poses,
                                                            double* __restrict__ out_host)
@@ -252,14 +242,12 @@ int run_batch(ecc_metric* m, const double* base, const float* base_vals_d, int K
         HIP_TRY(ecc_launch_k01(&p, ctx->stream));
         HIP_TRY(launch_pairs_timed(ctx, &p));
     }
-    const int slices = n_pairs >= 32768 ? SUM_SLICES : 1;  // ecc_launch_sum_pairs (pairs_kernel.hip)
+    // ecc_launch_sum_pairs' choice for the metric's own evaluations
+    const int slices = ecc_sum::slices(n_pairs, m->sum_scratch_d.ptr != nullptr);
     double* out_dev = reinterpret_cast<double*>(m->pose_h.dev + b_out);
-    if (slices == 1)
-        hipLaunchKernelGGL(sum_poses_kernel<1>, dim3(1, (unsigned)K), dim3(SUM_THREADS), 0, ctx->stream, base_vals_d, (long long)n_pairs,
-                           (int)n, Q, m->pose_lists_d.ptr, K, m->pose_values_d.ptr, m->pose_partial_d.ptr, out_dev);
-    else
-        hipLaunchKernelGGL(sum_poses_kernel<SUM_SLICES>, dim3(SUM_SLICES, (unsigned)K), dim3(SUM_THREADS), 0, ctx->stream, base_vals_d,
-                           (long long)n_pairs, (int)n, Q, m->pose_lists_d.ptr, K, m->pose_values_d.ptr, m->pose_partial_d.ptr, out_dev);
+    hipLaunchKernelGGL(slices == 1 ? sum_poses_kernel<1> : sum_poses_kernel<SUM_SLICES>, dim3((unsigned)slices, (unsigned)K), dim3(SUM_THREADS), 0,
+                       ctx->stream, base_vals_d, (long long)n_pairs, (int)n, Q, m->pose_lists_d.ptr, K, m->pose_values_d.ptr,
+                       m->pose_partial_d.ptr, out_dev);
     HIP_TRY(hipGetLastError());
     if (slices > 1) {
         hipLaunchKernelGGL(finish_poses_kernel, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, ctx->stream, m->pose_partial_d.ptr, slices, K, out_dev);
@@ -412,7 +400,7 @@ int evaluate_deltas(ecc_metric* m, int n_poses, const int32_t* off, const int32_
             not_batched->push_back(k);
             continue;
         }
-        if ((int64_t)b_views.size() + c > max_cols || b_pose.size() >= 32768) {  // (the sum's grid is slices x poses: y < 65 536)
+        if ((int64_t)b_views.size() + c > max_cols || b_pose.size() >= POSE_BATCH_MAX_POSES) {
             rc = flush();
             if (rc) return rc;
         }

@@ -159,26 +159,9 @@ __global__ __launch_bounds__(PK_MAIN_THREADS) PK_OCCUPANCY void pairs_kernel(Ecc
     double acc = 0.0;
     double mom2 = 0.0, mom3 = 0.0, mom4 = 0.0;  // CORR: sums of x*x, y*y, x*y (x, y alone are not used by cc())
     pair_accumulate<DERIV, CORR>(p, rec, iD0, iD1, lane, acc, mom2, mom3, mom4);
-    float val;
-    if (!CORR) {
-        for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
-        val = (float)acc;
-    } else {
-        for (int off = 32; off > 0; off >>= 1) {
-            mom2 += __shfl_down(mom2, off);
-            mom3 += __shfl_down(mom3, off);
-            mom4 += __shfl_down(mom4, off);
-        }
-        // host epilogue of the reference: cc = xy / (sqrt(xx) sqrt(yy)), cost = (1 - cc) * weight(= 1)
-        // (ref: ...RadonIntermediate.cpp:127-131,199-210)
-        const float xx = (float)mom2, yy = (float)mom3, xy = (float)mom4;
-        const float corr = (float)((double)xy / (sqrt((double)xx) * sqrt((double)yy)));
-        val = (1.0f - corr) * 1.0f;
-    }
-    if (lane == 0) {
-        if (p.pair_values) p.pair_values[p.value_slots ? (long long)p.value_slots[local] : local] = val;
-        if (p.cost && !p.indices) p.cost[(size_t)ci + (size_t)cj * p.n_views] = val;
-    }
+    wave_sum_pair<CORR>(acc, mom2, mom3, mom4);
+    const float val = pair_value<CORR>(acc, mom2, mom3, mom4);
+    if (lane == 0) store_pair_value(p, local, ci, cj, val);
     // (Fusing the final float64 sum in here -- last-ticket wave reduces -- was measured and dropped: one
     // device-scope atomic per wave on a single counter serialises, 0.51 -> 1.05 ms, and with acquire/release
     // fences per wave 3.15 ms: a cross-XCD release writes the L2 back.  The sum stays a 8-us kernel of its own.)
@@ -187,9 +170,9 @@ __global__ __launch_bounds__(PK_MAIN_THREADS) PK_OCCUPANCY void pairs_kernel(Ecc
 // Launches of at most ECC_PAIRS_SPLIT_MAX pairs (small all-pairs evaluations, shards of them, index lists, the moved view's
 // pairs of the pose-delta mode): one wave per pair leaves most SIMDs idle and the launch lasts as long as one wave's 12 - 23
 // dependent trips.  Here WPP = 4 or 2 waves share a pair: wave `sub` takes the 64-sample trips sub, sub + WPP, ... and
-// stores every sample's term in LDS; the pair's first wave then adds the terms per lane in the order ONE wave accumulates
-// them (k = lane, lane + 64, ... while kappa < kappa_max), so the value has pairs_kernel's bits
-// (tests/test_gpu_small_eval.py: the same pairs through both kernels).  Round 4, config 2 (2016 pairs): 16.9 -> ~7 us.
+// stores every sample's term in LDS; the pair's first wave then adds the terms again in one wave's order (resum_staged), so
+// the value has pairs_kernel's bits (tests/test_gpu_small_eval.py: the same pairs through both kernels).  Round 4, config 2
+// (2016 pairs): 16.9 -> ~7 us.
 // WPP = 8 (one pair per 512-thread workgroup, launches of at most ECC_PAIRS_SPLIT8_MAX pairs): a 512-pair index list
 // 30.2 -> 28.7 us end to end, smaller lists and the pose-delta sweep unchanged (their time is the record kernel and the
 // launches around it).
@@ -214,94 +197,9 @@ __global__ __launch_bounds__(WPP > 4 ? 64 * WPP : PK_THREADS) void pairs_split_k
     }
     __syncthreads();  // every wave of the pair has stored its trips
     if (!live || sub != 0) return;
-    const float dkappa = uniformf(rec->K1[6]), kappa_max = uniformf(rec->K1[7]);
-    for (int k = lane; k < p.k_limit; k += 64) {
-        const float kappa = dkappa * 0.5f + dkappa * k;  // ref: ...RadonIntermediate.cu:259 (same fp32 ops)
-        if (kappa >= kappa_max) break;
-        acc += (double)stage[k];
-    }
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
-    if (lane == 0) {
-        const float val = (float)acc;
-        if (p.pair_values) p.pair_values[p.value_slots ? (long long)p.value_slots[local] : local] = val;
-        if (p.cost && !p.indices) {
-            const int ci = rec->ci, cj = rec->cj;
-            p.cost[(size_t)ci + (size_t)cj * p.n_views] = val;
-        }
-    }
-}
-
-// Deterministic float64 sum of `count` pair values (single workgroup, fixed tree).
-// ref: ...RadonIntermediate.cpp:216-224 (host loop; weights are all 1).
-// values_host (optional, pinned and device-mapped): the kernel also hands the values themselves to the host -- every thread
-// stores what it loads, 16 contiguous bytes per lane, drained before the barrier in front of the result's store; writes of
-// one device to host memory arrive in order, so a host that sees the result sees the values (index lists: no copy command).
-__global__ __launch_bounds__(1024) void sum_pairs_kernel(const float* __restrict__ vals, long long count,
-                                                         double* __restrict__ out, float* __restrict__ values_host)
-{
-    __shared__ double s[1024 / 64];
-    // 16-byte loads, four independent float64 accumulators per thread (fixed order => deterministic)
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-    const long long n4 = count >> 2;
-    const float4* __restrict__ v4 = reinterpret_cast<const float4*>(vals);
-    if (values_host) {  // uniform; its own pass, so that the arithmetic below is the one code path it always was
-        // system-scope stores (plain stores to host memory may sit in the L2 until the kernel ends; the host reads the
-        // values as soon as it sees the result)
-        for (long long q = threadIdx.x; q < count; q += 1024)
-            __hip_atomic_store(reinterpret_cast<unsigned*>(values_host) + q, __float_as_uint(vals[q]), __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_SYSTEM);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    // eight loads in flight per thread: the kernel is one workgroup reading what other XCDs have just written
-    // (HBM latency each time), issued one at a time it took 10 us for 79 800 values
-    long long k = threadIdx.x;
-    // (All of a thread's ~20 loads in flight at once would make it one round trip, but 1024 threads x 20 float4 do not fit
-    // the 128 registers a thread of this workgroup may have: it spilled.  Ten per batch = two round trips.)
-    for (; k + 9 * 1024 < n4; k += 10 * 1024) {
-        float4 v[10];
-#pragma unroll
-        for (int u = 0; u < 10; ++u) v[u] = v4[k + u * 1024];
-#pragma unroll
-        for (int u = 0; u < 10; ++u) {
-            a0 += (double)v[u].x;
-            a1 += (double)v[u].y;
-            a2 += (double)v[u].z;
-            a3 += (double)v[u].w;
-        }
-    }
-    for (; k + 7 * 1024 < n4; k += 8 * 1024) {
-        float4 v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = v4[k + u * 1024];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            a0 += (double)v[u].x;
-            a1 += (double)v[u].y;
-            a2 += (double)v[u].z;
-            a3 += (double)v[u].w;
-        }
-    }
-    for (; k < n4; k += 1024) {
-        const float4 v = v4[k];
-        a0 += (double)v.x;
-        a1 += (double)v.y;
-        a2 += (double)v.z;
-        a3 += (double)v.w;
-    }
-    double acc = (a0 + a1) + (a2 + a3);
-    if (threadIdx.x == 0)
-        for (long long k = n4 << 2; k < count; ++k) acc += (double)vals[k];
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double tot = 0.0;
-        for (int w = 0; w < 1024 / 64; w++) tot += s[w];
-        // `out` is usually pinned host memory that the host polls (ecc_capi.hip: wait_result): one 8-byte store at
-        // system scope, written through, visible to the host before the kernel's end-of-dispatch write-back
-        __hip_atomic_store(reinterpret_cast<unsigned long long*>(out), (unsigned long long)__double_as_longlong(tot),
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    resum_staged<false>(p, uniformf(rec->K1[6]), uniformf(rec->K1[7]), lane, 64, stage, 0, acc, m2, m3, m4);
+    ecc_sum::wave_sum(acc);
+    if (lane == 0) store_pair_value(p, local, rec->ci, rec->cj, (float)acc);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -362,7 +260,7 @@ __global__ __launch_bounds__(256) void pair_samples_kernel(EccPairSamplesParams 
 // the CPU path (include/ecc_hip.h, ecc_metric_set_sampling).
 // -------------------------------------------------------------------------------------------------
 // SPLIT = 4: the four waves of a workgroup share ONE pair (thread T takes k = T, T + 256, ...; the wave sums are added in
-// wave order through LDS) -- a launch of at most a few hundred pairs leaves most of the 1024 SIMDs idle, and the time of
+// wave order through LDS: put_wave_partials / add_wave_partials) -- a launch of at most a few hundred pairs leaves most of the 1024 SIMDs idle, and the time of
 // the evaluation is the time of one pair: 81 -> ~50 us for a single-pair evaluation.  The float64 partial sums are
 // grouped differently from SPLIT = 1, so the mode of a metric is fixed by the size of the FULL range it evaluates
 // (fill_pair_params), not by the launch: pose-delta launches reproduce the full evaluation's bits.
@@ -389,46 +287,15 @@ __global__ __launch_bounds__(PK_THREADS) void pairs_reference_kernel(EccPairPara
     const GlobalFloats d1 = (GlobalFloats)p.slabs[iD1];
     double acc = 0.0, mom2 = 0.0, mom3 = 0.0, mom4 = 0.0;
     reference_loop<CORR>(p, K0, K1, d0, d1, SPLIT == 1 ? lane : (int)threadIdx.x, 64 * SPLIT, acc, mom2, mom3, mom4);
-    if (!CORR) {
-        for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
-    } else {
-        for (int off = 32; off > 0; off >>= 1) {
-            mom2 += __shfl_down(mom2, off);
-            mom3 += __shfl_down(mom3, off);
-            mom4 += __shfl_down(mom4, off);
-        }
-    }
-    if (SPLIT > 1) {  // wave sums -> wave 0, added in wave order
-        if (lane == 0) {
-            part[0][wave] = CORR ? mom2 : acc;
-            part[1][wave] = mom3;
-            part[2][wave] = mom4;
-        }
+    wave_sum_pair<CORR>(acc, mom2, mom3, mom4);
+    if (SPLIT > 1) {  // wave sums -> wave 0
+        if (lane == 0) put_wave_partials<CORR>(part, wave, acc, mom2, mom3, mom4);
         __syncthreads();
         if (wave != 0) return;
-        acc = mom2 = part[0][0];
-        mom3 = part[1][0];
-        mom4 = part[2][0];
-#pragma unroll
-        for (int w = 1; w < PK_THREADS / 64; ++w) {
-            acc += part[0][w];
-            mom2 += part[0][w];
-            mom3 += part[1][w];
-            mom4 += part[2][w];
-        }
+        add_wave_partials<CORR>(part, acc, mom2, mom3, mom4);
     }
-    float val;
-    if (!CORR) {
-        val = (float)acc;
-    } else {
-        const float xx = (float)mom2, yy = (float)mom3, xy = (float)mom4;
-        const float corr = (float)((double)xy / (sqrt((double)xx) * sqrt((double)yy)));
-        val = (1.0f - corr) * 1.0f;
-    }
-    if (lane == 0) {
-        if (p.pair_values) p.pair_values[p.value_slots ? (long long)p.value_slots[local] : local] = val;
-        if (p.cost && !p.indices) p.cost[(size_t)ci + (size_t)cj * p.n_views] = val;
-    }
+    const float val = pair_value<CORR>(acc, mom2, mom3, mom4);
+    if (lane == 0) store_pair_value(p, local, ci, cj, val);
 }
 
 // The wide form of pairs_reference_kernel<CORR, 4> for launches that leave most of the chip idle (at most
@@ -459,46 +326,15 @@ __global__ __launch_bounds__(ECC_REFERENCE_WIDE_THREADS) void pairs_reference_wi
                                ECC_REFERENCE_WIDE_THREADS, acc, mom2, mom3, mom4, ref_stage, stage_stride);
     __syncthreads();
     if (wave < 4) {  // wave-uniform
-        reference_resum<CORR>(p, K1[6], K1[7], (int)threadIdx.x, ref_stage, stage_stride, acc, mom2, mom3, mom4);
-        if (!CORR) {
-            for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
-        } else {
-            for (int off = 32; off > 0; off >>= 1) {
-                mom2 += __shfl_down(mom2, off);
-                mom3 += __shfl_down(mom3, off);
-                mom4 += __shfl_down(mom4, off);
-            }
-        }
-        if (lane == 0) {
-            part[0][wave] = CORR ? mom2 : acc;
-            part[1][wave] = mom3;
-            part[2][wave] = mom4;
-        }
+        resum_staged<CORR>(p, K1[6], K1[7], (int)threadIdx.x, 256, ref_stage, stage_stride, acc, mom2, mom3, mom4);
+        wave_sum_pair<CORR>(acc, mom2, mom3, mom4);
+        if (lane == 0) put_wave_partials<CORR>(part, wave, acc, mom2, mom3, mom4);
     }
     __syncthreads();
     if (wave != 0) return;
-    acc = mom2 = part[0][0];
-    mom3 = part[1][0];
-    mom4 = part[2][0];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) {
-        acc += part[0][w];
-        mom2 += part[0][w];
-        mom3 += part[1][w];
-        mom4 += part[2][w];
-    }
-    float val;
-    if (!CORR) {
-        val = (float)acc;
-    } else {
-        const float xx = (float)mom2, yy = (float)mom3, xy = (float)mom4;
-        const float corr = (float)((double)xy / (sqrt((double)xx) * sqrt((double)yy)));
-        val = (1.0f - corr) * 1.0f;
-    }
-    if (lane == 0) {
-        if (p.pair_values) p.pair_values[p.value_slots ? (long long)p.value_slots[local] : local] = val;
-        if (p.cost && !p.indices) p.cost[(size_t)ci + (size_t)cj * p.n_views] = val;
-    }
+    add_wave_partials<CORR>(part, acc, mom2, mom3, mom4);
+    const float val = pair_value<CORR>(acc, mom2, mom3, mom4);
+    if (lane == 0) store_pair_value(p, local, ci, cj, val);
 }
 
 }  // namespace
@@ -665,116 +501,5 @@ extern "C" hipError_t ecc_launch_pairs(const EccPairParams* p, hipStream_t strea
         else
             hipLaunchKernelGGL((pairs_kernel<false, false>), grid, block, 0, stream, *p);
     }
-    return hipGetLastError();
-}
-
-namespace {
-// The same sum over SUM_BLOCKS workgroups inside ONE launch (large counts): every workgroup reduces a contiguous slice in a
-// fixed order -- one memory round trip instead of the single workgroup's two -- and publishes its float64 partial; the
-// workgroup that arrives last (a ticket counter) adds the partials in slice order and stores the result.  Deterministic:
-// the same slices, the same order within a slice, the same order of the partials, whichever workgroup happens to be last.
-// Hand-off between workgroups as the CDNA4 guide prescribes for it (MI355X_MICROARCH.md, "Valid forms"): the partial is an
-// agent-scope (sc1, write-through) store, the storing lane drains it (s_waitcnt vmcnt(0)) before its agent-scope ticket
-// add, the last arriver -- told by the value its add returned -- reads the partials with agent-scope (sc1) loads.
-// That hand-off is what gfx950's code generation of these operations guarantees, not what the C++ memory model does for
-// relaxed atomics: the kernel is tied to the target it was written and measured for.
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
-#error "sum_pairs_split_kernel's cross-workgroup hand-off is specified for gfx950 only"
-#endif
-constexpr int SUM_BLOCKS = 16;
-struct SumScratch {
-    double partial[SUM_BLOCKS];
-    unsigned ticket;  // zero between launches (reset by the last arriver)
-};
-
-__global__ __launch_bounds__(1024) void sum_pairs_split_kernel(const float* __restrict__ vals, long long count,
-                                                               double* __restrict__ out, SumScratch* __restrict__ scratch)
-{
-    __shared__ double s[1024 / 64];
-    __shared__ unsigned s_ticket;
-    const long long n4 = count >> 2;
-    const long long per = (n4 + SUM_BLOCKS - 1) / SUM_BLOCKS;  // float4 per slice
-    const long long lo = (long long)blockIdx.x * per, hi = min(n4, lo + per);
-    const float4* __restrict__ v4 = reinterpret_cast<const float4*>(vals);
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-    long long k = lo + threadIdx.x;
-    for (; k + 3 * 1024 < hi; k += 4 * 1024) {
-        float4 v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) v[u] = v4[k + u * 1024];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            a0 += (double)v[u].x;
-            a1 += (double)v[u].y;
-            a2 += (double)v[u].z;
-            a3 += (double)v[u].w;
-        }
-    }
-    for (; k < hi; k += 1024) {
-        const float4 v = v4[k];
-        a0 += (double)v.x;
-        a1 += (double)v.y;
-        a2 += (double)v.z;
-        a3 += (double)v.w;
-    }
-    double acc = (a0 + a1) + (a2 + a3);
-    if (blockIdx.x == SUM_BLOCKS - 1 && threadIdx.x == 0)
-        for (long long q = n4 << 2; q < count; ++q) acc += (double)vals[q];  // the up to three values past the last float4
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double part = 0.0;
-        for (int w = 0; w < 1024 / 64; w++) part += s[w];
-        __hip_atomic_store(reinterpret_cast<unsigned long long*>(&scratch->partial[blockIdx.x]),
-                           (unsigned long long)__double_as_longlong(part), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        s_ticket = __hip_atomic_fetch_add(&scratch->ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (s_ticket == SUM_BLOCKS - 1) {  // every other workgroup's partial was drained before its add: all are visible
-            double tot = 0.0;
-            for (int b = 0; b < SUM_BLOCKS; ++b)
-                tot += __longlong_as_double((long long)__hip_atomic_load(
-                    reinterpret_cast<unsigned long long*>(&scratch->partial[b]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-            __hip_atomic_store(&scratch->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(reinterpret_cast<unsigned long long*>(out), (unsigned long long)__double_as_longlong(tot),
-                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
-}
-}  // namespace
-
-namespace {
-// One double from device memory into a pinned, device-mapped host slot (system-scope store): how a value that a
-// collective left on the device (the all-reduced sum of a sharded evaluation) reaches a polling host without a copy command.
-__global__ void publish_scalar_kernel(const double* __restrict__ value, double* __restrict__ host_slot)
-{
-    const unsigned long long bits = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(value), __ATOMIC_RELAXED,
-                                                      __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(reinterpret_cast<unsigned long long*>(host_slot), bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-}  // namespace
-
-extern "C" hipError_t ecc_launch_publish_scalar(const double* value_d, double* host_slot_dev, hipStream_t stream)
-{
-    hipLaunchKernelGGL(publish_scalar_kernel, dim3(1), dim3(1), 0, stream, value_d, host_slot_dev);
-    return hipGetLastError();
-}
-
-extern "C" size_t ecc_sum_scratch_bytes() { return sizeof(SumScratch); }
-
-// scratch: ecc_sum_scratch_bytes() of zeroed device memory owned by the caller (one per stream of launches), or null.
-extern "C" hipError_t ecc_launch_sum_pairs_to_host(const float* vals, long long count, double* out, float* values_host, hipStream_t stream)
-{
-    hipLaunchKernelGGL(sum_pairs_kernel, dim3(1), dim3(1024), 0, stream, vals, count, out, values_host);
-    return hipGetLastError();
-}
-
-extern "C" hipError_t ecc_launch_sum_pairs(const float* vals, long long count, double* out, void* scratch, hipStream_t stream)
-{
-    if (scratch && count >= 32768)
-        hipLaunchKernelGGL(sum_pairs_split_kernel, dim3(SUM_BLOCKS), dim3(1024), 0, stream, vals, count, out,
-                           static_cast<SumScratch*>(scratch));
-    else
-        hipLaunchKernelGGL(sum_pairs_kernel, dim3(1), dim3(1024), 0, stream, vals, count, out, (float*)nullptr);
     return hipGetLastError();
 }

@@ -16,17 +16,13 @@
 //   * phase A: the pair records of the workgroup's pairs by k01_fit_block<8> -- the code of k01_kernel<8>, 8 lanes per fit
 //     -- into LDS;
 //   * phase B: the sampling loops of pairs_kernel (pair_accumulate) or of pairs_reference_kernel<.., 4> (reference_loop).
-//     With few pairs most SIMDs would idle, so the four waves of a workgroup share ONE pair (WPP = 4): wave
-//     `sub` takes the 64-sample trips sub, sub + WPP, ... and stores every sample's term in LDS; the pair's first wave
-//     then adds the terms per lane in the order ONE wave accumulates them (k = lane, lane + 64, ...), so the pair value has
-//     the bits of pairs_kernel's.  The reference arithmetic keeps its own grouping (thread T: k = T, T + 256, ...; wave
-//     sums in wave order), which is what pairs_reference_kernel<.., 4> does for the same evaluation sizes -- from 1024
-//     threads per pair (pairs_reference_wide_kernel's scheme: terms staged in LDS, added by the first 256 threads in that
-//     order; the records are made by the first four waves);
+//     With few pairs most SIMDs would idle, so the four waves of a workgroup share ONE pair (WPP = 4) the way
+//     pairs_split_kernel's do: staged terms, added again in one wave's order (resum_staged, ecc_pairs_device.h), so the pair
+//     value has the bits of pairs_kernel's.  The reference arithmetic keeps the grouping of pairs_reference_kernel<.., 4>
+//     -- from 1024 threads per pair (pairs_reference_wide_kernel's scheme; the records are made by the first four waves);
 //   * phase C: each value goes to the device array (plain store) and, at system scope, into pinned host memory; the
 //     workgroup drains its stores and takes a ticket, and the workgroup that arrives last writes a "done" word the host
-//     polls.  The HOST then adds the values in sum_pairs_kernel's order (the float4 layout of its 1024 threads, its shuffle
-//     tree, its 16 wave sums in order: ecc_evaluate.hip, small_sum_on_host) -- at most 4096 values, under 2 us.  (First form,
+//     polls.  The HOST then adds the values in the order of the sum kernels (ecc_sum_order.h, sum_on_host) -- under 2 us.  (First form,
 //     measured: the last arriver added the values itself with agent-scope loads -- 55 us for 399 values; loads that must
 //     bypass the XCD's L2 cost microseconds each.  Asynchronous callers, who want the sum in device memory, keep the
 //     stream-ordered launches.)
@@ -65,7 +61,7 @@ __global__ __launch_bounds__(REF ? 1024 : 256, ECC_SMALL_MIN_WAVES) void small_e
     const bool member = !REF || threadIdx.x < 256;  // wave-uniform: the threads that make the records
     __shared__ K01Shared<ECC_K01_SMALL_LANES> ks;
     __shared__ int32_t idx_lds[4 * PPW];
-    __shared__ double part[4];
+    __shared__ double part[1][4];
 
 #ifdef ECC_SMALL_STAMPS  // experiments (scripts/exp_small_phases.py); the stamps cost registers: not in the product build
 #define ECC_SMALL_STAMP(i) do { if (x.dbg && threadIdx.x == 0) x.dbg[4 * blockIdx.x + (i)] = wall_clock64(); } while (0)
@@ -111,14 +107,12 @@ __global__ __launch_bounds__(REF ? 1024 : 256, ECC_SMALL_MIN_WAVES) void small_e
         }
         __syncthreads();  // every sample's term is staged
         if (wave < 4) {   // the sums of a 256-thread workgroup
-            if (live) reference_resum<false>(p, uniformf(rec->K1[6]), uniformf(rec->K1[7]), (int)threadIdx.x, stage_all, x.stage_stride, acc, m2, m3, m4);
-            for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
-            if (lane == 0) part[wave] = acc;
+            if (live) resum_staged<false>(p, uniformf(rec->K1[6]), uniformf(rec->K1[7]), (int)threadIdx.x, 256, stage_all, x.stage_stride, acc, m2, m3, m4);
+            ecc_sum::wave_sum(acc);
+            if (lane == 0) put_wave_partials<false>(part, wave, acc, m2, m3, m4);
         }
         __syncthreads();
-        acc = part[0];
-#pragma unroll
-        for (int w = 1; w < 4; ++w) acc += part[w];  // wave sums in wave order, as pairs_reference_kernel<.., 4>
+        add_wave_partials<false>(part, acc, m2, m3, m4);  // as pairs_reference_kernel<.., 4>
         val = (float)acc;
     } else {
         double acc = 0.0, m2 = 0.0, m3 = 0.0, m4 = 0.0;
@@ -131,23 +125,16 @@ __global__ __launch_bounds__(REF ? 1024 : 256, ECC_SMALL_MIN_WAVES) void small_e
         }
         if (WPP > 1) {
             __syncthreads();  // every wave of the pair has stored its trips
-            if (live && sub == 0) {
-                // the terms in the order one wave accumulates them: lane l adds k = l, l + 64, ... until kappa reaches kappa_max
-                const float dkappa = uniformf(rec->K1[6]), kappa_max = uniformf(rec->K1[7]);
-                for (int k = lane; k < p.k_limit; k += 64) {
-                    const float kappa = dkappa * 0.5f + dkappa * k;  // ref: ...RadonIntermediate.cu:259 (same fp32 ops)
-                    if (kappa >= kappa_max) break;
-                    acc += (double)stage[k];
-                }
-            }
+            if (live && sub == 0) resum_staged<false>(p, uniformf(rec->K1[6]), uniformf(rec->K1[7]), lane, 64, stage, 0, acc, m2, m3, m4);
         }
-        for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
+        ecc_sum::wave_sum(acc);
         val = (float)acc;
     }
 
     // ---- phase C: the pair values; the workgroup that arrives last announces them ----
     if (live && sub == 0 && lane == 0) {
-        if (p.pair_values) p.pair_values[local] = val;  // the device copy (later list launches, copies to the caller): visible at kernel end
+        // the device copy (later list launches, copies to the caller): visible at kernel end; store_pair_value without slots, see there
+        if (p.pair_values) p.pair_values[local] = val;
         if (p.cost && !p.indices) {
             const int ci = rec->ci, cj = rec->cj;
             p.cost[(size_t)ci + (size_t)cj * p.n_views] = val;

@@ -269,7 +269,7 @@ int ecc_metric_set_sampling(ecc_metric* m, int mode);
  * the pairs that contain a changed view (when at most a quarter of the views changed, otherwise everything), then sums
  * the whole array again.  The result is BIT-IDENTICAL to a full evaluation: a pair's value is a function of its two
  * matrices, its two Radon intermediates and the parameters only, the sampling mode is the one the full range resolves
- * to, and the float64 sum has a fixed order.  Changing parameters, sampling mode, the range, the number of views or
+ * to, and the float64 sum has a fixed order (csrc/ecc_sum_order.h).  Changing parameters, sampling mode, the range, the number of views or
  * calling ecc_metric_refresh_dtrs drops the kept values.  ecc_metric_last_evaluated_pairs reports how many pairs the
  * last evaluate_all / evaluate_range recomputed. */
 int ecc_metric_set_incremental(ecc_metric* m, int enable);
@@ -309,7 +309,7 @@ int ecc_metric_set_record_reuse(ecc_metric* m, int on);
  * tools/FluoroTracking/FluoroTracking.cpp:179-211): E1 of the views whose matrix changed is computed on the host (the same
  * code, bit-identical) and travels in the kernel arguments, each workgroup fits its pair's record and samples it with four
  * waves, every value goes to the device array and -- at system scope -- to pinned host memory, the workgroup that arrives
- * last writes the word the host polls, and the host adds the values in the sum kernel's order.  Larger evaluations keep the
+ * last writes the word the host polls, and the host adds the values in the sum kernel's order (csrc/ecc_sum_order.h).  Larger evaluations keep the
  * stream-ordered launches, up to 4096 pairs with several waves per pair (pairs_split_kernel), index lists without copy
  * commands (the list is read from pinned memory, the sum kernel hands the values back), and launches of at most 4096 pairs
  * also take E1 of up to 16 changed views in the arguments of their record kernel (k01_patched_kernel) instead of an e1_kernel
@@ -338,7 +338,7 @@ int ecc_metric_evaluate_all(ecc_metric* m, float* cost_nxn, double* mean);
  * matrices moved_Ps[12 * q ..] of the same entries q.  All poses of the call are ONE launch that lists the pairs and does E1
  * of the moved matrices, ONE record launch and ONE pair launch over the (pose, moved view) x partner grid -- n_views - 1 pairs
  * per moved view instead of n (n - 1) / 2 per pose -- and ONE segmented float64 sum that walks, per pose, the base's pair values with the pose's own
- * substituted in exactly the order the all-pairs sum adds them: every mean has the bits of ecc_metric_set_projections +
+ * substituted in exactly the order the all-pairs sum adds them (csrc/ecc_sum_order.h): every mean has the bits of ecc_metric_set_projections +
  * ecc_metric_evaluate_all on that pose's matrices (tests/test_gpu_pose_batch.py).  The base's pair values are kept between
  * calls (only the pairs of views that changed since are redone).  The metric's current matrices are unchanged by the call.
  * A pose with more than 32 moved views, or one that moves view 0 under the automatic object radius and changes it, is

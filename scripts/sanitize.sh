@@ -5,6 +5,7 @@
 #   3. the group's worker hand-off (csrc/ecc_worker_pool.h) under ThreadSanitizer: 8 ranks, 20 000 jobs, sleeps, failures
 #   3b. the pose batch's host-side comparison (csrc/ecc_pose_diff.h) under ThreadSanitizer: 1 and 8 threads, the same result
 #   3c. the change scan and pair lists of the evaluation paths (csrc/ecc_view_changes.h) under AddressSanitizer + UBSan
+#   3d. the host statement of the pair total's order (csrc/ecc_sum_order.h) under AddressSanitizer + UBSan
 #   4. host code of libecc_hip.so under UndefinedBehaviorSanitizer: the no-GPU ABI / host-function tests
 # usage: scripts/sanitize.sh [logfile]     (default profiles/r03_sanitize.log)
 set -u
@@ -38,6 +39,10 @@ g++ -std=c++17 -O1 -g -fsanitize=thread -fno-omit-frame-pointer tests/c/tsan_pos
 echo; echo "== 3c. ecc_view_changes.h: -fsanitize=address,undefined (tests/c/view_changes.cpp)"
 g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer tests/c/view_changes.cpp \
   -o $TMP/view_changes && ASAN_OPTIONS=abort_on_error=1 $TMP/view_changes || fail=1
+
+echo; echo "== 3d. ecc_sum_order.h: -fsanitize=address,undefined (tests/c/sum_order.cpp)"
+g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer tests/c/sum_order.cpp \
+  -o $TMP/sum_order && ASAN_OPTIONS=abort_on_error=1 $TMP/sum_order || fail=1
 
 echo; echo "== 4. libecc_hip.so host code: -Xarch_host -fsanitize=undefined (ECC_HIP_LIB), no-GPU ABI and host-function tests"
 python - <<PY || fail=1

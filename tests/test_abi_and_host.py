@@ -161,3 +161,17 @@ def test_view_changes_lists_the_pairs_of_the_changed_views(tmp_path):
                     f.write("%d %d %d\n" % (n, first, count))
     r = subprocess.run([exe, ranges], capture_output=True, text=True)
     assert r.returncode == 0 and "ok" in r.stdout and "132 extra ranges" in r.stdout, r.stdout + r.stderr
+
+
+def test_sum_order_header_states_the_order_of_the_sum_kernels(tmp_path):
+    """csrc/ecc_sum_order.h (host part): sum_on_host has the bits of the host sum the one-launch evaluation used before (a
+    verbatim copy in the driver) for every count 0 .. 4096, and, for one slice and sixteen and counts around every boundary
+    of the order (multiples of 4, 4096, 4 x 16, 32 767 / 32 768 / 79 800), those of a naive lane-by-lane emulation of a sum
+    workgroup; the slice bounds partition [0, n4); slices() switches at 32 768.  The same driver runs under ASan + UBSan in
+    scripts/sanitize.sh."""
+    import subprocess
+    exe = os.path.join(str(tmp_path), "sum_order")
+    subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", os.path.join(ROOT, "tests", "c", "sum_order.cpp"), "-o", exe],
+                   check=True)
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0 and "ok: 4097 counts" in r.stdout, r.stdout + r.stderr

@@ -59,5 +59,5 @@ def test_side_stream_kernels_fit_beside_the_pair_kernel():
 def test_every_kernel_of_the_library_is_listed():
     mod, ks = _resources()
     for part in ("radon_kernel", "k01_kernel", "pairs_kernel", "small_eval_kernel", "sum_pairs_kernel", "e1_kernel", "direct_lines_kernel",
-                 "preprocess_kernel", "ramp_kernel", "publish_scalar_kernel"):
+                 "preprocess_kernel", "ramp_kernel", "publish_scalar_kernel", "sum_poses_kernel", "pose_list_kernel"):
         assert mod.find(ks, part), part
