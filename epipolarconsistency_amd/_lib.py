@@ -79,6 +79,9 @@ SIGNATURES = {
     "ecc_metric_evaluate_pose_deltas": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "ecc_metric_set_pose_batching": (_i, [_vp, _i]),
     "ecc_metric_last_batched_poses": (_i, [_vp, C.POINTER(_i64)]),
+    "ecc_metric_evaluate_transforms": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
+    "ecc_metric_last_batched_transforms": (_i, [_vp, C.POINTER(_i64)]),
+    "ecc_host_compose_transform": (None, [_vp, _vp, _vp]),
     "ecc_metric_evaluate_range": (_i, [_vp, _i64, _i64, _vp, _pd]),
     "ecc_metric_evaluate_range_async": (_i, [_vp, _i64, _i64, _vp, _vp]),
     "ecc_metric_evaluate_pairs": (_i, [_vp, _vp, _i, _vp, _pd]),

@@ -640,6 +640,35 @@ class MetricRadonIntermediate:
         check(_lib.lib().ecc_metric_last_batched_poses(self._h, C.byref(v)))
         return v.value
 
+    def evaluate_transforms(self, n_source, Ts, want_pairs=False):
+        """ecc_metric_evaluate_transforms: the registration of two scans (ref: tools/Registration/Registration3D3D.hxx).  The
+        current matrices are the base, views [0, n_source) the source scan, the rest the target scan; Ts: anything np.asarray
+        turns into (K, 4, 4) float64 in the mathematical (row, column) sense.  Transform k evaluates the source matrices
+        geometry.compose_transform(P_i, Ts[k]) against the unchanged target matrices over the n_source x n_target cross pairs.
+        Returns the K means (float64), with want_pairs also the pair values as (K, n_target, n_source) float32: every number
+        bit-identical to setProjectionMatrices(composed) + evaluate(index list) per transform; the current matrices stay.
+        Fix the object radius (setObjectRadius) for a sweep whose values are compared with each other."""
+        T = np.asarray(Ts, dtype=np.float64)
+        if T.ndim == 2 and T.shape == (4, 4):
+            T = T[None]
+        if T.ndim != 3 or T.shape[1:] != (4, 4):
+            raise ValueError("Ts must be (K, 4, 4)")
+        flat = np.ascontiguousarray(T.transpose(0, 2, 1)).reshape(-1, 16)  # column-major per transform
+        n_source = int(n_source)
+        K, n = len(flat), self.getNumberOfProjetions()
+        means = np.zeros(K, np.float64)
+        pairs = np.zeros((K, max(n - n_source, 0), max(n_source, 0)), np.float32) if want_pairs else None
+        check(_lib.lib().ecc_metric_evaluate_transforms(self._h, n_source, K, C.c_void_p(flat.ctypes.data if K else 0),
+                                                        C.c_void_p(means.ctypes.data if K else 0),
+                                                        C.c_void_p(pairs.ctypes.data) if (want_pairs and pairs.size) else None))
+        return (means, pairs) if want_pairs else means
+
+    def last_batched_transforms(self):
+        """Transforms of the last evaluate_transforms call that went through the batch (0: the sequential way)."""
+        v = C.c_int64(0)
+        check(_lib.lib().ecc_metric_last_batched_transforms(self._h, C.byref(v)))
+        return v.value
+
     def evaluateForImagePair(self, i, j):
         """ref: evaluateForImagePair(i, j, redundant_samples0, redundant_samples1, kappas, radon_samples0,
         radon_samples1) (...RadonIntermediate.cpp:324-393, visualisation).  Returns (ecc, dict) with the

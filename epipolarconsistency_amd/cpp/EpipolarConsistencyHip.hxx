@@ -28,8 +28,8 @@
 //
 // Error behaviour: the reference prints and exit()s on any CUDA error (LibUtilsCuda/UtilsCuda.hxx:14-28);
 // the adapter throws std::runtime_error with ecc_last_error() instead.
-// Not carried over: BindlessTexture2D (there are no textures; getTexture() returns null),
-// setProjectionImages (a stub in the reference, ...RadonIntermediate.cpp:121-125).
+// Not carried over: BindlessTexture2D (there are no textures; getTexture() returns null; the type is only
+// declared, for Metric::setProjectionImages -- a stub here as in the reference, ...RadonIntermediate.cpp:121-125).
 #ifndef ECC_EPIPOLAR_CONSISTENCY_HIP_HXX
 #define ECC_EPIPOLAR_CONSISTENCY_HIP_HXX
 
@@ -58,9 +58,15 @@
 #endif
 #endif
 
+namespace UtilsCuda {
+template <typename T>
+class BindlessTexture2D;  // ref: LibUtilsCuda/UtilsCuda.hxx; never defined here (no textures): Metric::setProjectionImages names it
+}  // namespace UtilsCuda
+
 namespace Geometry {
 #ifdef ECC_ADAPTER_HAVE_EIGEN
 typedef Eigen::Matrix<double, 3, 4> ProjectionMatrix;  // ref: LibProjectiveGeometry/ProjectiveGeometry.hxx:22
+typedef Eigen::Matrix<double, 4, 4> RP3Homography;     // ref: LibProjectiveGeometry/ProjectiveGeometry.hxx (Eigen::Matrix4d)
 #else
 /// 3x4, column-major like Eigen's default: element (r, c) at data()[r + 3*c].
 struct ProjectionMatrix {
@@ -68,6 +74,15 @@ struct ProjectionMatrix {
     ProjectionMatrix() { for (double& x : v) x = 0; }
     double& operator()(int r, int c) { return v[r + 3 * c]; }
     double operator()(int r, int c) const { return v[r + 3 * c]; }
+    const double* data() const { return v; }
+    double* data() { return v; }
+};
+/// 4x4, column-major like Eigen's default: element (r, c) at data()[r + 4*c]; the identity by default.
+struct RP3Homography {
+    double v[16];
+    RP3Homography() { for (int i = 0; i < 16; ++i) v[i] = (i % 5 == 0) ? 1.0 : 0.0; }
+    double& operator()(int r, int c) { return v[r + 4 * c]; }
+    double operator()(int r, int c) const { return v[r + 4 * c]; }
     const double* data() const { return v; }
     double* data() { return v; }
 };
@@ -558,8 +573,14 @@ public:
     virtual Metric& setEpipolarPlaneStep(double dkappa_rad = 0) { dkappa = dkappa_rad; return *this; }
     virtual Metric& setProjectionMatrices(const std::vector<ProjectionMatrix>& _Ps) { Ps = _Ps; return *this; }
     const std::vector<ProjectionMatrix>& getProjectionMatrices() const { return Ps; }
+    /// ref: EpipolarConsistency.h:76 (pure there; every implementation in the reference tree that takes Radon intermediates
+    /// is an empty stub, ...RadonIntermediate.cpp:121-125).  There are no textures here: does nothing.
+    virtual Metric& setProjectionImages(const std::vector<UtilsCuda::BindlessTexture2D<float>*>&) { return *this; }
     virtual int getNumberOfProjetions() = 0;
     virtual double evaluate(float* cost_image = 0x0) = 0;
+    /// ref: EpipolarConsistency.h:85-87: just the two images i and j, optionally the redundant values.
+    virtual double evaluateForImagePair(int i, int j, std::vector<float>* redundant_samples0 = 0x0,
+                                        std::vector<float>* redundant_samples1 = 0x0, std::vector<float>* kappas = 0x0) = 0;
 };
 
 /// ref: class MetricRadonIntermediate : public Metric
@@ -715,6 +736,32 @@ public:
         detail::check(ecc_metric_evaluate_pose_deltas(m_h, (int)moved_views.size(), off.data(), views.empty() ? nullptr : views.data(),
                                                       flat.empty() ? nullptr : flat.data(), means.data()));
         return means;
+    }
+
+    /// Not in the reference: ecc_metric_evaluate_transforms -- the registration of two scans (ref:
+    /// tools/Registration/Registration3D3D.hxx:56-62, :91-110: the source scan's views first, the target scan's behind them, every
+    /// source matrix times one 4x4 transform per cost call, the index list of all source x target pairs) for a whole population
+    /// of transforms in one call.  means[k]: the mean over the n_source x n_target cross pairs under Ts[k] applied to the CURRENT
+    /// source matrices (views [0, n_source)); pair_values (nullable): Ts.size() x n_target x n_source floats, source index fast.
+    /// Every number is bit-identical to Ps[i] * Ts[k] by ecc_host_compose_transform, setProjectionMatrices and
+    /// evaluate(indices, out) per transform; the current matrices stay.  A caller that compares the values of a sweep fixes the
+    /// object radius (setObjectRadius): the automatic one follows the composed first view.  Single device only.
+    void evaluateTransforms(int n_source, const std::vector<Geometry::RP3Homography>& Ts, std::vector<double>& means,
+                            float* pair_values = 0x0)
+    {
+        if (m_gh) throw std::runtime_error("evaluateTransforms: not available on a device group");
+        means.assign(Ts.size(), 0.0);
+        std::vector<double> flat(16 * Ts.size());
+        for (size_t k = 0; k < Ts.size(); ++k)
+            for (int q = 0; q < 16; ++q) flat[16 * k + q] = Ts[k].data()[q];
+        detail::check(ecc_metric_evaluate_transforms(m_h, n_source, (int)Ts.size(), flat.data(), means.data(), pair_values));
+    }
+    /// How many transforms of the last evaluateTransforms went through the batch (0: the sequential way).
+    long long lastBatchedTransforms() const
+    {
+        int64_t v = 0;
+        if (m_h && !m_gh) detail::check(ecc_metric_last_batched_transforms(m_h, &v));
+        return (long long)v;
     }
 
     /// The metric borrows the dtrs: "DO NOT delete or change _dtrs during lifetime" (ref: .h:45).

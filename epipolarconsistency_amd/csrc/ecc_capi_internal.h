@@ -39,6 +39,7 @@ extern "C" hipError_t ecc_launch_build_paired(const float* const* slabs_tbl_d, f
 extern "C" hipError_t ecc_launch_build_quad(const float* const* slabs_tbl_d, float* quads_d, int64_t quad_stride_floats, int n,
                                             int rows, int pitch, hipStream_t stream);
 extern "C" hipError_t ecc_launch_k01(const EccPairParams* p, hipStream_t stream);
+extern "C" hipError_t ecc_launch_k01_radii(const EccPairParams* p, const float* radii_d, int period, hipStream_t stream);
 extern "C" hipError_t ecc_launch_k01_patched(const EccPairParams* p, const EccSmallEval* x, hipStream_t stream);
 extern "C" hipError_t ecc_launch_pairs(const EccPairParams* p, hipStream_t stream);
 extern "C" int ecc_small_eval_plan(const EccPairParams* p, long long forced_bound, int* wpp, size_t* lds_bytes);
@@ -55,6 +56,11 @@ extern "C" hipError_t ecc_launch_sum_pairs_to_host(const float* vals, long long 
 extern "C" hipError_t ecc_launch_publish_scalar(const double* value_d, double* host_slot_dev, hipStream_t stream);
 extern "C" size_t ecc_sum_scratch_bytes();
 extern "C" hipError_t ecc_launch_e1(const double* Ps_d, int n, float* PinvTs_d, float* Cs_d, hipStream_t stream);
+
+#ifndef ECC_POSE_BATCH_MAX_ENTRIES
+// grid entries (records of 296 bytes) per batch of ecc_poses.hip / ecc_transforms.hip: longer lists go in several batches
+#define ECC_POSE_BATCH_MAX_ENTRIES (1 << 20)
+#endif
 
 #define ECC_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -371,6 +377,10 @@ struct ecc_metric {
     DeviceArray<double> pose_partial_d;
     DeviceArray<int32_t> pose_lists_d;
     int64_t last_batched_poses = 0;    // poses the last ecc_metric_evaluate_poses* call took through the batch (ecc_metric_last_batched_poses)
+    // ecc_metric_evaluate_transforms (ecc_transforms.hip) uses the scratch above (pose_lists_d: its value slots) and, under the
+    // automatic object radius, one float per transform of a batch
+    DeviceArray<float> transform_radii_d;
+    int64_t last_batched_transforms = 0;  // ecc_metric_last_batched_transforms
     // ecc_debug_step_stamps: host clock (seconds, steady) at fixed points of the last set_projections / synchronous evaluation
     double stamps[ECC_STEP_STAMPS] = {0};
 };

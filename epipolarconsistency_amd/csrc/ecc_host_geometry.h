@@ -142,6 +142,25 @@ ECC_HD inline void source_position(const double* P, float* out4)
     for (int i = 0; i < 4; ++i) out4[i] = (float)(Q[i + 12] / Q[15]);
 }
 
+// P (3x4) times T (4x4), both column-major: out(r, c) = ((P(r,0) T(0,c) + P(r,1) T(1,c)) + P(r,2) T(2,c)) + P(r,3) T(3,c),
+// every product and every sum rounded to binary64 on its own (include/ecc_hip.h, ecc_host_compose_transform).  The library is
+// built with -ffp-contract=off; the pragma says the same to a translation unit built with hipcc's default (fast-honor-pragmas) or
+// with `on` (only an explicit -ffp-contract=fast ignores it): 48 v_mul_f64 + 36 v_add_f64 and no v_fma_f64 on gfx950
+// (tests/test_transforms_host.py compiles it and counts).  out may not alias P.
+ECC_HD inline void compose_transform(const double* P, const double* T, double* out)
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    for (int c = 0; c < 4; ++c)
+        for (int r = 0; r < 3; ++r) {
+            const double p0 = P[r] * T[4 * c], p1 = P[r + 3] * T[4 * c + 1], p2 = P[r + 6] * T[4 * c + 2], p3 = P[r + 9] * T[4 * c + 3];
+            const double s01 = p0 + p1;
+            const double s012 = s01 + p2;
+            out[r + 3 * c] = s012 + p3;
+        }
+}
+
 ECC_HD inline void cross3(const double* a, const double* b, double* c)
 {
     c[0] = a[1] * b[2] - a[2] * b[1];

@@ -936,10 +936,14 @@ __device__ __forceinline__ constexpr double cheb_weight(int n, int k)
     return k == 0 && n > 0 ? 0.5 * w : w;
 }
 
+// radii (k01_radii_kernel, the transform batch of ecc_transforms.hip): entry e of the launch takes radii[e % radii_period]
+// for its object radius instead of the launch's one p.object_radius_mm -- the float the host would have passed for that
+// entry's transform.  Null in every other caller: a compile-time constant there, the scalar path's code is what it was.
 typedef const EccSmallEval __attribute__((address_space(4))) * EccSmallEvalArg;
 template <int LANES>
 __device__ __forceinline__ void k01_fit_block(const EccPairParams& p, long long blk_first, int live_slots, K01Shared<LANES>& sh,
-                                              EccSmallEvalArg small = nullptr, const int32_t* idx_lds = nullptr, const bool member = true)
+                                              EccSmallEvalArg small = nullptr, const int32_t* idx_lds = nullptr, const bool member = true,
+                                              const float* radii = nullptr, int radii_period = 1)
 {
     constexpr int N = ECC_POLY_DEG + 1;
     const int role = (threadIdx.x >> 6) & 3, v = role & 1, slot = (threadIdx.x & 63) / LANES, jl = threadIdx.x & (LANES - 1);
@@ -1016,8 +1020,8 @@ __device__ __forceinline__ void k01_fit_block(const EccPairParams& p, long long 
         }
         baseline_pencil(C0, C1, Kp, s2, s3);
         project_pencil(Pv, Kp, p.n_x2, p.n_y2, Kv);
-        pencil_range(s2, s3, p.object_radius_mm, p.num_samples, p.dkappa_user, p.K01_out != nullptr && angle_role, K06, K07,
-                     dkappa, kappa_max);
+        const float radius = radii ? radii[(unsigned long long)(p.first + local) % (unsigned)radii_period] : p.object_radius_mm;
+        pencil_range(s2, s3, radius, p.num_samples, p.dkappa_user, p.K01_out != nullptr && angle_role, K06, K07, dkappa, kappa_max);
         Kv[6] = v ? dkappa : K06;
         Kv[7] = v ? kappa_max : K07;
     }

@@ -29,9 +29,6 @@ using namespace ecc_internal;
 #ifndef ECC_POSE_BATCH_MAX_MOVED
 #define ECC_POSE_BATCH_MAX_MOVED 32  // moved views per pose the batch takes; a pose with more is evaluated the sequential way
 #endif
-#ifndef ECC_POSE_BATCH_MAX_ENTRIES
-#define ECC_POSE_BATCH_MAX_ENTRIES (1 << 20)  // grid entries (records of 296 bytes) per batch: longer pose lists go in several batches
-#endif
 
 namespace {
 

@@ -41,12 +41,13 @@ namespace {
 // time IS the chain length.  Identical records either way.
 // The records of the workgroup's pairs (k01_fit_block) out of LDS into p.records.
 template <int LANES>
-__device__ __forceinline__ void k01_block(const EccPairParams& p, K01Shared<LANES>& sh, EccSmallEvalArg small, bool poison)
+__device__ __forceinline__ void k01_block(const EccPairParams& p, K01Shared<LANES>& sh, EccSmallEvalArg small, bool poison,
+                                          const float* radii = nullptr, int radii_period = 1)
 {
     constexpr int K01_PAIRS = 64 / LANES;
     // The records are assembled in LDS and leave the workgroup as one contiguous, coalesced block: written straight
     // from the threads every store instruction would scatter its 64 lanes over 64 records 296 bytes apart.
-    k01_fit_block<LANES>(p, (long long)blockIdx.x * K01_PAIRS, K01_PAIRS, sh, small);
+    k01_fit_block<LANES>(p, (long long)blockIdx.x * K01_PAIRS, K01_PAIRS, sh, small, nullptr, true, radii, radii_period);
     const long long first_pair = (long long)blockIdx.x * K01_PAIRS;
     const long long n_here = min((long long)K01_PAIRS, p.count - first_pair);
     if (n_here > 0) {
@@ -81,6 +82,16 @@ __global__ __launch_bounds__(256) void k01_kernel(EccPairParams p)
 {
     __shared__ K01Shared<LANES> sh;
     k01_block<LANES>(p, sh, nullptr, false);
+}
+
+// k01_kernel with an object radius per entry: entry e of the launch takes radii[e % period] instead of p.object_radius_mm (the
+// transform batch of ecc_transforms.hip: under the automatic radius every transform of a call has its own, and the radius enters
+// the records only through pencil_range).  A kernel of its own so that k01_kernel's code and registers stay what they are.
+template <int LANES>
+__global__ __launch_bounds__(256) void k01_radii_kernel(EccPairParams p, const float* __restrict__ radii, int period)
+{
+    __shared__ K01Shared<LANES> sh;
+    k01_block<LANES>(p, sh, nullptr, false, radii, period);
 }
 
 // k01_kernel<8> with E1 of the views whose matrix changed since the device arrays were made in the KERNEL ARGUMENTS (x.patch_*,
@@ -422,6 +433,22 @@ extern "C" hipError_t ecc_launch_k01(const EccPairParams* p, hipStream_t stream)
     } else if (p->count <= ECC_K01_WIDE_MAX_PAIRS)
         hipLaunchKernelGGL(k01_kernel<8>, dim3((unsigned)((p->count + 7) / 8)), dim3(256), 0, stream, *p);
     else hipLaunchKernelGGL(k01_kernel<1>, dim3((unsigned)((p->count + 63) / 64)), dim3(256), 0, stream, *p);
+    return hipGetLastError();
+}
+
+// ecc_launch_k01 with the object radius of entry e taken from radii_d[e % period] (device memory, period >= 1 floats); the
+// same choice of lanes per fit, identical records for identical radii.
+extern "C" hipError_t ecc_launch_k01_radii(const EccPairParams* p, const float* radii_d, int period, hipStream_t stream)
+{
+    if (p->count <= 0) return hipSuccess;
+    if (!radii_d || period < 1) return hipErrorInvalidValue;
+    if (p->count <= ECC_K01_LANES16_MAX_PAIRS) {
+        constexpr int per_wg = 64 / ECC_K01_SMALL_LANES;
+        hipLaunchKernelGGL(k01_radii_kernel<ECC_K01_SMALL_LANES>, dim3((unsigned)((p->count + per_wg - 1) / per_wg)), dim3(256), 0, stream, *p,
+                           radii_d, period);
+    } else if (p->count <= ECC_K01_WIDE_MAX_PAIRS)
+        hipLaunchKernelGGL(k01_radii_kernel<8>, dim3((unsigned)((p->count + 7) / 8)), dim3(256), 0, stream, *p, radii_d, period);
+    else hipLaunchKernelGGL(k01_radii_kernel<1>, dim3((unsigned)((p->count + 63) / 64)), dim3(256), 0, stream, *p, radii_d, period);
     return hipGetLastError();
 }
 

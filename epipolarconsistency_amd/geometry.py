@@ -94,3 +94,17 @@ def fundamental_matrix(P0, P1):
     e1 = P1 @ camera_center(P0)
     e1x = np.array([[0, e1[2], -e1[1]], [-e1[2], 0, e1[0]], [e1[1], -e1[0], 0]])
     return e1x @ P1 @ np.linalg.pinv(P0)
+
+
+def compose_transform(P, T):
+    """P (3x4) times T (4x4) by the library's host helper ecc_host_compose_transform: out[r, c] = ((P[r,0] T[0,c] +
+    P[r,1] T[1,c]) + P[r,2] T[2,c]) + P[r,3] T[3,c], every product and sum rounded to float64 on its own -- the matrices
+    MetricRadonIntermediate.evaluate_transforms evaluates, bit for bit (P @ T may fuse or reorder)."""
+    import ctypes as C
+
+    from . import _lib
+    Pc = np.ascontiguousarray(np.asarray(P, dtype=np.float64).reshape(3, 4).T)  # column-major, as the C ABI stores matrices
+    Tc = np.ascontiguousarray(np.asarray(T, dtype=np.float64).reshape(4, 4).T)
+    out = np.empty((4, 3), np.float64)
+    _lib.lib().ecc_host_compose_transform(C.c_void_p(Pc.ctypes.data), C.c_void_p(Tc.ctypes.data), C.c_void_p(out.ctypes.data))
+    return np.ascontiguousarray(out.T)

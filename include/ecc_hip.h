@@ -362,6 +362,42 @@ int ecc_metric_evaluate_poses_strided(ecc_metric* m, int n_poses, const double* 
 int ecc_metric_set_pose_batching(ecc_metric* m, int on);
 int ecc_metric_last_batched_poses(const ecc_metric* m, int64_t* poses);
 
+/* n_transforms rigid source-to-target transforms of two scans in one call: the registration of two scans (ref:
+ * tools/Registration/Registration3D3D.hxx:56-62, :91-110 -- a cost call multiplies every source matrix by one 4x4 transform,
+ * calls setProjectionMatrices and evaluates the index list of all source x target pairs).
+ *
+ * The metric's CURRENT matrices are the base.  Views [0, n_source) are the source scan, views [n_source, n_views) the target
+ * scan (n_target = n_views - n_source), as the reference orders them.  For transform k (Ts + 16 k, a 4x4 float64 matrix stored
+ * column-major like every matrix of this ABI) the source matrices become ecc_host_compose_transform(P_i, T_k), the target
+ * matrices stay, and the index list is: entry q = j * n_source + i -> (i, n_source + j, i, n_source + j), source index fast.
+ * means[k] = the total of that list's values in the order of csrc/ecc_sum_order.h divided by n_source * n_target -- the mean
+ * over the CROSS pairs only: source x source pairs do not change under a common rigid transform and target x target pairs do
+ * not change at all.  pair_values (host, nullable) receives n_transforms x n_target x n_source floats in list order.
+ *
+ * The contract: every means[k] and every pair value has the bits of ecc_metric_set_projections(the composed matrices) +
+ * ecc_metric_evaluate_pairs(that list) on a metric with the same parameters (tests/test_gpu_transforms.py).  So the sampling
+ * mode resolves from the list length n_source * n_target, and under the automatic object radius (the default) the radius of
+ * transform k is the one derived from the COMPOSED view 0: it differs from transform to transform, and with it the range of
+ * epipolar planes, so the values of a sweep are not strictly comparable with each other.  A registration caller should FIX
+ * the radius (ecc_metric_set_params); the automatic one is supported, inside the batch, because it is the default and the
+ * contract is the sequential calls' bits.  use_corr, a user dkappa and a fixed radius work as in the sequential calls.
+ *
+ * All transforms of the call are ONE launch that composes P_i T_k, does E1 of the composed matrices and lists the pairs, ONE
+ * record launch and ONE pair launch over the pair x transform grid, and ONE segmented float64 sum (csrc/ecc_transforms.hip);
+ * calls of more than 2^20 grid entries are cut into batches of whole transforms.  The call leaves the metric as it found it:
+ * current matrices, kept records, the kept values of the pose-delta mode and of the pose batch.  A single transform whose list
+ * alone exceeds a batch, and every transform after ecc_metric_set_pose_batching(m, 0), is evaluated the sequential way inside
+ * the call (same bits).  n_transforms = 0 does nothing.  ecc_metric_last_batched_transforms: how many transforms of the last
+ * call went through the batch.  Needs one Radon intermediate per view and 1 <= n_source < n_views.
+ * An "evaluation" here is n_source * n_target sampled pairs; it is not the all-pairs evaluation the pose batch counts. */
+int ecc_metric_evaluate_transforms(ecc_metric* m, int n_source, int n_transforms, const double* Ts, double* means,
+                                   float* pair_values);
+int ecc_metric_last_batched_transforms(const ecc_metric* m, int64_t* transforms);
+/* P (3x4) times T (4x4), both float64 and stored column-major: out(r, c) = ((P(r,0) T(0,c) + P(r,1) T(1,c)) + P(r,2) T(2,c))
+ * + P(r,3) T(3,c), every product and every sum rounded to binary64 on its own (no fused multiply-add) -- host, device and
+ * tests agree on the bits.  out12 may be P12. */
+void ecc_host_compose_transform(const double* P12, const double* T16, double* out12);
+
 /* Multi-GPU building block: evaluate only pairs ij in [first, first+count) of the get_ij order
  * (ref: EpipolarConsistencyCommon.hxx:52-79); returns the partial sum (float64) -- the caller
  * all-reduces {sum, count}.  pair_values (host, nullable) receives `count` floats. */
