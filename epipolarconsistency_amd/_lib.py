@@ -79,6 +79,8 @@ SIGNATURES = {
     "ecc_metric_evaluate_pose_deltas": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "ecc_metric_set_pose_batching": (_i, [_vp, _i]),
     "ecc_metric_last_batched_poses": (_i, [_vp, C.POINTER(_i64)]),
+    "ecc_metric_evaluate_gradient": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ecc_metric_last_gradient_path": (_i, [_vp, C.POINTER(_i)]),
     "ecc_metric_evaluate_transforms": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "ecc_metric_last_batched_transforms": (_i, [_vp, C.POINTER(_i64)]),
     "ecc_host_compose_transform": (None, [_vp, _vp, _vp]),
@@ -142,6 +144,7 @@ SIGNATURES = {
     "ecc_debug_set_small_eval_bound": (_i, [_vp, _i64]),
     "ecc_debug_set_result_polling": (_i, [_i]),
     "ecc_debug_set_quad_copies": (_i, [_vp, _i]),
+    "ecc_debug_set_gradient_launch": (_i, [_vp, _i]),
     "ecc_ctx_set_quad_copies": (_i, [_vp, _i]),
     "ecc_debug_small_stamps": (_i, [_vp, _i]),
     "ecc_debug_step_stamps": (_i, [_vp, _vp]),

@@ -400,6 +400,16 @@ class MetricRadonIntermediate:
             check(_lib.lib().ecc_debug_set_poly_tolerance(self._h, float(self._debug["poly_tolerance"])))
         if "small_eval_bound" in self._debug:
             check(_lib.lib().ecc_debug_set_small_eval_bound(self._h, int(self._debug["small_eval_bound"])))
+        if "gradient_launch" in self._debug:
+            check(_lib.lib().ecc_debug_set_gradient_launch(self._h, int(self._debug["gradient_launch"])))
+
+    def debugSetGradientLaunch(self, on=True):
+        """ecc_debug_set_gradient_launch (experiments; off by default): on = evaluate_gradient takes the probes' own launch
+        (path 2, small_poses_kernel) where it applies; off = the pose batch (path 1).  Same bits."""
+        self._debug["gradient_launch"] = 1 if on else 0
+        if self._h:
+            self._apply_debug()
+        return self
 
     def debugSetPolyTolerance(self, tol_bins):
         """ecc_debug_set_poly_tolerance (experiments): economisation bound of the polynomial path in Radon bins."""
@@ -638,6 +648,52 @@ class MetricRadonIntermediate:
     def last_batched_poses(self):
         v = C.c_int64(0)
         check(_lib.lib().ecc_metric_last_batched_poses(self._h, C.byref(v)))
+        return v.value
+
+    def evaluate_gradient(self, view, Ps_plus, Ps_minus, h, want_probes=False):
+        """ecc_metric_evaluate_gradient: the metric at the current matrices and its central-difference gradient over p pose
+        parameters of one view.  Ps_plus / Ps_minus: the view's 3x4 matrix at x + h[k] e_k and at x - h[k] e_k, p matrices each
+        (or (p, 12) column-major rows); h: the p step lengths (finite, not zero).  Returns (value, grad) -- with want_probes
+        (value, grad, probes), probes = the 2 p means plus_0, minus_0, plus_1, ...: every probe has the bits of
+        evaluate_pose_deltas / setProjectionMatrices + evaluate on its matrices, value those of evaluate(), and
+        grad[k] = (probes[2k] - probes[2k + 1]) / (2.0 * h[k]).  The current matrices stay.  last_gradient_path() says which
+        launches the call took."""
+        def rows(Ps):
+            Ps = np.asarray(Ps, np.float64)
+            return np.ascontiguousarray(Ps.reshape(-1, 12) if (Ps.shape[-1] == 12 and Ps.ndim <= 2) else _Ps_colmajor(Ps))
+        plus, minus = rows(Ps_plus), rows(Ps_minus)
+        h = np.ascontiguousarray(np.atleast_1d(h), np.float64)
+        p = len(h)
+        if p < 1 or len(plus) != p or len(minus) != p:
+            raise ValueError("Ps_plus / Ps_minus / h disagree")
+        value = C.c_double(0.0)
+        grad, probes = np.zeros(p, np.float64), np.zeros(2 * p, np.float64)
+        check(_lib.lib().ecc_metric_evaluate_gradient(self._h, int(view), p, C.c_void_p(plus.ctypes.data), C.c_void_p(minus.ctypes.data),
+                                                      C.c_void_p(h.ctypes.data), C.byref(value), C.c_void_p(grad.ctypes.data),
+                                                      C.c_void_p(probes.ctypes.data) if want_probes else None))
+        return (value.value, grad, probes) if want_probes else (value.value, grad)
+
+    def evaluate_gradient_rigid(self, view, steps, want_probes=False):
+        """evaluate_gradient over the six parameters (tx, ty, tz, rx, ry, rz) of geometry.rigid_transform for one view: probe
+        +-k is geometry.compose_transform(P_view, rigid_transform(+-steps[k] e_k)); steps: six step lengths (mm, mm, mm, rad,
+        rad, rad)."""
+        from .geometry import compose_transform, rigid_transform
+        steps = np.asarray(steps, np.float64)
+        if steps.shape != (6,):
+            raise ValueError("steps: (tx, ty, tz, rx, ry, rz)")
+        if self._Ps is None or not 0 <= int(view) < len(self._Ps):
+            raise ValueError("view outside the projection matrices")
+        P = self._Ps[int(view)].reshape(4, 3).T
+        names = ("tx", "ty", "tz", "rx", "ry", "rz")
+        plus = [compose_transform(P, rigid_transform(**{names[k]: steps[k]})) for k in range(6)]
+        minus = [compose_transform(P, rigid_transform(**{names[k]: -steps[k]})) for k in range(6)]
+        return self.evaluate_gradient(view, plus, minus, steps, want_probes)
+
+    def last_gradient_path(self):
+        """ecc_metric_last_gradient_path: 1 = the pose batch (evaluate_pose_deltas; the default), 0 = every probe sequentially
+        (setPoseBatching(False)), 2 = the probes' records and sampling as one launch (debugSetGradientLaunch(True))."""
+        v = C.c_int(0)
+        check(_lib.lib().ecc_metric_last_gradient_path(self._h, C.byref(v)))
         return v.value
 
     def evaluate_transforms(self, n_source, Ts, want_pairs=False):

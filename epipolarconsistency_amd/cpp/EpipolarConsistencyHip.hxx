@@ -764,6 +764,39 @@ public:
         return (long long)v;
     }
 
+    /// Not in the reference: ecc_metric_evaluate_gradient -- the metric at the current matrices (returned) and its
+    /// central-difference gradient over h.size() pose parameters of ONE view.  plus[p] / minus[p]: the view's matrix at
+    /// x + h[p] e_p and at x - h[p] e_p (any motion model: the caller composes them, e.g. H2D * P * T3D of
+    /// Gui/SingleImageMotion.h); grad[p] = (probes[2p] - probes[2p+1]) / (2.0 * h[p]); probes (nullable): the 2 h.size() means
+    /// plus_0, minus_0, plus_1, ..., each bit-identical to replacing the view, setProjectionMatrices and evaluate(); the
+    /// returned value is bit-identical to evaluate().  The current matrices stay.  Single device only.
+    double evaluateGradient(int view, const std::vector<Geometry::ProjectionMatrix>& plus, const std::vector<Geometry::ProjectionMatrix>& minus,
+                            const std::vector<double>& h, std::vector<double>& grad, std::vector<double>* probes = 0x0)
+    {
+        if (m_gh) throw std::runtime_error("evaluateGradient: not available on a device group");
+        if (h.empty() || plus.size() != h.size() || minus.size() != h.size())
+            throw std::runtime_error("evaluateGradient: one plus matrix, one minus matrix and one step per parameter");
+        std::vector<double> fp(12 * h.size()), fm(12 * h.size());
+        for (size_t p = 0; p < h.size(); ++p)
+            for (int q = 0; q < 12; ++q) {
+                fp[12 * p + q] = plus[p].data()[q];
+                fm[12 * p + q] = minus[p].data()[q];
+            }
+        grad.assign(h.size(), 0.0);
+        if (probes) probes->assign(2 * h.size(), 0.0);
+        double value = 0.0;
+        detail::check(ecc_metric_evaluate_gradient(m_h, view, (int)h.size(), fp.data(), fm.data(), h.data(), &value, grad.data(),
+                                                   probes ? probes->data() : 0x0));
+        return value;
+    }
+    /// Which launches the last evaluateGradient took: 1 the pose batch (default), 0 sequential, 2 the probes' own launch (opt-in, ecc_hip.h).
+    int lastGradientPath() const
+    {
+        int v = 0;
+        if (m_h && !m_gh) detail::check(ecc_metric_last_gradient_path(m_h, &v));
+        return v;
+    }
+
     /// The metric borrows the dtrs: "DO NOT delete or change _dtrs during lifetime" (ref: .h:45).
     MetricRadonIntermediate& setRadonIntermediates(const std::vector<RadonIntermediate*>& _dtrs)
     {

@@ -44,6 +44,8 @@ extern "C" hipError_t ecc_launch_k01_patched(const EccPairParams* p, const EccSm
 extern "C" hipError_t ecc_launch_pairs(const EccPairParams* p, hipStream_t stream);
 extern "C" int ecc_small_eval_plan(const EccPairParams* p, long long forced_bound, int* wpp, size_t* lds_bytes);
 extern "C" hipError_t ecc_launch_small_eval(const EccPairParams* p, const EccSmallEval* x, hipStream_t stream);
+extern "C" int ecc_small_poses_plan(const EccPairParams* p, int Q, int* wpp, size_t* lds_bytes);
+extern "C" hipError_t ecc_launch_small_poses(const EccPairParams* p, const EccSmallEval* x, const EccSmallPoses* y, hipStream_t stream);
 extern "C" hipError_t ecc_launch_preprocess(const EccPreprocessParams* p, hipStream_t stream);
 extern "C" size_t ecc_preprocess_lds_bytes(int k);
 extern "C" hipError_t ecc_launch_direct_views(const double* Ps_d, int n, EccDirectView* views, int n_u, int n_v,
@@ -377,6 +379,10 @@ struct ecc_metric {
     DeviceArray<double> pose_partial_d;
     DeviceArray<int32_t> pose_lists_d;
     int64_t last_batched_poses = 0;    // poses the last ecc_metric_evaluate_poses* call took through the batch (ecc_metric_last_batched_poses)
+    // ecc_metric_evaluate_gradient (ecc_gradient.hip): the probes of one moved view as ONE record-and-sampling launch
+    // (small_poses_kernel.hip) in front of the batch's segmented sum; it uses pose_values_d, pose_partial_d, pose_lists_d and pose_h.
+    int gradient_launch = 0;     // ecc_debug_set_gradient_launch: off by default -- measured no faster than the pose batch
+    int last_gradient_path = 0;  // ecc_metric_last_gradient_path
     // ecc_metric_evaluate_transforms (ecc_transforms.hip) uses the scratch above (pose_lists_d: its value slots) and, under the
     // automatic object radius, one float per transform of a batch
     DeviceArray<float> transform_radii_d;
@@ -409,6 +415,11 @@ int fill_pair_params(ecc_metric* m, EccPairParams* p, int64_t mode_count, bool n
 int launch_range(ecc_metric* m, int64_t first, int64_t count, float* pair_values_d, float* cost_d, float* K01_d, double* sum_d,
                  bool synchronous = false);
 int evaluate_cached(ecc_metric* m, int64_t first, int64_t count, double* sum_d, float** vals_out);
+
+// ecc_poses.hip: the segmented sum behind a batch's pair launch and the wait for its results; whether a pose keeps the base's
+// (automatic) object radius
+int sum_poses(ecc_metric* m, const float* base_vals_d, int K, int Q, volatile uint64_t* out, double* out_dev, double* sums);
+bool pose_keeps_radius(const ecc_metric* m, double base_radius, int c, const int32_t* views, const double* moved_Ps);
 
 // The pair launch p -- or, with x, the one-launch evaluation -- on the context's stream between its timing events (ecc_ctx_enable_timing).
 inline hipError_t launch_pairs_timed(ecc_ctx* ctx, const EccPairParams* p, const EccSmallEval* x = nullptr)

@@ -220,6 +220,16 @@ struct EccSmallEval {
     float patch_geo[ECC_SMALL_PATCH_MAX][16];
 };
 
+// ---- the probes of a finite-difference gradient in one launch (small_poses_kernel.hip) ---------
+// Q probe matrices of ONE moved view: entry u * Q + q of the launch is the pair {partner u, view} under probe q's matrix, whose
+// E1 is entry q of the EccSmallEval patch list in the same kernel arguments, filed under the geometry index n_views + q.
+struct EccSmallPoses {
+    int view;          // the moved view
+    int Q;             // probes (at most ECC_SMALL_PATCH_MAX)
+    int n_poses;       // poses sum_poses_kernel adds afterwards: the Q probes, one column each, then poses that move nothing
+    int32_t* lists_d;  // the (pose -> moved view) lists of sum_poses_kernel (ecc_poses.hip), written by workgroup 0
+};
+
 // ---- projection pre-processing ------------------------------------------------
 #define ECC_PRE_MAX_CHUNKS 32  // workgroups per image of the maximum search in front of PreProccess::process (normalize)
 struct EccPreprocessParams {

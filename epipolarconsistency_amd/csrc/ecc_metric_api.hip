@@ -244,8 +244,9 @@ ECC_EXPORT int ecc_metric_set_projections(ecc_metric* m, const double* Ps, int n
         m->done_generation = m->set_generation;
         m->dev_valid = false;
         m->geom_capacity = 0;  // until all of them have grown: a failed ensure may leave an array freed
-        rc = m->Cs_d.ensure(4 * (int64_t)n_views, ctx->stream);
-        if (!rc) rc = m->PinvTs_d.ensure(12 * (int64_t)n_views, ctx->stream);
+        // (behind the views: room for the ECC_SMALL_PATCH_MAX probe entries small_poses_kernel files under n_views, n_views + 1, ...)
+        rc = m->Cs_d.ensure(4 * (int64_t)(n_views + ECC_SMALL_PATCH_MAX), ctx->stream);
+        if (!rc) rc = m->PinvTs_d.ensure(12 * (int64_t)(n_views + ECC_SMALL_PATCH_MAX), ctx->stream);
         for (int b = 0; b < 2 && !rc; ++b) rc = m->Ps_h[b].ensure(12 * (int64_t)n_views, 0, ctx->stream);
         if (rc) return rc;
         m->geom_capacity = n_views;

@@ -362,6 +362,47 @@ int ecc_metric_evaluate_poses_strided(ecc_metric* m, int n_poses, const double* 
 int ecc_metric_set_pose_batching(ecc_metric* m, int on);
 int ecc_metric_last_batched_poses(const ecc_metric* m, int64_t* poses);
 
+/* The finite-difference gradient of the metric over n_params pose parameters of ONE view: the metric at the current matrices
+ * and its 2 n_params central-difference probes in one call (what every optimiser step of a moved view asks for; ref:
+ * Gui/SingleImageMotion.h:84-90, six parameters of the "3D Rigid" model).  The caller supplies the probe MATRICES -- Ps_plus and
+ * Ps_minus: n_params x 12 float64, the view's 3x4 matrix (column-major) at x + h[p] e_p and at x - h[p] e_p -- so the library
+ * stays free of any motion model.  h: the n_params step lengths.  value (nullable), grad (n_params), probes (nullable,
+ * 2 n_params: plus_0, minus_0, plus_1, ...).
+ *
+ * The contract (tests/test_gpu_gradient.py):
+ *   - probes[k] has THE BITS of ecc_metric_evaluate_pose_deltas for the pose "current matrices with `view` replaced by probe k",
+ *     hence of ecc_metric_set_projections + ecc_metric_evaluate_all on those matrices; *value has the bits of
+ *     ecc_metric_evaluate_all on the current matrices.
+ *   - grad[p] = (probes[2p] - probes[2p + 1]) / (2.0 * h[p]) in binary64: one subtraction, one multiplication, one division,
+ *     in that order, on the host.
+ *   - The call leaves the metric as ecc_metric_evaluate_pose_deltas does: current matrices unchanged, the base's pair values
+ *     kept for the next call (only the pairs of views changed since are redone).
+ *   - Errors before anything is launched (ECC_ERR_INVALID_ARGUMENT): m == NULL (checked first), another null pointer among
+ *     Ps_plus, Ps_minus, h, grad; n_params < 1; no matrices set, fewer than two views; view outside [0, n_views); an h[p] that
+ *     is zero or not finite.
+ *
+ * ecc_metric_last_gradient_path: which way the last call went.
+ *   1  (the default) ecc_metric_evaluate_pose_deltas with the 2 n_params probes and one pose that moves nothing (for *value);
+ *      that call evaluates a probe that changes the automatic object radius the sequential way itself.
+ *   0  the same call after ecc_metric_set_pose_batching(m, 0): every probe sequentially.
+ *   2  ONE launch for records and sampling of all probes (csrc/small_poses_kernel.hip: E1 of the probe matrices on the host,
+ *      handed over in the kernel arguments) + the segmented sum of the pose batch: two launches, three from 257 views, instead
+ *      of five.  OPT-IN, ecc_debug_set_gradient_launch(m, 1): measured on one MI355X it is not faster than path 1 by more than
+ *      the run-to-run spread at 400 views and slower at 258 (DESIGN.md 4.11 has the numbers), so the default stays path 1.
+ * Same bits whichever way.  With the launch switched on, whatever it does not take goes through path 1 (or 0) INSIDE the same
+ * call.  It declines, and only then:
+ *   - n_params > 8 (the launch holds 16 probe entries);
+ *   - view == 0 under the automatic object radius (object_radius_mm <= 0) when a probe changes the radius;
+ *   - use_corr (MetricRadonIntermediate::useCorrelation);
+ *   - ECC_SAMPLING_REFERENCE chosen with ecc_metric_set_sampling on more than 2048 pairs (65 views or more; the automatic mode
+ *     never resolves to the reference arithmetic there);
+ *   - ecc_metric_set_pose_batching(m, 0) (path 0).
+ * Every other state is taken: the automatic sampling mode at every size, ECC_SAMPLING_POLYNOMIAL / _PER_SAMPLE, a user dkappa, a
+ * fixed or automatic radius, record reuse on or off, the pose-delta mode on or off. */
+int ecc_metric_evaluate_gradient(ecc_metric* m, int view, int n_params, const double* Ps_plus, const double* Ps_minus,
+                                 const double* h, double* value, double* grad, double* probes);
+int ecc_metric_last_gradient_path(const ecc_metric* m, int* path);
+
 /* n_transforms rigid source-to-target transforms of two scans in one call: the registration of two scans (ref:
  * tools/Registration/Registration3D3D.hxx:56-62, :91-110 -- a cost call multiplies every source matrix by one 4x4 transform,
  * calls setProjectionMatrices and evaluates the index list of all source x target pairs).
@@ -640,12 +681,15 @@ int ecc_ctx_last_kernel_ms(ecc_ctx* ctx, int which, float* ms);
  * ecc_debug_set_result_polling: process-wide; 0 = synchronous calls wait for the stream instead of polling the pinned
  *   result slot.  Same bits.
  * ecc_debug_set_quad_copies: ecc_ctx_set_quad_copies(ctx, on ? ECC_QUAD_COPIES_ON : ECC_QUAD_COPIES_OFF), the experiments' old name.
+ * ecc_debug_set_gradient_launch: 1 = ecc_metric_evaluate_gradient takes its own launch (path 2, csrc/small_poses_kernel.hip)
+ *   where that launch applies; 0 (default) = always the pose batch.  Same bits either way.
  * ecc_debug_small_stamps: only in builds with -DECC_SMALL_STAMPS (returns ECC_ERR_INVALID_ARGUMENT otherwise). */
 #define ECC_POLY_ECONOMISE_TOL_BINS 2e-8f
 int ecc_debug_set_poly_tolerance(ecc_metric* m, float tol_bins);
 int ecc_debug_set_small_eval_bound(ecc_metric* m, int64_t max_pairs);
 int ecc_debug_set_result_polling(int on);
 int ecc_debug_set_quad_copies(ecc_ctx* ctx, int on);
+int ecc_debug_set_gradient_launch(ecc_metric* m, int on);
 /* Row-quad copies.  Metrics created from ctx AFTERWARDS keep, beside the row-paired copy of every Radon intermediate (one
  * 16-byte footprint per sample), a second copy in which four consecutive angle rows share a 128-byte line (4x the slab's
  * memory: 3.9 GB for 400 views of 768 x 768 bins).  The pairs whose baseline passes through the object (kappa_max = pi/2,
