@@ -696,6 +696,21 @@ class MetricRadonIntermediate:
         check(_lib.lib().ecc_metric_last_gradient_path(self._h, C.byref(v)))
         return v.value
 
+    def evaluate_gram(self, n_channels, want_pairs=False):
+        """ecc_metric_evaluate_gram: the metric as a quadratic form of the coefficients of n_channels fixed channel images per view
+        (corrected image of view i = sum_c a_c I_c,i).  The metric holds n_channels * n_views Radon intermediates, channel-major
+        (channel c of view i is dtr c * n_views + i), computed with POST_IDENTITY.  Returns G, (K, K) float64 and symmetric, with
+        metric(a) = gram_value(G, a) -- with want_pairs (G, pairs), pairs (n_pairs, K (K + 1) / 2) float32 in the pair order of
+        evaluate(cost) and the entry order (0,0), (0,1) .. (K-1,K-1).  Diagonal entries have the bits of evaluate(cost) on a metric
+        of that channel's intermediates alone.  The current matrices and everything the metric keeps stay."""
+        K = int(n_channels)
+        n = 0 if self._Ps is None else len(self._Ps)  # (no matrices: the library reports it)
+        G = np.zeros((max(K, 0), max(K, 0)), np.float64)
+        pairs = np.zeros((n * (n - 1) // 2, max(K, 0) * (max(K, 0) + 1) // 2), np.float32) if want_pairs else None
+        check(_lib.lib().ecc_metric_evaluate_gram(self._h, K, C.c_void_p(pairs.ctypes.data) if (want_pairs and pairs.size) else None,
+                                                  C.c_void_p(G.ctypes.data) if G.size else None))
+        return (G, pairs) if want_pairs else G
+
     def evaluate_transforms(self, n_source, Ts, want_pairs=False):
         """ecc_metric_evaluate_transforms: the registration of two scans (ref: tools/Registration/Registration3D3D.hxx).  The
         current matrices are the base, views [0, n_source) the source scan, the rest the target scan; Ts: anything np.asarray
@@ -1179,3 +1194,33 @@ def estimateIsoCenter(Ps):
 
 
 estimateObjectRadius = host_object_radius  # ref: estimateObjectRadius (EpipolarConsistency.cpp:35-47)
+
+
+def gram_value(G, a):
+    """a^T G a in float64: the metric of the coefficient vector a under the Gram matrix of evaluate_gram."""
+    G = np.asarray(G, np.float64)
+    a = np.asarray(a, np.float64).reshape(-1)
+    if G.ndim != 2 or G.shape != (len(a), len(a)):
+        raise ValueError("G must be (K, K) and a (K,)")
+    return float(a @ (G @ a))
+
+
+def gram_minimizer(G, fixed=0, value=1.0):
+    """The minimiser of a^T G a under a[fixed] = value: with F the free coordinates, G[F, F] a_F = -value * G[F, fixed] (one
+    numpy.linalg.solve).  Returns (a, a^T G a).  Raises numpy.linalg.LinAlgError when G[F, F] is not positive definite -- the form
+    has no minimum there."""
+    G = np.asarray(G, np.float64)
+    if G.ndim != 2 or G.shape[0] != G.shape[1] or G.shape[0] < 1:
+        raise ValueError("G must be (K, K)")
+    K = G.shape[0]
+    fixed = int(fixed)
+    if not 0 <= fixed < K:
+        raise ValueError("fixed outside [0, K)")
+    free = [c for c in range(K) if c != fixed]
+    a = np.zeros(K, np.float64)
+    a[fixed] = float(value)
+    if free:
+        H = 0.5 * (G[np.ix_(free, free)] + G[np.ix_(free, free)].T)
+        np.linalg.cholesky(H)  # raises LinAlgError unless positive definite
+        a[free] = np.linalg.solve(H, -float(value) * 0.5 * (G[free, fixed] + G[fixed, free]))
+    return a, gram_value(G, a)

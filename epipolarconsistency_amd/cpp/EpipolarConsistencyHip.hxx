@@ -797,6 +797,24 @@ public:
         return v;
     }
 
+    /// Not in the reference: ecc_metric_evaluate_gram -- the metric as a quadratic form a^T G a of the coefficients of n_channels
+    /// fixed channel images per view (corrected image of view i = sum_c a_c I_c,i: beam-hardening linearisation, scatter or
+    /// offset correction).  The Radon intermediates are channel-major -- channel c of view i is dtrs[c * n_views + i] -- and
+    /// computed with the IDENTITY post-process.  G: n_channels x n_channels, symmetric, row-major; pair_grams (nullable):
+    /// n_pairs x n_channels (n_channels + 1) / 2 floats, pair-major, entries (0,0), (0,1) .. (K-1,K-1).  The diagonal entries are
+    /// bit-identical to evaluate() on each channel's intermediates alone (ecc_hip.h).  Single device only.
+    void evaluateGram(int n_channels, std::vector<double>& G, std::vector<float>* pair_grams = 0x0)
+    {
+        if (m_gh) throw std::runtime_error("evaluateGram: not available on a device group");
+        if (n_channels < 1 || n_channels > ECC_GRAM_MAX_CHANNELS) throw std::runtime_error("evaluateGram: n_channels outside [1, ECC_GRAM_MAX_CHANNELS]");
+        G.assign((size_t)n_channels * n_channels, 0.0);
+        if (pair_grams) {
+            const size_t n = Ps.size(), T = (size_t)n_channels * (n_channels + 1) / 2;
+            pair_grams->assign(n * (n > 0 ? n - 1 : 0) / 2 * T, 0.f);
+        }
+        detail::check(ecc_metric_evaluate_gram(m_h, n_channels, pair_grams ? pair_grams->data() : 0x0, G.data()));
+    }
+
     /// The metric borrows the dtrs: "DO NOT delete or change _dtrs during lifetime" (ref: .h:45).
     MetricRadonIntermediate& setRadonIntermediates(const std::vector<RadonIntermediate*>& _dtrs)
     {

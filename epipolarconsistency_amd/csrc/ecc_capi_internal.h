@@ -383,6 +383,11 @@ struct ecc_metric {
     // (small_poses_kernel.hip) in front of the batch's segmented sum; it uses pose_values_d, pose_partial_d, pose_lists_d and pose_h.
     int gradient_launch = 0;     // ecc_debug_set_gradient_launch: off by default -- measured no faster than the pose batch
     int last_gradient_path = 0;  // ecc_metric_last_gradient_path
+    // ecc_metric_evaluate_gram (ecc_gram.hip): records, pair entries (T columns) and slice sums of that call alone, grown on demand --
+    // the call leaves the kept records and values above as they are
+    DeviceArray<EccPairRecord> gram_records_d;
+    DeviceArray<float> gram_values_d;
+    DeviceArray<double> gram_partial_d;
     // ecc_metric_evaluate_transforms (ecc_transforms.hip) uses the scratch above (pose_lists_d: its value slots) and, under the
     // automatic object radius, one float per transform of a batch
     DeviceArray<float> transform_radii_d;

@@ -230,6 +230,19 @@ struct EccSmallPoses {
     int32_t* lists_d;  // the (pose -> moved view) lists of sum_poses_kernel (ecc_poses.hip), written by workgroup 0
 };
 
+// ---- the metric as a quadratic form of channel coefficients (gram_kernel.hip) -------------------
+// The metric's Radon intermediates are channel-major: channel c of view i is dtr c * n_views + i.  Its row-paired (row-quad)
+// copies are ONE allocation with dtr k at k * copy size, so channel c of a view is a launch-uniform byte distance away.
+// T = K (K + 1) / 2 entries per pair, (0,0), (0,1) .. (0,K-1), (1,1) .. (K-1,K-1), stored COLUMN-major: entry t of pair q at
+// values[t * col_stride + q] (col_stride a multiple of 4 floats: every column is summed as float4, ecc_sum_order.h).
+#define ECC_GRAM_CHANNELS_MAX 4
+struct EccGramParams {
+    int64_t paired_channel_bytes;  // n_views * bytes of one row-paired copy
+    int64_t quad_channel_bytes;    // n_views * bytes of one row-quad copy (used when EccPairParams::quads is set)
+    float* values;                 // T columns of col_stride floats
+    int64_t col_stride;
+};
+
 // ---- projection pre-processing ------------------------------------------------
 #define ECC_PRE_MAX_CHUNKS 32  // workgroups per image of the maximum search in front of PreProccess::process (normalize)
 struct EccPreprocessParams {

@@ -403,6 +403,50 @@ int ecc_metric_evaluate_gradient(ecc_metric* m, int view, int n_params, const do
                                  const double* h, double* value, double* grad, double* probes);
 int ecc_metric_last_gradient_path(const ecc_metric* m, int* path);
 
+/* The metric as a QUADRATIC FORM of channel coefficients, for the optimisers that move the IMAGES and leave the matrices alone
+ * (beam-hardening linearisation, empirical scatter or offset correction):
+ *     corrected image of view i = sum_c a_c I_c,i      (I_c,i: K fixed "channel" images per view, a: K coefficients).
+ * Line integrals, the derivative across t, the ramp filter and bilinear sampling are linear, so the Radon intermediate of the
+ * corrected image is sum_c a_c D_c,i (D_c,i: the intermediate of I_c,i), every redundant sample is linear in a, and
+ *     metric(a) = a^T G a,   G[c][d] = mean over the pairs of g_ij[c][d],
+ *     g_ij[c][d] = sum_kappa (delta_c+ delta_d+ + delta_c- delta_d-) K0[6] dkappa,  delta_c = signed sample of D_c,i - of D_c,j,
+ * with the sample positions, fold signs, kappa range and weights of ecc_metric_evaluate_all (they depend on the matrices only).
+ * One call replaces the device work of the whole optimisation: G gives the metric of every a in closed form.
+ *
+ * The metric must hold n_dtrs = n_channels * n_views Radon intermediates, CHANNEL-MAJOR: channel c of view i is dtr
+ * c * n_views + i.  The POST-PROCESS of every intermediate must be the identity (ECC_POST_IDENTITY): square root and logarithm
+ * are not linear, and the metric cannot check it (ecc_dtr_info does not report it).  All channels need the same bin counts
+ * (ecc_metric_create checks that) and the same image size.  The other calls keep their meaning on such a metric:
+ * ecc_metric_evaluate_all and the pose calls evaluate dtrs 0 .. n_views - 1, i.e. channel 0; ecc_metric_evaluate_transforms
+ * wants n_dtrs == n_views and goes on refusing it.  Memory: the metric's private copies grow with K * n like any metric's
+ * (row-paired always, row-quad when they are built); the call adds none, only 296 + 2 K (K + 1) bytes per pair of scratch.
+ *
+ * gram (required): n_channels x n_channels float64, the full symmetric matrix.  pair_grams (host, nullable): n_pairs x T
+ * float32, T = K (K + 1) / 2, pair-major in the pair order of get_ij, entries in the order (0,0), (0,1) .. (0,K-1), (1,1) ..
+ * (K-1,K-1).  All pairs over the current matrices.  The sampling mode resolves from n (n - 1) / 2 as in ecc_metric_evaluate_all;
+ * ECC_SAMPLING_POLYNOMIAL (with its per-pair fallback and exact tail), _PER_SAMPLE and _REFERENCE are all taken, and so are a
+ * fixed or automatic object radius, a user dkappa and non-derivative intermediates (the flag comes from dtrs[0], as everywhere).
+ *
+ * The contract (tests/test_gpu_gram.py):
+ *   1. Diagonal, bit for bit.  pair_grams[q][(c,c)] has the bits of the cost-image entry ecc_metric_evaluate_all writes for pair
+ *      q on a metric created from channel c's n_views intermediates alone with the same matrices, parameters and sampling mode;
+ *      gram[c][c] has the bits of that call's mean.  Per sample the term of entry (c, d) is that evaluation's expression with the
+ *      second factor exchanged, accumulated in float64 per lane in the same trip order, reduced by the same wave tree, rounded to
+ *      float32 per pair entry; each of the T columns is summed over the pairs in the order of csrc/ecc_sum_order.h and divided
+ *      by n_pairs.  n_channels = 1 is ecc_metric_evaluate_all with a cost image.
+ *   2. Symmetric by construction: only c <= d is computed, gram[d][c] is a copy.
+ *   3. Off-diagonal entries agree with the polarisation of the CPU oracle's pair values to its own floor (the tests measure it).
+ *   - The call changes nothing a later call can see: current matrices, kept records, the kept values of the pose-delta mode and
+ *     of the pose batch.
+ *   - Errors before anything is launched, ECC_ERR_INVALID_ARGUMENT: m == NULL (checked first), gram == NULL, n_channels outside
+ *     [1, ECC_GRAM_MAX_CHANNELS], no matrices set or fewer than two views, n_dtrs != n_channels * n_views.  use_corr set:
+ *     ECC_ERR_UNSUPPORTED (the correlation cost is not a quadratic form).
+ * Launches (csrc/ecc_gram.hip, csrc/gram_kernel.hip): the record kernel over all pairs, pairs_gram_kernel -- one wave per pair,
+ * the position arithmetic of a kappa step once for all channels, 4 K gathers and T products per step --, one launch for the T
+ * column sums.  A once-per-data-set call: it has no small-evaluation or sharded form. */
+#define ECC_GRAM_MAX_CHANNELS 4
+int ecc_metric_evaluate_gram(ecc_metric* m, int n_channels, float* pair_grams, double* gram);
+
 /* n_transforms rigid source-to-target transforms of two scans in one call: the registration of two scans (ref:
  * tools/Registration/Registration3D3D.hxx:56-62, :91-110 -- a cost call multiplies every source matrix by one 4x4 transform,
  * calls setProjectionMatrices and evaluates the index list of all source x target pairs).
