@@ -1,5 +1,6 @@
 // ecc_pairs_device.h -- device code shared by the pair kernels (pairs_kernel.hip: k01_kernel, pairs_kernel,
-// pairs_reference_kernel, pair_samples_kernel) and the one-launch evaluation of small pair sets (small_eval_kernel.hip):
+// pairs_reference_kernel, pair_samples_kernel), the one-launch evaluations of small pair sets (small_eval_kernel.hip,
+// small_poses_kernel.hip) and the Gram form's kernels (gram_kernel.hip):
 // pair geometry (ref: EpipolarConsistencyCommon.hxx:82-149), the sampling loops of one pair (ref:
 // EpipolarConsistencyRadonIntermediate.cu:71-113,214-276), the polynomial fit of the sample coordinates and the plain
 // CPU-path arithmetic of ECC_SAMPLING_REFERENCE.  Everything is in an anonymous namespace: each translation unit gets
@@ -9,6 +10,7 @@
 
 #include <hip/hip_runtime.h>
 #include <float.h>
+#include <type_traits>
 
 #include "ecc_layout.h"
 #include "ecc_sum_order.h"
@@ -125,6 +127,51 @@ struct __attribute__((packed, aligned(4))) F4 {
 __device__ __forceinline__ float uniformf(float v)
 {
     return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+}
+
+// A wave-uniform 64-bit index into scalar registers (readfirstlane makes an address formed from it provably uniform: scalar loads).
+__device__ __forceinline__ long long uniform_index(long long i)
+{
+    return ((long long)__builtin_amdgcn_readfirstlane((int)(i >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)i);
+}
+
+// Workgroup and wave -> pair of the one-wave-per-pair kernels (pairs_kernel; pairs_gram_kernel, gram_kernel.hip), launched on
+// main_pairs_grid(count): false when this wave has none (no barriers in those kernels: waves leave independently), else the
+// pair's index in `local` -- the same in all lanes; the caller moves it to scalar registers (uniform_index) once it is past
+// the test (inside this helper the compiler takes the merged value for a vector again).
+// XCD-aware: workgroups b and b+8 share an XCD, and an XCD walks a contiguous part of the
+// pair order (consecutive pairs share view i and have neighbouring partners j: their dtr bands are re-used out
+// of that XCD's L2).  The four waves of a workgroup, however, take pairs a quarter of the range apart: with four
+// CONSECUTIVE pairs per workgroup the waves run in lockstep through nearly the same lines of view i, and the L1
+// serialises hits on lines whose fill is still in flight (TCP_PENDING_STALL_CYCLES: a quarter of its busy time)
+// -- 0.400 -> 0.335 ms for 79 800 pairs; spreading further (other strides, 2-D tiles of views that halve the HBM
+// traffic) was slower, see DESIGN.md 4.2.
+// (Several waves per pair for small shards -- wave h takes the kappa iterations it % split == h, float64 partial
+// sums combined by the sum kernel -- were measured and dropped: a 9 975-pair shard 80 us per step with whole-pair
+// waves, 89 us with two, 106 us with four waves per pair.)
+// (A host-made launch schedule that gives the kappa_max = pi/2 pairs evenly spaced positions, everything else keeping
+// its order: with explicit index lists over all 79 800 pairs it looked promising -- natural order 0.361 ms, those
+// pairs first 0.460, last 0.422, as whole workgroups first 0.601, spread evenly 0.348, scripts/exp_heavy_first.py --
+// but built into this mapping it was 1.5 % SLOWER, 0.3365 vs 0.3315 ms: the four-quarters mapping already spreads
+// them over the first quarter of every workgroup.)
+// (Persistent waves -- a launch sized to be resident at once, every wave handling several pairs in turn -- were
+// measured too: 79 800 pairs 0.38 / 0.43 ms with 5 / 10 pairs per wave against 0.33 ms, the shard 86 us with two.)
+__device__ __forceinline__ bool main_pair_of_wave(long long count, long long& local)
+{
+    const int wave = threadIdx.x >> 6;
+    const long long nblk = (count + PK_MAIN_WAVES - 1) / PK_MAIN_WAVES;
+    const long long per_xcd = (nblk + 7) / 8;
+    const long long blk = (long long)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+    if (blk >= nblk) return false;
+    local = (long long)wave * nblk + blk;
+    return local < count;
+}
+
+// The grid main_pair_of_wave is written for: whole rounds of the 8 XCDs.
+inline dim3 main_pairs_grid(long long count)
+{
+    const long long nblk = (count + PK_MAIN_WAVES - 1) / PK_MAIN_WAVES, per_xcd = (nblk + 7) / 8;
+    return dim3((unsigned)(per_xcd * 8));
 }
 
 // sin and cos of kappa in [0, pi/2]: reduce to [0, pi/4] by kappa -> pi/2 - kappa (exact subtraction
@@ -374,17 +421,22 @@ __device__ __forceinline__ void poly_pm(const float* c, float lo_plus, float lo_
 #endif
 }
 
-// Addressing, the one 16-byte load and the bilinear rule for a sample whose coordinates are already known.
+// Addressing, the one 16-byte load and the bilinear rule for a sample whose coordinates are already known: sample_at is
+// sample_tap (where) + sample_tap_value (what is there) + the fold's sign.
 // (Non-temporal loads for the view whose band no later pair of the XCD re-uses were measured: they bypass the L1 as
 // well and lose the reuse between neighbouring lanes, 0.397 vs 0.338 ms.)
 // NOCLAMP: k01's bound on the pair's polynomials (record.poly_ok bit 0) says that neither coordinate can reach a clamp: the
 // two v_med3 would return their inputs, and are left out.
-template <bool DERIV, int PITCH4, bool NOCLAMP = false>
-__device__ __forceinline__ float sample_at(float xa, float yd, unsigned fold, const SlabView sv, float n_t_f, float pitch4_f,
-                                           float xa_max)
+struct SampleTap {
+    unsigned off;  // byte offset of the 2x2 footprint inside a row-paired copy
+    float fx, fy;  // bilinear weights
+};
+
+// The position half: cell, fractions and byte offset (the same for every copy of the same layout -- gram_kernel.hip).
+template <int PITCH4, bool NOCLAMP = false>
+__device__ __forceinline__ SampleTap sample_tap(float xa, float yd, const SlabView sv, float n_t_f, float pitch4_f, float xa_max)
 {
-    float fx, fy;
-    unsigned off;
+    SampleTap t;
     if (PITCH4 > 0) {
         // Cell index and fraction without v_fract_f32 / v_cvt_u32_f32 (quarter rate): x + (2^23 - 0.5) is rounded to the
         // integer 2^23 + rn(x - 0.5) -- the cell floor(x), or x - 1 with fraction 1 when x is an exact integer: the same
@@ -397,24 +449,36 @@ __device__ __forceinline__ float sample_at(float xa, float yd, unsigned fold, co
         // pitch: one v_med3 keeps a misbehaving fit inside the slab (advisor, round 3; values in range are not changed)
         if (!NOCLAMP) xa = __builtin_amdgcn_fmed3f(xa, 0.5f, xa_max);
         const float ma = xa + 8388607.5f, md = yd + 8388607.5f;
-        fx = xa - (ma - 8388608.f);
-        fy = yd - (md - 8388608.f);
+        t.fx = xa - (ma - 8388608.f);
+        t.fy = yd - (md - 8388608.f);
         unsigned bin8;  // the low 24 bits of md's pattern (the bin index) times 8: one v_mul_u32_u24 (the compiler would
                         // turn the multiplication by 8 into a shift and a mask)
         asm("v_mul_u32_u24 %0, %1, 8" : "=v"(bin8) : "v"(__float_as_uint(md)));
-        off = __umul24(__float_as_uint(ma), (unsigned)PITCH4) + bin8;
+        t.off = __umul24(__float_as_uint(ma), (unsigned)PITCH4) + bin8;
     } else {
         yd = __builtin_amdgcn_fmed3f(yd, 0.f, n_t_f);
         xa = __builtin_amdgcn_fmed3f(xa, 0.5f, xa_max);
-        fx = __builtin_amdgcn_fractf(xa);
-        fy = __builtin_amdgcn_fractf(yd);
-        off = footprint_offset<PITCH4>(xa - fx, yd - fy, sv.pitch4, pitch4_f);
+        t.fx = __builtin_amdgcn_fractf(xa);
+        t.fy = __builtin_amdgcn_fractf(yd);
+        t.off = footprint_offset<PITCH4>(xa - t.fx, yd - t.fy, sv.pitch4, pitch4_f);
     }
-    const ecc_v4f_a4 q4 = *(GlobalF4)(sv.origin + off);
-    const F4 q = {q4.x, q4.y, q4.z, q4.w};
-    const float r0 = fmaf(fx, q.y, q.x);  // q.y, q.w: the row differences, formed when the copy is built
-    const float r1 = fmaf(fx, q.w, q.z);
-    const float v = fmaf(fy, r1 - r0, r0);
+    return t;
+}
+
+// The value half: the one 16-byte load at `origin` (a copy's base) and the bilinear rule; the unsigned sample.
+__device__ __forceinline__ float sample_tap_value(GlobalBytes origin, const SampleTap t)
+{
+    const ecc_v4f_a4 q4 = *(GlobalF4)(origin + t.off);
+    const float r0 = fmaf(t.fx, q4.y, q4.x);  // q4.y, q4.w: the row differences, formed when the copy is built
+    const float r1 = fmaf(t.fx, q4.w, q4.z);
+    return fmaf(t.fy, r1 - r0, r0);
+}
+
+template <bool DERIV, int PITCH4, bool NOCLAMP = false>
+__device__ __forceinline__ float sample_at(float xa, float yd, unsigned fold, const SlabView sv, float n_t_f, float pitch4_f,
+                                           float xa_max)
+{
+    const float v = sample_tap_value(sv.origin, sample_tap<PITCH4, NOCLAMP>(xa, yd, sv, n_t_f, pitch4_f, xa_max));
     return DERIV ? __uint_as_float(__float_as_uint(v) ^ fold) : v;
 }
 
@@ -1137,6 +1201,64 @@ __device__ __forceinline__ void k01_fit_block(const EccPairParams& p, long long 
 }
 
 
+// Which polynomial loop a pair takes, from wave-uniform selectors: f(PITCH4, DEG, NOCLAMP) is called once, with
+// std::integral_constants, so that a generic lambda can name the loop's template arguments (pair_accumulate below;
+// gram_accumulate, gram_kernel.hip).  poly_ok: the degree the record asks for; in_range: its clamp-free bit.
+template <int V> using IntC = std::integral_constant<int, V>;
+template <bool V> using BoolC = std::integral_constant<bool, V>;
+
+template <class F>
+__device__ __forceinline__ void poly_loop_dispatch(bool wide_offsets, unsigned pitch4, int poly_ok, bool in_range, F&& f)
+{
+    if (wide_offsets) {
+        if (poly_ok <= 6) f(IntC<-1>{}, IntC<6>{}, BoolC<false>{});
+        else f(IntC<-1>{}, IntC<ECC_POLY_DEG>{}, BoolC<false>{});
+    } else if (pitch4 == 6400u && in_range) {  // (the clamp-free loops exist for the default 768 distance bins only)
+        if (poly_ok <= 4) f(IntC<6400>{}, IntC<4>{}, BoolC<true>{});
+        else if (poly_ok <= 6) f(IntC<6400>{}, IntC<6>{}, BoolC<true>{});
+        else if (poly_ok <= 8) f(IntC<6400>{}, IntC<8>{}, BoolC<true>{});
+        else f(IntC<6400>{}, IntC<ECC_POLY_DEG>{}, BoolC<true>{});
+    } else if (pitch4 == 6400u) {
+        if (poly_ok <= 4) f(IntC<6400>{}, IntC<4>{}, BoolC<false>{});
+        else if (poly_ok <= 6) f(IntC<6400>{}, IntC<6>{}, BoolC<false>{});
+        else if (poly_ok <= 8) f(IntC<6400>{}, IntC<8>{}, BoolC<false>{});
+        else f(IntC<6400>{}, IntC<ECC_POLY_DEG>{}, BoolC<false>{});
+    } else {
+        if (poly_ok <= 6) f(IntC<0>{}, IntC<6>{}, BoolC<false>{});
+        else f(IntC<0>{}, IntC<ECC_POLY_DEG>{}, BoolC<false>{});
+    }
+}
+
+// Which exact loop a pair takes: f(REDUCE, PITCH4, view 0, view 1) is called once, with the copies that loop samples.
+// (The row-quad views are formed here, inside their branch: chosen inside the lambda, by a ternary or an if constexpr, they
+// changed pairs_kernel's and pairs_split_kernel's instructions.)
+template <class F>
+__device__ __forceinline__ void exact_loop_dispatch(const EccPairParams& p, bool reduce, unsigned pitch4, const SlabView sv0,
+                                                    const SlabView sv1, int iD0, int iD1, F&& f)
+{
+    if (reduce && p.quads) {
+        // kappa_max > pi/4: in practice the pairs whose baseline passes through the object (kappa_max = pi/2).  Their
+        // sampling curve crosses the whole Radon intermediate diagonally -- the 64 samples of a gather sit in ~17
+        // different angle rows, one cache line each in the row-major copies -- and on their own they are memory-bound
+        // (27.6 us per 1000 pairs against 8.5 us with the loads removed, scripts/exp_pair_classes.py).  In the row-quad
+        // copy four consecutive rows share a line: 11.3 us per 1000 such pairs.  OPT-IN (ECC_QUAD_COPIES=1, 4x the slab
+        // memory): inside the benchmark's mixed launch, where these are 3.5 % of the pairs, it buys 1 % (0.328 vs
+        // 0.331 ms) -- there they cost 5 % as their own wave time and 5 % by slowing everybody else down
+        // (scripts/exp_wave_timeline.py: a degree-8 wave takes 26.2 us next to them, 25.0 us without), whichever copy
+        // they sample.  Useful for per-sample / index-list workloads made of such pairs.
+        const SlabView q0 = {(GlobalBytes)p.quads[iD0], p.quad_group_bytes};
+        const SlabView q1 = {(GlobalBytes)p.quads[iD1], p.quad_group_bytes};
+        f(BoolC<true>{}, IntC<ECC_QUAD_LAYOUT>{}, q0, q1);
+    } else if (p.wide_offsets) {
+        f(BoolC<true>{}, IntC<-1>{}, sv0, sv1);
+    } else if (pitch4 == 6400u) {  // 768 distance bins, the reference's default (Gui/ComputeRadonIntermediate.hxx:43-44)
+        if (reduce) f(BoolC<true>{}, IntC<6400>{}, sv0, sv1);
+        else f(BoolC<false>{}, IntC<6400>{}, sv0, sv1);
+    } else {
+        f(BoolC<true>{}, IntC<0>{}, sv0, sv1);
+    }
+}
+
 // The sampling loops of ONE pair in one wave (ref: kernelEpipolarCosistency, ...RadonIntermediate.cu:214-276): the record's
 // polynomials where k01's fit was accepted, the exact per-sample path otherwise; per-lane float64 partial sums in acc
 // (CORR: the three moments).  iD0 / iD1: the pair's Radon intermediates (already read from the record by the caller).
@@ -1160,28 +1282,10 @@ __device__ __forceinline__ void pair_accumulate(const EccPairParams& p, const Ec
     int k_first = lane + 64 * sub;  // the lane's first sample of the exact loop
     if (poly_ok) {
         const float kappa_fit = ecc_kappa_fit(kappa_max), dkappa = uniformf(rec->K1[6]), w06 = uniformf(rec->K0[6]);
-#define ECC_POLY_LOOP_NC(P4, DEG, NC) \
-    k_first = kappa_loop_poly<DERIV, CORR, P4, DEG, WPP, NC>(lane, p.k_limit, rec, dkappa, kappa_max, kappa_fit, w06, sv0, sv1, n_alpha_f, n_t_f, pitch4_f, acc, mom2, mom3, mom4, sub, stage)
-#define ECC_POLY_LOOP(P4, DEG) ECC_POLY_LOOP_NC(P4, DEG, false)
-        if (p.wide_offsets) {
-            if (poly_ok <= 6) ECC_POLY_LOOP(-1, 6);
-            else ECC_POLY_LOOP(-1, ECC_POLY_DEG);
-        } else if (pitch4 == 6400u && in_range) {  // (the clamp-free loops exist for the default 768 distance bins only)
-            if (poly_ok <= 4) ECC_POLY_LOOP_NC(6400, 4, true);
-            else if (poly_ok <= 6) ECC_POLY_LOOP_NC(6400, 6, true);
-            else if (poly_ok <= 8) ECC_POLY_LOOP_NC(6400, 8, true);
-            else ECC_POLY_LOOP_NC(6400, ECC_POLY_DEG, true);
-        } else if (pitch4 == 6400u) {
-            if (poly_ok <= 4) ECC_POLY_LOOP(6400, 4);
-            else if (poly_ok <= 6) ECC_POLY_LOOP(6400, 6);
-            else if (poly_ok <= 8) ECC_POLY_LOOP(6400, 8);
-            else ECC_POLY_LOOP(6400, ECC_POLY_DEG);
-        } else {
-            if (poly_ok <= 6) ECC_POLY_LOOP(0, 6);
-            else ECC_POLY_LOOP(0, ECC_POLY_DEG);
-        }
-#undef ECC_POLY_LOOP
-#undef ECC_POLY_LOOP_NC
+        poly_loop_dispatch(p.wide_offsets != 0, pitch4, poly_ok, in_range, [&](auto P4, auto DEG, auto NOCL) {
+            k_first = kappa_loop_poly<DERIV, CORR, decltype(P4)::value, decltype(DEG)::value, WPP, decltype(NOCL)::value>(
+                lane, p.k_limit, rec, dkappa, kappa_max, kappa_fit, w06, sv0, sv1, n_alpha_f, n_t_f, pitch4_f, acc, mom2, mom3, mom4, sub, stage);
+        });
         if (!(kappa_fit < kappa_max)) return;  // wave-uniform: the polynomials covered the whole range (the normal case)
         // what follows is read from the record afterwards: nothing of the exact loop occupies a register during the loops above
         // (their scalar registers are the kernel's occupancy limit, pairs_kernel.hip)
@@ -1195,34 +1299,10 @@ __device__ __forceinline__ void pair_accumulate(const EccPairParams& p, const Ec
         K1[i] = uniformf(rec->K1[i]);
     }
     const float dist_scale = n_t_f / p.range_t, dist_bias = fmaf(0.5f, n_t_f, 0.5f);
-    if (reduce && p.quads) {
-        // kappa_max > pi/4: in practice the pairs whose baseline passes through the object (kappa_max = pi/2).  Their
-        // sampling curve crosses the whole Radon intermediate diagonally -- the 64 samples of a gather sit in ~17
-        // different angle rows, one cache line each in the row-major copies -- and on their own they are memory-bound
-        // (27.6 us per 1000 pairs against 8.5 us with the loads removed, scripts/exp_pair_classes.py).  In the row-quad
-        // copy four consecutive rows share a line: 11.3 us per 1000 such pairs.  OPT-IN (ECC_QUAD_COPIES=1, 4x the slab
-        // memory): inside the benchmark's mixed launch, where these are 3.5 % of the pairs, it buys 1 % (0.328 vs
-        // 0.331 ms) -- there they cost 5 % as their own wave time and 5 % by slowing everybody else down
-        // (scripts/exp_wave_timeline.py: a degree-8 wave takes 26.2 us next to them, 25.0 us without), whichever copy
-        // they sample.  Useful for per-sample / index-list workloads made of such pairs.
-        const SlabView q0 = {(GlobalBytes)p.quads[iD0], p.quad_group_bytes};
-        const SlabView q1 = {(GlobalBytes)p.quads[iD1], p.quad_group_bytes};
-        kappa_loop<DERIV, CORR, true, ECC_QUAD_LAYOUT, WPP>(k_first, p.k_limit, K0, K1, q0, q1, n_alpha_f, n_t_f, dist_scale, dist_bias,
-                                                       pitch4_f, acc, mom2, mom3, mom4, stage);
-    } else if (p.wide_offsets) {
-        kappa_loop<DERIV, CORR, true, -1, WPP>(k_first, p.k_limit, K0, K1, sv0, sv1, n_alpha_f, n_t_f, dist_scale, dist_bias,
-                                          pitch4_f, acc, mom2, mom3, mom4, stage);
-    } else if (pitch4 == 6400u) {  // 768 distance bins, the reference's default (Gui/ComputeRadonIntermediate.hxx:43-44)
-        if (reduce)
-            kappa_loop<DERIV, CORR, true, 6400, WPP>(k_first, p.k_limit, K0, K1, sv0, sv1, n_alpha_f, n_t_f, dist_scale,
-                                                dist_bias, pitch4_f, acc, mom2, mom3, mom4, stage);
-        else
-            kappa_loop<DERIV, CORR, false, 6400, WPP>(k_first, p.k_limit, K0, K1, sv0, sv1, n_alpha_f, n_t_f, dist_scale,
-                                                 dist_bias, pitch4_f, acc, mom2, mom3, mom4, stage);
-    } else {
-        kappa_loop<DERIV, CORR, true, 0, WPP>(k_first, p.k_limit, K0, K1, sv0, sv1, n_alpha_f, n_t_f, dist_scale, dist_bias,
-                                         pitch4_f, acc, mom2, mom3, mom4, stage);
-    }
+    exact_loop_dispatch(p, reduce, pitch4, sv0, sv1, iD0, iD1, [&](auto REDUCE, auto P4, const SlabView v0, const SlabView v1) {
+        kappa_loop<DERIV, CORR, decltype(REDUCE)::value, decltype(P4)::value, WPP>(k_first, p.k_limit, K0, K1, v0, v1, n_alpha_f, n_t_f, dist_scale,
+                                                                                 dist_bias, pitch4_f, acc, mom2, mom3, mom4, stage);
+    });
 }
 
 

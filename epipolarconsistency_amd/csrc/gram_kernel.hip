@@ -13,7 +13,8 @@
 //                                                                    terms in the same order, so one step per trip is enough here)
 //   exact loop         ((p_c * p_d + m_c * m_d) * K0[6]) * dkappa  (kappa_step)
 //   reference loop     the same expression on sample_line_plain's samples (reference_loop)
-// Only c <= d is computed.  The T = NC (NC + 1) / 2 columns are then summed by sum_gram_kernel in the order of ecc_sum_order.h.
+// Only c <= d is computed.  The T = NC (NC + 1) / 2 columns are then summed by sum_gram_kernel (sum_kernel.hip) in the order of
+// ecc_sum_order.h.
 #include <hip/hip_runtime.h>
 #include <float.h>
 
@@ -23,44 +24,6 @@
 namespace {
 
 constexpr int gram_entries(int nc) { return nc * (nc + 1) / 2; }
-
-// The cell, the fractions and the byte offset of sample_at (ecc_pairs_device.h) without its load: the same operations.
-struct GramTap {
-    unsigned off;
-    float fx, fy;
-};
-
-template <int PITCH4, bool NOCLAMP>
-__device__ __forceinline__ GramTap gram_tap_at(float xa, float yd, const SlabView sv, float n_t_f, float pitch4_f, float xa_max)
-{
-    GramTap t;
-    if (PITCH4 > 0) {
-        if (!NOCLAMP) yd = __builtin_amdgcn_fmed3f(yd, 0.5f, n_t_f);
-        if (!NOCLAMP) xa = __builtin_amdgcn_fmed3f(xa, 0.5f, xa_max);
-        const float ma = xa + 8388607.5f, md = yd + 8388607.5f;
-        t.fx = xa - (ma - 8388608.f);
-        t.fy = yd - (md - 8388608.f);
-        unsigned bin8;
-        asm("v_mul_u32_u24 %0, %1, 8" : "=v"(bin8) : "v"(__float_as_uint(md)));
-        t.off = __umul24(__float_as_uint(ma), (unsigned)PITCH4) + bin8;
-    } else {
-        yd = __builtin_amdgcn_fmed3f(yd, 0.f, n_t_f);
-        xa = __builtin_amdgcn_fmed3f(xa, 0.5f, xa_max);
-        t.fx = __builtin_amdgcn_fractf(xa);
-        t.fy = __builtin_amdgcn_fractf(yd);
-        t.off = footprint_offset<PITCH4>(xa - t.fx, yd - t.fy, sv.pitch4, pitch4_f);
-    }
-    return t;
-}
-
-// The one 16-byte load and the bilinear rule of sample_at (unsigned sample).
-__device__ __forceinline__ float gram_tap_value(GlobalBytes origin, const GramTap t)
-{
-    const ecc_v4f_a4 q4 = *(GlobalF4)(origin + t.off);
-    const float r0 = fmaf(t.fx, q4.y, q4.x);
-    const float r1 = fmaf(t.fx, q4.w, q4.z);
-    return fmaf(t.fy, r1 - r0, r0);
-}
 
 // acc[t] += term(c, d) for c <= d in the order of the columns
 template <int NC, class Term>
@@ -110,16 +73,16 @@ __device__ __forceinline__ int gram_loop_poly(int lane, int k_limit, const EccPa
         poly_pm<DEG>(cd[0], cd[0][ECC_POLY_DEG + 1], 0.f, true, x, z, yd0p, yd0m);
         poly_pm<DEG>(ca[1], ca[1][ECC_POLY_DEG + 1], ca[1][ECC_POLY_DEG + 2], false, x, z, xa1p, xa1m);
         poly_pm<DEG>(cd[1], cd[1][ECC_POLY_DEG + 1], 0.f, true, x, z, yd1p, yd1m);
-        const GramTap t0p = gram_tap_at<PITCH4, NOCLAMP>(xa0p, yd0p, sv0, n_t_f, pitch4_f, xa_max);
-        const GramTap t1p = gram_tap_at<PITCH4, NOCLAMP>(xa1p, yd1p, sv1, n_t_f, pitch4_f, xa_max);
-        const GramTap t0m = gram_tap_at<PITCH4, NOCLAMP>(xa0m, yd0m, sv0, n_t_f, pitch4_f, xa_max);
-        const GramTap t1m = gram_tap_at<PITCH4, NOCLAMP>(xa1m, yd1m, sv1, n_t_f, pitch4_f, xa_max);
+        const SampleTap t0p = sample_tap<PITCH4, NOCLAMP>(xa0p, yd0p, sv0, n_t_f, pitch4_f, xa_max);
+        const SampleTap t1p = sample_tap<PITCH4, NOCLAMP>(xa1p, yd1p, sv1, n_t_f, pitch4_f, xa_max);
+        const SampleTap t0m = sample_tap<PITCH4, NOCLAMP>(xa0m, yd0m, sv0, n_t_f, pitch4_f, xa_max);
+        const SampleTap t1m = sample_tap<PITCH4, NOCLAMP>(xa1m, yd1m, sv1, n_t_f, pitch4_f, xa_max);
         float vp[NC], vm[NC];
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             const GlobalBytes o0 = sv0.origin + chan * c, o1 = sv1.origin + chan * c;
-            const float v0p = gram_tap_value(o0, t0p), v1p = gram_tap_value(o1, t1p);
-            const float v0m = gram_tap_value(o0, t0m), v1m = gram_tap_value(o1, t1m);
+            const float v0p = sample_tap_value(o0, t0p), v1p = sample_tap_value(o1, t1p);
+            const float v0m = sample_tap_value(o0, t0m), v1m = sample_tap_value(o1, t1m);
             vp[c] = fmaf(v1p, rel_sign, v0p);
             vm[c] = fmaf(v1m, rel_sign, v0m);
         }
@@ -169,7 +132,8 @@ __device__ __forceinline__ void gram_loop_exact(int k_first, int k_limit, const 
     }
 }
 
-// pair_accumulate<DERIV, false> (ecc_pairs_device.h) for NC channels: the same choice of loop for the same record.
+// pair_accumulate<DERIV, false> (ecc_pairs_device.h) for NC channels: the same choice of loop for the same record, made by the same
+// helpers (poly_loop_dispatch, exact_loop_dispatch).
 template <bool DERIV, int NC>
 __device__ __forceinline__ void gram_accumulate(const EccPairParams& p, const EccGramParams& g, const EccPairRecord* __restrict__ rec,
                                                 int iD0, int iD1, int lane, double (&acc)[gram_entries(NC)])
@@ -189,28 +153,10 @@ __device__ __forceinline__ void gram_accumulate(const EccPairParams& p, const Ec
     int k_first = lane;
     if (poly_ok) {
         const float kappa_fit = ecc_kappa_fit(kappa_max), dkappa = uniformf(rec->K1[6]), w06 = uniformf(rec->K0[6]);
-#define ECC_GRAM_LOOP_NC(P4, DEG, NOCL) \
-    k_first = gram_loop_poly<DERIV, NC, P4, DEG, NOCL>(lane, p.k_limit, rec, dkappa, kappa_fit, w06, sv0, sv1, chan, n_alpha_f, n_t_f, pitch4_f, acc)
-#define ECC_GRAM_LOOP(P4, DEG) ECC_GRAM_LOOP_NC(P4, DEG, false)
-        if (p.wide_offsets) {
-            if (poly_ok <= 6) ECC_GRAM_LOOP(-1, 6);
-            else ECC_GRAM_LOOP(-1, ECC_POLY_DEG);
-        } else if (pitch4 == 6400u && in_range) {
-            if (poly_ok <= 4) ECC_GRAM_LOOP_NC(6400, 4, true);
-            else if (poly_ok <= 6) ECC_GRAM_LOOP_NC(6400, 6, true);
-            else if (poly_ok <= 8) ECC_GRAM_LOOP_NC(6400, 8, true);
-            else ECC_GRAM_LOOP_NC(6400, ECC_POLY_DEG, true);
-        } else if (pitch4 == 6400u) {
-            if (poly_ok <= 4) ECC_GRAM_LOOP(6400, 4);
-            else if (poly_ok <= 6) ECC_GRAM_LOOP(6400, 6);
-            else if (poly_ok <= 8) ECC_GRAM_LOOP(6400, 8);
-            else ECC_GRAM_LOOP(6400, ECC_POLY_DEG);
-        } else {
-            if (poly_ok <= 6) ECC_GRAM_LOOP(0, 6);
-            else ECC_GRAM_LOOP(0, ECC_POLY_DEG);
-        }
-#undef ECC_GRAM_LOOP
-#undef ECC_GRAM_LOOP_NC
+        poly_loop_dispatch(p.wide_offsets != 0, pitch4, poly_ok, in_range, [&](auto P4, auto DEG, auto NOCL) {
+            k_first = gram_loop_poly<DERIV, NC, decltype(P4)::value, decltype(DEG)::value, decltype(NOCL)::value>(
+                lane, p.k_limit, rec, dkappa, kappa_fit, w06, sv0, sv1, chan, n_alpha_f, n_t_f, pitch4_f, acc);
+        });
         if (!(kappa_fit < kappa_max)) return;  // wave-uniform: the polynomials covered the whole range (the normal case)
         asm volatile("" : "+s"(rec));  // what follows is read from the record afterwards (as in pair_accumulate)
     }
@@ -221,24 +167,14 @@ __device__ __forceinline__ void gram_accumulate(const EccPairParams& p, const Ec
         K1[i] = uniformf(rec->K1[i]);
     }
     const float dist_scale = n_t_f / p.range_t, dist_bias = fmaf(0.5f, n_t_f, 0.5f);
-    if (reduce && p.quads) {
-        const SlabView q0 = {(GlobalBytes)p.quads[iD0], p.quad_group_bytes};
-        const SlabView q1 = {(GlobalBytes)p.quads[iD1], p.quad_group_bytes};
-        gram_loop_exact<DERIV, NC, true, ECC_QUAD_LAYOUT>(k_first, p.k_limit, K0, K1, q0, q1, g.quad_channel_bytes, n_alpha_f, n_t_f,
-                                                          dist_scale, dist_bias, pitch4_f, acc);
-    } else if (p.wide_offsets) {
-        gram_loop_exact<DERIV, NC, true, -1>(k_first, p.k_limit, K0, K1, sv0, sv1, chan, n_alpha_f, n_t_f, dist_scale, dist_bias, pitch4_f, acc);
-    } else if (pitch4 == 6400u) {
-        if (reduce)
-            gram_loop_exact<DERIV, NC, true, 6400>(k_first, p.k_limit, K0, K1, sv0, sv1, chan, n_alpha_f, n_t_f, dist_scale, dist_bias, pitch4_f, acc);
-        else
-            gram_loop_exact<DERIV, NC, false, 6400>(k_first, p.k_limit, K0, K1, sv0, sv1, chan, n_alpha_f, n_t_f, dist_scale, dist_bias, pitch4_f, acc);
-    } else {
-        gram_loop_exact<DERIV, NC, true, 0>(k_first, p.k_limit, K0, K1, sv0, sv1, chan, n_alpha_f, n_t_f, dist_scale, dist_bias, pitch4_f, acc);
-    }
+    exact_loop_dispatch(p, reduce, pitch4, sv0, sv1, iD0, iD1, [&](auto REDUCE, auto P4, const SlabView v0, const SlabView v1) {
+        const long long chan_here = decltype(P4)::value == ECC_QUAD_LAYOUT ? g.quad_channel_bytes : chan;
+        gram_loop_exact<DERIV, NC, decltype(REDUCE)::value, decltype(P4)::value>(k_first, p.k_limit, K0, K1, v0, v1, chan_here, n_alpha_f, n_t_f,
+                                                                               dist_scale, dist_bias, pitch4_f, acc);
+    });
 }
 
-// One wave per pair, the workgroup -> pairs mapping of pairs_kernel (XCD-aware, the four waves a quarter of the range apart).
+// One wave per pair, on pairs_kernel's workgroup -> pairs mapping (main_pair_of_wave, ecc_pairs_device.h).
 // Registers: a kappa step has 4 NC gathers of 16 bytes in flight and the loop carries 2 T accumulator
 // registers, so the kernel does not run at pairs_kernel's seven waves per SIMD; tests/test_gram_abi.py pins what was planned.
 // (Measured and dropped: a scheduling barrier behind every channel, or every second one, of a step -- 4 or 8 gathers in flight
@@ -250,15 +186,10 @@ template <bool DERIV, int NC>
 __global__ __launch_bounds__(PK_MAIN_THREADS) void pairs_gram_kernel(EccPairParams p, EccGramParams g)
 {
     constexpr int T = gram_entries(NC);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long nblk = (p.count + PK_MAIN_WAVES - 1) / PK_MAIN_WAVES;
-    const long long per_xcd = (nblk + 7) / 8;
-    const long long blk = (long long)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
-    if (blk >= nblk) return;
-    long long local = (long long)wave * nblk + blk;
-    if (local >= p.count) return;  // no barriers below: waves leave independently
-    local = ((long long)__builtin_amdgcn_readfirstlane((int)(local >> 32)) << 32) |
-            (unsigned)__builtin_amdgcn_readfirstlane((int)local);
+    const int lane = threadIdx.x & 63;
+    long long local;
+    if (!main_pair_of_wave(p.count, local)) return;
+    local = uniform_index(local);
     const EccPairRecord* __restrict__ rec = p.records + local;
     const int iD0 = __builtin_amdgcn_readfirstlane(rec->iD0), iD1 = __builtin_amdgcn_readfirstlane(rec->iD1);
     double acc[T];
@@ -275,6 +206,7 @@ __global__ __launch_bounds__(PK_MAIN_THREADS) void pairs_gram_kernel(EccPairPara
 
 // ---- ECC_SAMPLING_REFERENCE -------------------------------------------------------------------------
 // sample_line_plain (ecc_pairs_device.h) in two halves: the line's sample position (once per line) ...
+// (kept apart: sharing changes pairs_kernel's code, see CHANGELOG)
 struct PlainTap {
     float a, d;
     bool moved;
@@ -353,6 +285,7 @@ __global__ __launch_bounds__(PK_THREADS) void pairs_gram_reference_kernel(EccPai
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     long long local = SPLIT == 1 ? (long long)blockIdx.x * 4 + wave : (long long)blockIdx.x;
     if (local >= p.count) return;  // SPLIT > 1: uniform over the workgroup
+    // the preamble of pairs_reference_kernel (kept apart: sharing changes pairs_kernel's code, see CHANGELOG)
     local = ((long long)__builtin_amdgcn_readfirstlane((int)(local >> 32)) << 32) |
             (unsigned)__builtin_amdgcn_readfirstlane((int)local);
     const EccPairRecord* __restrict__ rec = p.records + local;
@@ -396,34 +329,6 @@ __global__ __launch_bounds__(PK_THREADS) void pairs_gram_reference_kernel(EccPai
     }
 }
 
-// The T column sums in one launch: workgroup (slice, column) adds its slice of the column as sum_pairs_kernel /
-// sum_pairs_split_kernel do (ecc_sum_order.h) and stores the slice's sum; the host adds the slice sums to 0.0 in slice order.
-__global__ __launch_bounds__(ecc_sum::THREADS) void sum_gram_kernel(const float* __restrict__ values, long long col_stride, long long count,
-                                                                    int n_slices, double* __restrict__ partial)
-{
-    constexpr int TH = ecc_sum::THREADS;
-    __shared__ double s[ecc_sum::WAVES];
-    const float* __restrict__ vals = values + (long long)blockIdx.y * col_stride;
-    const long long n4 = count >> 2;
-    long long lo, hi;
-    ecc_sum::slice_bounds(n4, n_slices, blockIdx.x, &lo, &hi);
-    const float4* __restrict__ v4 = reinterpret_cast<const float4*>(vals);
-    ecc_sum::Acc4 a;
-    long long k = lo + threadIdx.x;
-    for (; k + 3 * TH < hi; k += 4 * TH) {
-        float4 v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) v[u] = v4[k + u * TH];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) ecc_sum::add(a, v[u]);
-    }
-    for (; k < hi; k += TH) ecc_sum::add(a, v4[k]);
-    double acc = ecc_sum::combine(a);
-    if ((int)blockIdx.x == n_slices - 1 && threadIdx.x == 0) ecc_sum::add_tail(acc, vals + (n4 << 2), n4, count);
-    ecc_sum::stage_wave_sums(acc, s);
-    if (threadIdx.x == 0) partial[(long long)blockIdx.y * ecc_sum::SLICES + blockIdx.x] = ecc_sum::waves_in_order(s);
-}
-
 template <int NC>
 hipError_t launch_gram_nc(const EccPairParams& p, const EccGramParams& g, hipStream_t stream)
 {
@@ -434,8 +339,7 @@ hipError_t launch_gram_nc(const EccPairParams& p, const EccGramParams& g, hipStr
             hipLaunchKernelGGL((pairs_gram_reference_kernel<NC, 1>), dim3((unsigned)((p.count + 3) / 4)), dim3(PK_THREADS), 0, stream, p, g);
         return hipGetLastError();
     }
-    const long long nblk = (p.count + PK_MAIN_WAVES - 1) / PK_MAIN_WAVES, per_xcd = (nblk + 7) / 8;
-    const dim3 grid((unsigned)(per_xcd * 8)), block(PK_MAIN_THREADS);
+    const dim3 grid = main_pairs_grid(p.count), block(PK_MAIN_THREADS);
     if (p.is_derivative) hipLaunchKernelGGL((pairs_gram_kernel<true, NC>), grid, block, 0, stream, p, g);
     else hipLaunchKernelGGL((pairs_gram_kernel<false, NC>), grid, block, 0, stream, p, g);
     return hipGetLastError();
@@ -456,14 +360,4 @@ extern "C" hipError_t ecc_launch_pairs_gram(const EccPairParams* p, const EccGra
     case 4: return launch_gram_nc<4>(*p, *g, stream);
     default: return hipErrorInvalidValue;
     }
-}
-
-// partial_d: n_columns x ecc_sum::SLICES doubles; entry [t][s] = sum of slice s of column t, s < n_slices (1 or ecc_sum::SLICES).
-extern "C" hipError_t ecc_launch_sum_gram(const float* values_d, long long col_stride, long long count, int n_columns, int n_slices,
-                                          double* partial_d, hipStream_t stream)
-{
-    if (count <= 0 || n_columns < 1 || (n_slices != 1 && n_slices != ecc_sum::SLICES)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(sum_gram_kernel, dim3((unsigned)n_slices, (unsigned)n_columns), dim3(ecc_sum::THREADS), 0, stream, values_d,
-                       col_stride, count, n_slices, partial_d);
-    return hipGetLastError();
 }

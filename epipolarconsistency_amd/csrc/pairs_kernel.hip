@@ -131,33 +131,10 @@ __global__ __launch_bounds__(256) void k01_patched_kernel(EccPairParams p, EccSm
 template <bool DERIV, bool CORR>
 __global__ __launch_bounds__(PK_MAIN_THREADS) PK_OCCUPANCY void pairs_kernel(EccPairParams p)
 {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    // Workgroup -> pairs.  XCD-aware: workgroups b and b+8 share an XCD, and an XCD walks a contiguous part of the
-    // pair order (consecutive pairs share view i and have neighbouring partners j: their dtr bands are re-used out
-    // of that XCD's L2).  The four waves of a workgroup, however, take pairs a quarter of the range apart: with four
-    // CONSECUTIVE pairs per workgroup the waves run in lockstep through nearly the same lines of view i, and the L1
-    // serialises hits on lines whose fill is still in flight (TCP_PENDING_STALL_CYCLES: a quarter of its busy time)
-    // -- 0.400 -> 0.335 ms for 79 800 pairs; spreading further (other strides, 2-D tiles of views that halve the HBM
-    // traffic) was slower, see DESIGN.md 4.2.
-    // (Several waves per pair for small shards -- wave h takes the kappa iterations it % split == h, float64 partial
-    // sums combined by the sum kernel -- were measured and dropped: a 9 975-pair shard 80 us per step with whole-pair
-    // waves, 89 us with two, 106 us with four waves per pair.)
-    // (A host-made launch schedule that gives the kappa_max = pi/2 pairs evenly spaced positions, everything else keeping
-    // its order: with explicit index lists over all 79 800 pairs it looked promising -- natural order 0.361 ms, those
-    // pairs first 0.460, last 0.422, as whole workgroups first 0.601, spread evenly 0.348, scripts/exp_heavy_first.py --
-    // but built into this mapping it was 1.5 % SLOWER, 0.3365 vs 0.3315 ms: the four-quarters mapping already spreads
-    // them over the first quarter of every workgroup.)
-    // (Persistent waves -- a launch sized to be resident at once, every wave handling several pairs in turn -- were
-    // measured too: 79 800 pairs 0.38 / 0.43 ms with 5 / 10 pairs per wave against 0.33 ms, the shard 86 us with two.)
-    const long long nblk = (p.count + PK_MAIN_WAVES - 1) / PK_MAIN_WAVES;
-    const long long per_xcd = (nblk + 7) / 8;
-    const long long blk = (long long)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
-    if (blk >= nblk) return;
-    long long local = (long long)wave * nblk + blk;
-    if (local >= p.count) return;  // no barriers below: waves leave independently
-    // wave-uniform record -> SGPRs (readfirstlane makes the address provably uniform: scalar loads)
-    local = ((long long)__builtin_amdgcn_readfirstlane((int)(local >> 32)) << 32) |
-            (unsigned)__builtin_amdgcn_readfirstlane((int)local);
+    const int lane = threadIdx.x & 63;
+    long long local;
+    if (!main_pair_of_wave(p.count, local)) return;
+    local = uniform_index(local);  // wave-uniform record -> SGPRs
     // a list launch over records kept in their slots of an all-pairs array (record reuse): the slot comes from the list
     const long long rec_index = p.record_slots ? (long long)__builtin_amdgcn_readfirstlane(p.record_slots[local]) : local;
     const EccPairRecord* __restrict__ rec = p.records + rec_index;
@@ -196,7 +173,7 @@ __global__ __launch_bounds__(WPP > 4 ? 64 * WPP : PK_THREADS) void pairs_split_k
     const int slot = wave / WPP, sub = wave % WPP;  // wave-uniform
     long long local = (long long)blockIdx.x * PPW + slot;
     const bool live = local < p.count;
-    local = ((long long)__builtin_amdgcn_readfirstlane((int)(local >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)local);
+    local = uniform_index(local);
     double acc = 0.0, m2 = 0.0, m3 = 0.0, m4 = 0.0;
     const EccPairRecord* __restrict__ rec = nullptr;
     float* stage = stage_all + (size_t)slot * stage_stride;
@@ -423,16 +400,26 @@ extern "C" hipError_t ecc_launch_build_paired(const float* const* slabs_tbl_d, f
     return hipGetLastError();
 }
 
+namespace {
+// The form of a k01 launch from its size: launch(LANES, grid) is called once, LANES (a std::integral_constant) the threads per fit
+// and grid the workgroups of 64 / LANES pairs.  Small launches: ECC_K01_SMALL_LANES or 8 lanes per fit (the kernel's time is
+// one thread's chain there); the records are identical.
+template <class Launch>
+void k01_launch_form(long long count, Launch&& launch)
+{
+    const auto grid = [count](int lanes) { return dim3((unsigned)((count + 64 / lanes - 1) / (64 / lanes))); };
+    if (count <= ECC_K01_LANES16_MAX_PAIRS) launch(IntC<ECC_K01_SMALL_LANES>{}, grid(ECC_K01_SMALL_LANES));
+    else if (count <= ECC_K01_WIDE_MAX_PAIRS) launch(IntC<8>{}, grid(8));
+    else launch(IntC<1>{}, grid(1));
+}
+}  // namespace
+
 extern "C" hipError_t ecc_launch_k01(const EccPairParams* p, hipStream_t stream)
 {
     if (p->count <= 0) return hipSuccess;
-    // small launches: 8 lanes per fit (the kernel's time is one thread's chain there); the records are identical
-    if (p->count <= ECC_K01_LANES16_MAX_PAIRS) {
-        constexpr int per_wg = 64 / ECC_K01_SMALL_LANES;
-        hipLaunchKernelGGL(k01_kernel<ECC_K01_SMALL_LANES>, dim3((unsigned)((p->count + per_wg - 1) / per_wg)), dim3(256), 0, stream, *p);
-    } else if (p->count <= ECC_K01_WIDE_MAX_PAIRS)
-        hipLaunchKernelGGL(k01_kernel<8>, dim3((unsigned)((p->count + 7) / 8)), dim3(256), 0, stream, *p);
-    else hipLaunchKernelGGL(k01_kernel<1>, dim3((unsigned)((p->count + 63) / 64)), dim3(256), 0, stream, *p);
+    k01_launch_form(p->count, [&](auto LANES, dim3 grid) {
+        hipLaunchKernelGGL(k01_kernel<decltype(LANES)::value>, grid, dim3(256), 0, stream, *p);
+    });
     return hipGetLastError();
 }
 
@@ -442,13 +429,9 @@ extern "C" hipError_t ecc_launch_k01_radii(const EccPairParams* p, const float* 
 {
     if (p->count <= 0) return hipSuccess;
     if (!radii_d || period < 1) return hipErrorInvalidValue;
-    if (p->count <= ECC_K01_LANES16_MAX_PAIRS) {
-        constexpr int per_wg = 64 / ECC_K01_SMALL_LANES;
-        hipLaunchKernelGGL(k01_radii_kernel<ECC_K01_SMALL_LANES>, dim3((unsigned)((p->count + per_wg - 1) / per_wg)), dim3(256), 0, stream, *p,
-                           radii_d, period);
-    } else if (p->count <= ECC_K01_WIDE_MAX_PAIRS)
-        hipLaunchKernelGGL(k01_radii_kernel<8>, dim3((unsigned)((p->count + 7) / 8)), dim3(256), 0, stream, *p, radii_d, period);
-    else hipLaunchKernelGGL(k01_radii_kernel<1>, dim3((unsigned)((p->count + 63) / 64)), dim3(256), 0, stream, *p, radii_d, period);
+    k01_launch_form(p->count, [&](auto LANES, dim3 grid) {
+        hipLaunchKernelGGL(k01_radii_kernel<decltype(LANES)::value>, grid, dim3(256), 0, stream, *p, radii_d, period);
+    });
     return hipGetLastError();
 }
 
@@ -459,11 +442,10 @@ extern "C" hipError_t ecc_launch_k01_patched(const EccPairParams* p, const EccSm
     if (p->count > ECC_K01_WIDE_MAX_PAIRS || p->patch_count || x->patch_count < 0 || x->patch_count > ECC_SMALL_PATCH_MAX) return hipErrorInvalidValue;
     EccSmallEval xx = *x;
     xx.magic = ECC_SMALL_MAGIC;
-    if (p->count <= ECC_K01_LANES16_MAX_PAIRS) {
-        constexpr int per_wg = 64 / ECC_K01_SMALL_LANES;
-        hipLaunchKernelGGL(k01_patched_kernel<ECC_K01_SMALL_LANES>, dim3((unsigned)((p->count + per_wg - 1) / per_wg)), dim3(256), 0, stream, *p, xx);
-    } else
-        hipLaunchKernelGGL(k01_patched_kernel<8>, dim3((unsigned)((p->count + 7) / 8)), dim3(256), 0, stream, *p, xx);
+    k01_launch_form(p->count, [&](auto LANES, dim3 grid) {
+        // (no one-lane form of this kernel: the count was checked above)
+        if constexpr (decltype(LANES)::value > 1) hipLaunchKernelGGL(k01_patched_kernel<decltype(LANES)::value>, grid, dim3(256), 0, stream, *p, xx);
+    });
     return hipGetLastError();
 }
 
@@ -471,7 +453,7 @@ extern "C" hipError_t ecc_launch_k01_patched(const EccPairParams* p, const EccSm
 extern "C" hipError_t ecc_launch_pairs(const EccPairParams* p, hipStream_t stream)
 {
     if (p->count <= 0) return hipSuccess;
-    long long nblk = (p->count + 3) / 4;
+    const long long nblk = (p->count + 3) / 4;  // the reference kernel with one wave per pair
     if (p->reference_arithmetic) {
         const int stride = (p->k_limit + 63) & ~63;
         const size_t wide_lds = sizeof(float) * (size_t)stride * (p->use_corr ? 3u : 1u);
@@ -514,9 +496,7 @@ extern "C" hipError_t ecc_launch_pairs(const EccPairParams* p, hipStream_t strea
             return hipGetLastError();
         }
     }
-    nblk = (p->count + PK_MAIN_WAVES - 1) / PK_MAIN_WAVES;
-    long long per_xcd = (nblk + 7) / 8;
-    dim3 grid((unsigned)(per_xcd * 8)), block(PK_MAIN_THREADS);
+    const dim3 grid = main_pairs_grid(p->count), block(PK_MAIN_THREADS);
     if (p->use_corr) {
         if (p->is_derivative)
             hipLaunchKernelGGL((pairs_kernel<true, true>), grid, block, 0, stream, *p);

@@ -1,6 +1,7 @@
 // sum_kernel.hip -- the float64 total of the pair values of an evaluation (gfx950): one workgroup, or ecc_sum::SLICES of them
-// inside one launch from ecc_sum::SPLIT_MIN_COUNT values on.  The order of the additions is ecc_sum_order.h's; what is
-// written here is how the values are fetched and how the result reaches its reader.
+// inside one launch from ecc_sum::SPLIT_MIN_COUNT values on; and the column sums of the Gram form (sum_gram_kernel).  The order
+// of the additions is ecc_sum_order.h's; what is written here is how the values are fetched and how the result reaches its
+// reader.
 #include <hip/hip_runtime.h>
 
 #include "ecc_sum_order.h"
@@ -117,6 +118,36 @@ __global__ __launch_bounds__(ecc_sum::THREADS) void sum_pairs_split_kernel(const
     }
 }
 
+// The T column sums of ecc_metric_evaluate_gram (gram_kernel.hip) in one launch: workgroup (slice, column) adds its slice of the
+// column as sum_pairs_kernel / sum_pairs_split_kernel do (ecc_sum_order.h) and stores the slice's sum; the host adds the slice
+// sums to 0.0 in slice order.  The slice loop is sum_pairs_split_kernel's, statement by statement
+// (kept apart: sharing changes sum_pairs_split_kernel's code, see CHANGELOG).
+__global__ __launch_bounds__(ecc_sum::THREADS) void sum_gram_kernel(const float* __restrict__ values, long long col_stride, long long count,
+                                                                    int n_slices, double* __restrict__ partial)
+{
+    constexpr int TH = ecc_sum::THREADS;
+    __shared__ double s[ecc_sum::WAVES];
+    const float* __restrict__ vals = values + (long long)blockIdx.y * col_stride;
+    const long long n4 = count >> 2;
+    long long lo, hi;
+    ecc_sum::slice_bounds(n4, n_slices, blockIdx.x, &lo, &hi);
+    const float4* __restrict__ v4 = reinterpret_cast<const float4*>(vals);
+    ecc_sum::Acc4 a;
+    long long k = lo + threadIdx.x;
+    for (; k + 3 * TH < hi; k += 4 * TH) {
+        float4 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = v4[k + u * TH];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) ecc_sum::add(a, v[u]);
+    }
+    for (; k < hi; k += TH) ecc_sum::add(a, v4[k]);
+    double acc = ecc_sum::combine(a);
+    if ((int)blockIdx.x == n_slices - 1 && threadIdx.x == 0) ecc_sum::add_tail(acc, vals + (n4 << 2), n4, count);
+    ecc_sum::stage_wave_sums(acc, s);
+    if (threadIdx.x == 0) partial[(long long)blockIdx.y * ecc_sum::SLICES + blockIdx.x] = ecc_sum::waves_in_order(s);
+}
+
 // One double from device memory into a pinned, device-mapped host slot (system-scope store): how a value that a
 // collective left on the device (the all-reduced sum of a sharded evaluation) reaches a polling host without a copy command.
 __global__ void publish_scalar_kernel(const double* __restrict__ value, double* __restrict__ host_slot)
@@ -150,5 +181,15 @@ extern "C" hipError_t ecc_launch_sum_pairs(const float* vals, long long count, d
                            static_cast<SumScratch*>(scratch));
     else
         hipLaunchKernelGGL(sum_pairs_kernel, dim3(1), dim3(ecc_sum::THREADS), 0, stream, vals, count, out, (float*)nullptr);
+    return hipGetLastError();
+}
+
+// partial_d: n_columns x ecc_sum::SLICES doubles; entry [t][s] = sum of slice s of column t, s < n_slices (1 or ecc_sum::SLICES).
+extern "C" hipError_t ecc_launch_sum_gram(const float* values_d, long long col_stride, long long count, int n_columns, int n_slices,
+                                          double* partial_d, hipStream_t stream)
+{
+    if (count <= 0 || n_columns < 1 || (n_slices != 1 && n_slices != ecc_sum::SLICES)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sum_gram_kernel, dim3((unsigned)n_slices, (unsigned)n_columns), dim3(ecc_sum::THREADS), 0, stream, values_d,
+                       col_stride, count, n_slices, partial_d);
     return hipGetLastError();
 }

@@ -106,6 +106,83 @@ def test_diagonal_bits_in_other_states(gpu_ctx, setup):
         d.close()
 
 
+# ---- the loops of the production grids (csrc/ecc_pairs_device.h: poly_loop_dispatch, exact_loop_dispatch) --------------------
+KAPPA_FIT_MAX = float(np.float32(0.98))   # csrc/ecc_layout.h: ecc_kappa_fit
+
+
+def _catalog_scan(gpu_ctx, name, n, K, n_alpha, n_t, seed=5):
+    """n views of tests/geometry_catalog.py and K * n DIFFERENT random-normal intermediates of n_alpha x n_t bins."""
+    import epipolarconsistency_amd as E
+    import geometry_catalog
+    rng = np.random.default_rng(seed)
+    Ps, n_u, n_v = geometry_catalog.make(name, n)
+    dtrs = [E.RadonIntermediate.from_host(gpu_ctx, rng.standard_normal((n_t, n_alpha), dtype=np.float32), n_u, n_v) for _ in range(K * n)]
+    return Ps, dtrs
+
+
+def _pair_classes(gpu_ctx, Ps, dtrs, radius):
+    """The classes of the scan's pairs, from the records of a single-channel metric (as tests/test_gpu_geometry_parity.py reads them)."""
+    import epipolarconsistency_amd as E
+    n = len(Ps)
+    n_pairs = n * (n - 1) // 2
+    m = E.MetricRadonIntermediate(gpu_ctx, Ps, dtrs[:n]).setSampling("polynomial")
+    m.setObjectRadius(radius)
+    recs = m.debug_polynomials(0, n_pairs)
+    kmax = m.debug_K01(0, n_pairs)[:, 15]
+    m.close()
+    ok = np.array([r["poly_ok"] for r in recs])
+    free = np.array([r["clamp_free"] for r in recs])
+    live = kmax > 0
+    return dict(clamp_free=int((ok & free).sum()), clamped=int((ok & ~free).sum()), refused=int((~ok & live).sum()),
+                partial=int((ok & (kmax > KAPPA_FIT_MAX)).sum()), above=int((kmax > np.pi / 4).sum()),
+                below=int((live & (kmax <= np.pi / 4)).sum()))
+
+
+# Geometry, views and object radius (mm; 0: automatic) of the two grids, chosen so that the asserted classes occur with room to
+# spare.  16 views of the near-opposite orbit (source at 740 mm) and a 185-mm object: neighbouring views have short ranges in the
+# middle of the detector (clamp-free); most others reach the detector's edge (clamped); views seven steps apart (157.5 deg) have their
+# baseline 144 mm from the centre, inside the object, so kappa_max = pi/2 and the fit ends at 0.98 before the range does (partial);
+# views eight steps apart face each other, the baseline passes within millimetres of the centre and no fit is accepted (refused).
+GRID_768 = ("near_opposite", 16, 185.0)
+GRID_WIDE = ("angulated", 4, 0.0)
+
+
+@pytest.mark.parametrize("mode,quads", [("polynomial", False), ("per_sample", False), ("polynomial", True)])
+def test_diagonal_bits_on_the_default_grid(gpu_ctx, mode, quads):
+    """768 x 768 bins (row pitch 6400 bytes): the clamp-free and the clamped polynomial loops of that pitch, the exact loops with and
+    without the pi/4 reduction and, with row-quad copies, the row-quad loop in the exact tails -- each reached by at least one pair."""
+    name, n, radius = GRID_768
+    K = 2
+    gpu_ctx.setQuadCopies("on" if quads else "off")
+    try:
+        Ps, dtrs = _catalog_scan(gpu_ctx, name, n, K, 768, 768)
+        cls = _pair_classes(gpu_ctx, Ps, dtrs, radius)
+        print("classes of %s, %d views, radius %.0f mm at 768 x 768:" % (name, n, radius), cls)
+        if mode == "polynomial":
+            assert cls["clamp_free"] > 0 and cls["clamped"] > 0 and cls["refused"] > 0 and cls["partial"] > 0, cls
+        else:
+            assert cls["above"] > 0 and cls["below"] > 0, cls
+        _check_diagonal(gpu_ctx, Ps, dtrs, K, lambda m: m.setSampling(mode).setObjectRadius(radius))
+    finally:
+        gpu_ctx.setQuadCopies("auto")
+    for d in dtrs:
+        d.close()
+
+
+@pytest.mark.parametrize("mode", ["polynomial", "per_sample"])
+def test_diagonal_bits_on_the_first_wide_offset_grid(gpu_ctx, mode):
+    """2621 x 768 bins: the first grid whose copies need integer offsets (tests/test_gpu_geometry_parity.py); 8 slabs of 8 MB."""
+    name, n, radius = GRID_WIDE
+    K = 2
+    Ps, dtrs = _catalog_scan(gpu_ctx, name, n, K, 2621, 768)
+    cls = _pair_classes(gpu_ctx, Ps, dtrs, radius)
+    print("classes of %s, %d views, radius %.0f mm at 2621 x 768:" % (name, n, radius), cls)
+    assert cls["clamp_free"] + cls["clamped"] > 0, cls
+    _check_diagonal(gpu_ctx, Ps, dtrs, K, lambda m: m.setSampling(mode).setObjectRadius(radius))
+    for d in dtrs:
+        d.close()
+
+
 def test_one_channel_is_evaluate(gpu_ctx):
     import epipolarconsistency_amd as E
     for n, mode in ((8, "auto"), (64, "polynomial")):
