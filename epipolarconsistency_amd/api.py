@@ -711,6 +711,28 @@ class MetricRadonIntermediate:
                                                   C.c_void_p(G.ctypes.data) if G.size else None))
         return (G, pairs) if want_pairs else G
 
+    def evaluate_view_coefficients(self, coeffs, want_pairs=False):
+        """ecc_metric_evaluate_view_coefficients: the metric at per-view channel coefficients and its gradient.  coeffs: (K, n) --
+        a[c, i] multiplies channel c of view i; the metric holds K * n Radon intermediates, channel-major, computed with
+        POST_IDENTITY, as for evaluate_gram; the coefficients are passed as float32.  Returns (value, grad), grad (K, n) float64 =
+        d value / d a -- with want_pairs (value, grad, pairs), pairs (n_pairs, 1 + 2 K) float32 in the pair order of evaluate(cost):
+        per pair i < j its value, then h0[c] = 1/2 d (pair value) / d a[c, i] and h1[c] = 1/2 d (pair value) / d a[c, j].  The metric
+        is a quadratic form of a, so grad is linear in a and the same call at a direction v returns the Hessian-vector product
+        (minimize_view_coefficients).  The current matrices and everything the metric keeps stay."""
+        a = np.ascontiguousarray(coeffs, np.float32)
+        if a.ndim != 2:
+            raise ValueError("coeffs must be (n_channels, n_views)")
+        K, n = a.shape
+        if self._Ps is not None and n != len(self._Ps):
+            raise ValueError("coeffs must be (n_channels, n_views)")
+        value = C.c_double(0.0)
+        grad = np.zeros((K, n), np.float64)
+        pairs = np.zeros((n * (n - 1) // 2, 1 + 2 * K), np.float32) if want_pairs else None
+        check(_lib.lib().ecc_metric_evaluate_view_coefficients(self._h, K, C.c_void_p(a.ctypes.data) if a.size else None, C.byref(value),
+                                                               C.c_void_p(grad.ctypes.data) if grad.size else None,
+                                                               C.c_void_p(pairs.ctypes.data) if (want_pairs and pairs.size) else None))
+        return (value.value, grad, pairs) if want_pairs else (value.value, grad)
+
     def evaluate_transforms(self, n_source, Ts, want_pairs=False):
         """ecc_metric_evaluate_transforms: the registration of two scans (ref: tools/Registration/Registration3D3D.hxx).  The
         current matrices are the base, views [0, n_source) the source scan, the rest the target scan; Ts: anything np.asarray
@@ -1224,3 +1246,51 @@ def gram_minimizer(G, fixed=0, value=1.0):
         np.linalg.cholesky(H)  # raises LinAlgError unless positive definite
         a[free] = np.linalg.solve(H, -float(value) * 0.5 * (G[free, fixed] + G[fixed, free]))
     return a, gram_value(G, a)
+
+
+def minimize_view_coefficients(metric, K, start, free, tol=1e-4, max_iter=None):
+    """Conjugate gradients on the host over per-view channel coefficients (MetricRadonIntermediate.evaluate_view_coefficients).
+    start: (K, n) coefficients; free: (K, n) boolean mask of the coefficients to minimise over, the others stay at `start`.  The
+    metric is the quadratic form a^T G a, so with the free coordinates x (a = start + P x) the system is H x = -g0, H = the free
+    block of 2 G, g0 = the free gradient at `start`; every product H p is ONE call of evaluate_view_coefficients at the direction
+    P p (the gradient of a quadratic form is linear).  Returns (a, value, iterations) once |free gradient|_inf <= tol * |g0|_inf (the
+    recurrence's residual; iterations = operator products); a is (K, n) float64 and the value is the metric's at a (rounded to
+    float32 by the call).  Raises numpy.linalg.LinAlgError when a direction has p . H p <= 0 -- the form has no minimum over the
+    free coordinates -- and RuntimeError when max_iter (default: twice the number of free coefficients plus ten) products did not
+    reach the tolerance.  `metric` needs evaluate_view_coefficients only."""
+    a = np.array(start, np.float64)
+    mask = np.asarray(free, bool)
+    if a.ndim != 2 or a.shape[0] != int(K) or mask.shape != a.shape:
+        raise ValueError("start and free must be (K, n_views)")
+    n_free = int(mask.sum())
+    if max_iter is None:
+        max_iter = 2 * n_free + 10
+
+    def gradient(coeffs):
+        value, grad = metric.evaluate_view_coefficients(coeffs)[:2]
+        return float(value), np.asarray(grad, np.float64)[mask]
+    value, g0 = gradient(a)
+    scale = float(np.max(np.abs(g0))) if n_free else 0.0
+    iterations = 0
+    if scale == 0.0:
+        return a, value, iterations
+    r = -g0
+    p = r.copy()
+    rr = float(r @ r)
+    direction = np.zeros_like(a)
+    while np.max(np.abs(r)) > tol * scale:
+        if iterations >= max_iter:
+            raise RuntimeError("minimize_view_coefficients: %d products did not reach the tolerance" % iterations)
+        direction[mask] = p
+        Hp = gradient(direction)[1]
+        iterations += 1
+        pHp = float(p @ Hp)
+        if not pHp > 0.0:
+            raise np.linalg.LinAlgError("the metric has no minimum over the free coefficients: a direction with p . H p <= 0")
+        alpha = rr / pHp
+        a[mask] += alpha * p
+        r -= alpha * Hp
+        rr_new = float(r @ r)
+        p = r + (rr_new / rr) * p
+        rr = rr_new
+    return a, metric.evaluate_view_coefficients(a)[0], iterations

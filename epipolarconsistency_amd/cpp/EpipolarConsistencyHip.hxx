@@ -815,6 +815,28 @@ public:
         detail::check(ecc_metric_evaluate_gram(m_h, n_channels, pair_grams ? pair_grams->data() : 0x0, G.data()));
     }
 
+    /// Not in the reference: ecc_metric_evaluate_view_coefficients -- the metric at PER-VIEW channel coefficients (corrected
+    /// intermediate of view i = sum_c a_c,i D_c,i: a gain, an offset or a scatter scale per view) and its gradient by all of them.
+    /// Intermediates as for evaluateGram; coeffs: n_channels x n_views, coeffs[c * n_views + i] = a_c,i.  grad (nullable):
+    /// d value / d a_c,i in the same order; pair_terms (nullable): n_pairs x (1 + 2 n_channels) floats, pair-major, per pair i < j
+    /// {value, h0[c] = 1/2 d pair / d a_c,i, h1[c] = 1/2 d pair / d a_c,j}.  The metric is quadratic in a: the same call at a
+    /// direction returns the Hessian-vector product (ecc_hip.h).  Single device only.
+    double evaluateViewCoefficients(int n_channels, const std::vector<float>& coeffs, std::vector<double>* grad = 0x0,
+                                    std::vector<float>* pair_terms = 0x0)
+    {
+        if (m_gh) throw std::runtime_error("evaluateViewCoefficients: not available on a device group");
+        if (n_channels < 1 || n_channels > ECC_VIEW_COEFF_MAX_CHANNELS)
+            throw std::runtime_error("evaluateViewCoefficients: n_channels outside [1, ECC_VIEW_COEFF_MAX_CHANNELS]");
+        const size_t n = Ps.size();
+        if (coeffs.size() != (size_t)n_channels * n) throw std::runtime_error("evaluateViewCoefficients: one coefficient per channel and view");
+        if (grad) grad->assign(coeffs.size(), 0.0);
+        if (pair_terms) pair_terms->assign(n * (n > 0 ? n - 1 : 0) / 2 * (size_t)(1 + 2 * n_channels), 0.f);
+        double value = 0.0;
+        detail::check(ecc_metric_evaluate_view_coefficients(m_h, n_channels, coeffs.data(), &value, grad ? grad->data() : 0x0,
+                                                            pair_terms ? pair_terms->data() : 0x0));
+        return value;
+    }
+
     /// The metric borrows the dtrs: "DO NOT delete or change _dtrs during lifetime" (ref: .h:45).
     MetricRadonIntermediate& setRadonIntermediates(const std::vector<RadonIntermediate*>& _dtrs)
     {

@@ -388,6 +388,10 @@ struct ecc_metric {
     DeviceArray<EccPairRecord> gram_records_d;
     DeviceArray<float> gram_values_d;
     DeviceArray<double> gram_partial_d;
+    // ecc_metric_evaluate_view_coefficients (ecc_view_coeff.hip) shares the three arrays above and adds the coefficients on the
+    // device and the per-(view, channel) sums of the gradient terms, K * n_views each
+    DeviceArray<float> coeff_d;
+    DeviceArray<double> coeff_sums_d;
     // ecc_metric_evaluate_transforms (ecc_transforms.hip) uses the scratch above (pose_lists_d: its value slots) and, under the
     // automatic object radius, one float per transform of a batch
     DeviceArray<float> transform_radii_d;

@@ -243,6 +243,17 @@ struct EccGramParams {
     int64_t col_stride;
 };
 
+// ---- the metric at per-view channel coefficients and its gradient terms (view_coeff_kernel.hip) ----
+// The same channel-major intermediates and copies.  1 + 2 K entries per pair i < j -- the value, h0[0 .. K) = 1/2 d value / d a_c,i,
+// h1[0 .. K) = 1/2 d value / d a_c,j -- stored COLUMN-major like the Gram form's entries.
+struct EccViewCoeffParams {
+    int64_t paired_channel_bytes;  // as in EccGramParams
+    int64_t quad_channel_bytes;
+    float* values;                 // 1 + 2 K columns of col_stride floats
+    int64_t col_stride;
+    const float* coeffs;           // K * n_views floats on the device: a[c * n_views + i]
+};
+
 // ---- projection pre-processing ------------------------------------------------
 #define ECC_PRE_MAX_CHUNKS 32  // workgroups per image of the maximum search in front of PreProccess::process (normalize)
 struct EccPreprocessParams {

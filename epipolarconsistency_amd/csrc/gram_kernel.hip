@@ -205,39 +205,6 @@ __global__ __launch_bounds__(PK_MAIN_THREADS) void pairs_gram_kernel(EccPairPara
 }
 
 // ---- ECC_SAMPLING_REFERENCE -------------------------------------------------------------------------
-// sample_line_plain (ecc_pairs_device.h) in two halves: the line's sample position (once per line) ...
-// (kept apart: sharing changes pairs_kernel's code, see CHANGELOG)
-struct PlainTap {
-    float a, d;
-    bool moved;
-};
-
-__device__ __forceinline__ PlainTap plain_line_tap(const float* K, float x0, float x1, float range_t)
-{
-    const float Pi = 3.14159265359f;
-    float l0 = K[0] * x0 + K[3] * x1;
-    float l1 = K[1] * x0 + K[4] * x1;
-    float l2 = K[2] * x0 + K[5] * x1;
-    const float length = sqrtf(l0 * l0 + l1 * l1);
-    float a = (float)atan2((double)l1, (double)l0) / Pi;
-    if (a < 0) a += 2;
-    float d = -(l2 / length) / range_t + 0.5f;
-    bool moved = false;
-    if (a > 1) {
-        a = a - 1.f;
-        d = 1.f - d;
-        moved = true;
-    }
-    return {a, d, moved};
-}
-
-// ... and the clamped bilinear sample of one channel's slab there.
-__device__ __forceinline__ float plain_tap_value(const PlainTap t, GlobalFloats slab, int pitch, int n_alpha, int n_t, bool derivative)
-{
-    const float v = slab_tex2d_norm(slab, pitch, n_alpha, n_t, t.a, t.d);
-    return (derivative && t.moved) ? -v : v;
-}
-
 // reference_loop<false> for NC channels: the samples first_k, first_k + stride, ... of one pair.
 template <int NC>
 __device__ __forceinline__ void gram_reference_loop(const EccPairParams& p, const float (&K0)[8], const float (&K1)[8],

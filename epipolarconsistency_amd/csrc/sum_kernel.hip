@@ -1,5 +1,6 @@
 // sum_kernel.hip -- the float64 total of the pair values of an evaluation (gfx950): one workgroup, or ecc_sum::SLICES of them
-// inside one launch from ecc_sum::SPLIT_MIN_COUNT values on; and the column sums of the Gram form (sum_gram_kernel).  The order
+// inside one launch from ecc_sum::SPLIT_MIN_COUNT values on; the column sums of the Gram form (sum_gram_kernel) and the per-view sums of
+// the view-coefficient gradient (sum_view_terms_kernel).  The order
 // of the additions is ecc_sum_order.h's; what is written here is how the values are fetched and how the result reaches its
 // reader.
 #include <hip/hip_runtime.h>
@@ -148,6 +149,30 @@ __global__ __launch_bounds__(ecc_sum::THREADS) void sum_gram_kernel(const float*
     if (threadIdx.x == 0) partial[(long long)blockIdx.y * ecc_sum::SLICES + blockIdx.x] = ecc_sum::waves_in_order(s);
 }
 
+// The gradient sums of ecc_metric_evaluate_view_coefficients (view_coeff_kernel.hip): workgroup (view v, channel c) adds the n - 1
+// terms of the pairs that contain v -- column 1 + c (h0) of the pair (v, w) where v is the smaller index, column 1 + K + c (h1) of
+// the pair (w, v) where it is the larger.  THE order, for every reader of these sums: the partners w = 0 .. n - 1 without v in
+// ascending order are terms u = 0 .. n - 2; thread t adds its terms u = t, t + THREADS, ... in float64 to 0.0; the 64 threads of a
+// wave are combined by ecc_sum::wave_sum's tree and the wave sums added to 0.0 in wave order (stage_wave_sums, waves_in_order).
+// No atomics: the same bits on every run.
+__global__ __launch_bounds__(ecc_sum::THREADS) void sum_view_terms_kernel(const float* __restrict__ values, long long col_stride, int n_views,
+                                                                          int n_channels, double* __restrict__ sums)
+{
+    __shared__ double s[ecc_sum::WAVES];
+    const int v = blockIdx.x, c = blockIdx.y;
+    const float* __restrict__ h0 = values + (long long)(1 + c) * col_stride;
+    const float* __restrict__ h1 = values + (long long)(1 + n_channels + c) * col_stride;
+    double acc = 0.0;
+    for (int u = threadIdx.x; u < n_views - 1; u += ecc_sum::THREADS) {
+        const int w = u < v ? u : u + 1;
+        const long long lo = w < v ? w : v, hi = w < v ? v : w;
+        const long long pair = lo * n_views - lo * (lo + 1) / 2 + (hi - lo - 1);  // get_ij order (ecc_layout.h)
+        acc += (double)(w < v ? h1[pair] : h0[pair]);
+    }
+    ecc_sum::stage_wave_sums(acc, s);
+    if (threadIdx.x == 0) sums[(long long)c * n_views + v] = ecc_sum::waves_in_order(s);
+}
+
 // One double from device memory into a pinned, device-mapped host slot (system-scope store): how a value that a
 // collective left on the device (the all-reduced sum of a sharded evaluation) reaches a polling host without a copy command.
 __global__ void publish_scalar_kernel(const double* __restrict__ value, double* __restrict__ host_slot)
@@ -191,5 +216,16 @@ extern "C" hipError_t ecc_launch_sum_gram(const float* values_d, long long col_s
     if (count <= 0 || n_columns < 1 || (n_slices != 1 && n_slices != ecc_sum::SLICES)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(sum_gram_kernel, dim3((unsigned)n_slices, (unsigned)n_columns), dim3(ecc_sum::THREADS), 0, stream, values_d,
                        col_stride, count, n_slices, partial_d);
+    return hipGetLastError();
+}
+
+// sums_d: n_channels x n_views doubles; entry [c][v] = the sum of the gradient terms of (view v, channel c) over the pairs with v.
+// values_d: the 1 + 2 n_channels columns of ecc_launch_pairs_coeff for all n_views (n_views - 1) / 2 pairs.
+extern "C" hipError_t ecc_launch_sum_view_terms(const float* values_d, long long col_stride, int n_views, int n_channels, double* sums_d,
+                                                hipStream_t stream)
+{
+    if (n_views < 2 || n_channels < 1 || col_stride < (long long)n_views * (n_views - 1) / 2) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sum_view_terms_kernel, dim3((unsigned)n_views, (unsigned)n_channels), dim3(ecc_sum::THREADS), 0, stream, values_d,
+                       col_stride, n_views, n_channels, sums_d);
     return hipGetLastError();
 }

@@ -447,6 +447,50 @@ int ecc_metric_last_gradient_path(const ecc_metric* m, int* path);
 #define ECC_GRAM_MAX_CHANNELS 4
 int ecc_metric_evaluate_gram(ecc_metric* m, int n_channels, float* pair_grams, double* gram);
 
+/* The metric at PER-VIEW channel coefficients, and its gradient with respect to all of them, in one call -- for the image-domain
+ * corrections whose coefficients differ from view to view (a gain, an offset or a scatter scale per view):
+ *     corrected intermediate of view i = sum_c a_c,i D_c,i      (n_channels * n_views coefficients instead of n_channels).
+ * The metric is a quadratic form f(a) = a^T G a of the n K coefficients, so its gradient 2 G a is linear in a and THE SAME CALL at
+ * a direction v returns the Hessian-vector product: H v = grad f(v).  Gradient descent, L-BFGS or conjugate gradients over
+ * n K coefficients need nothing else, and the (n K) x (n K) matrix is never formed; a call costs about one
+ * ecc_metric_evaluate_gram call of the same n_channels.
+ *
+ * The metric holds n_channels * n_views Radon intermediates, channel-major, with the identity post-process, exactly as for
+ * ecc_metric_evaluate_gram: channel c of view i is dtr c * n_views + i.
+ *   coeffs (host, required): n_channels * n_views float32, coeffs[c * n_views + i] = a_c,i.
+ *   value (required): the metric of the corrected intermediates, the mean over all pairs.
+ *   grad (host, nullable): n_channels * n_views float64, grad[c * n_views + i] = d value / d a_c,i.
+ *   pair_terms (host, nullable): n_pairs x (1 + 2 K) float32, pair-major in the pair order of get_ij (the order of
+ *     ecc_metric_evaluate_all's cost image), per pair i < j the entries {value, h0[0 .. K), h1[0 .. K)} with
+ *     h0[c] = 1/2 d (pair value) / d a_c,i and h1[c] = 1/2 d (pair value) / d a_c,j.
+ * All pairs over the current matrices; the sampling mode resolves from n (n - 1) / 2 as in ecc_metric_evaluate_all, and
+ * ECC_SAMPLING_POLYNOMIAL (with its per-pair fallback and exact tail), _PER_SAMPLE and _REFERENCE are all taken, as are a fixed
+ * or automatic object radius, a user dkappa and non-derivative intermediates.
+ *
+ * The contract (tests/test_gpu_view_coefficients.py):
+ *   1. Per sample and side the combined sample is s = a_0 v_0, then s = fmaf(a_c, v_c, s) in channel order; the two differences
+ *      and the value term are ecc_metric_evaluate_all's expressions, accumulated in float64 per lane in the same trip order,
+ *      reduced by the same wave tree, rounded to float32 per pair, summed in the order of csrc/ecc_sum_order.h and divided by
+ *      n_pairs.  So with ONE coefficient 1.0 per view and the others 0.0, value and the pair values have the bits of
+ *      ecc_metric_evaluate_all on a metric of the selected intermediates alone (n_channels = 1, all ones: of this metric).
+ *   2. The gradient terms are the value term with its second factor exchanged for the channel's sample (signed so that h1 is the
+ *      derivative by view j's coefficient); grad[c * n + v] = 2 / n_pairs * the float64 sum of the n - 1 terms of the pairs that
+ *      contain v, added in ONE fixed order (csrc/sum_kernel.hip, sum_view_terms_kernel): no atomics, the same bits on every run.
+ *   3. value, grad and the pair terms agree with the CPU oracle on intermediates combined on the host to the project's bars, and
+ *      sum_k a_k grad_k = 2 value (Euler) to 1e-5 of the terms' magnitudes.
+ *   - The call changes nothing a later call can see: current matrices, kept records, the kept values of the pose-delta mode and
+ *     of the pose batch.  (It shares ecc_metric_evaluate_gram's scratch.)
+ *   - Errors before anything is launched or written, ECC_ERR_INVALID_ARGUMENT: m == NULL (checked first), value == NULL,
+ *     coeffs == NULL, n_channels outside [1, ECC_VIEW_COEFF_MAX_CHANNELS], no matrices set or fewer than two views,
+ *     n_dtrs != n_channels * n_views.  use_corr set: ECC_ERR_UNSUPPORTED.
+ * Launches (csrc/ecc_view_coeff.hip, csrc/view_coeff_kernel.hip): the record kernel over all pairs, pairs_coeff_kernel -- one
+ * wave per pair, a pair's 2 K coefficients in scalar registers, the position arithmetic of a kappa step once, 4 K gathers and
+ * 1 + 2 K products per step --, one launch for the value's sum, one for the n K gradient sums.  No small-evaluation, range, group
+ * or sharded form. */
+#define ECC_VIEW_COEFF_MAX_CHANNELS 4
+int ecc_metric_evaluate_view_coefficients(ecc_metric* m, int n_channels, const float* coeffs,
+                                          double* value, double* grad, float* pair_terms);
+
 /* n_transforms rigid source-to-target transforms of two scans in one call: the registration of two scans (ref:
  * tools/Registration/Registration3D3D.hxx:56-62, :91-110 -- a cost call multiplies every source matrix by one 4x4 transform,
  * calls setProjectionMatrices and evaluates the index list of all source x target pairs).
