@@ -194,14 +194,16 @@ def test_one_hot_on_the_first_wide_offset_grid(gpu_ctx):
 
 # ---- 6. the gradient is the sum of its terms; 8. Euler's identity ---------------------------------------------------------------
 @pytest.mark.parametrize("n,K,setup", [(8, 2, "auto"), (10, 4, "auto"), (64, 3, "polynomial"), (64, 1, "per_sample"), (66, 2, "reference"),
-                                       (258, 2, "polynomial"), (1030, 1, "polynomial")])
+                                       (258, 2, "polynomial"), (1030, 1, "polynomial"), (64, 4, "polynomial"), (20, 2, "filter_none")])
 def test_gradient_is_the_sum_of_its_terms(gpu_ctx, n, K, setup):
     """grad = 2 / n_pairs x the float64 sum of the returned h0 / h1 entries per (view, channel), within 4 n 2^-53 sum |terms| (the
     kernel's order of the n - 1 additions is not numpy's); identical bits from two calls; want_pairs changes nothing.  n = 1030: a
     thread of sum_view_terms_kernel adds more than one term (1024 threads).  And Euler's identity on the call's own outputs, f being
-    homogeneous of degree two: |sum a grad - 2 value| <= 1e-5 x (2 / N) sum_pairs sum_c (|a_c,i h0_c| + |a_c,j h1_c|)."""
+    homogeneous of degree two: |sum a grad - 2 value| <= 1e-5 x (2 / N) sum_pairs sum_c (|a_c,i h0_c| + |a_c,j h1_c|).
+    (64, 4, "polynomial"): four channels on the main path (10 views under "auto" take the reference arithmetic); "filter_none":
+    non-derivative intermediates, the kernels' DERIV = false."""
     import epipolarconsistency_amd as E
-    Ps, dtrs, _ = _scan(gpu_ctx, n, K, B=32 if n >= 60 else 48)
+    Ps, dtrs, _ = _scan(gpu_ctx, n, K, B=32 if n >= 60 else 48, filt=E.FILTER_NONE if setup == "filter_none" else None)
     a = np.random.default_rng(7).uniform(0.5, 1.5, (K, n)).astype(np.float32)
     m = _configure(setup)(E.MetricRadonIntermediate(gpu_ctx, Ps, dtrs))
     value, grad, pairs = m.evaluate_view_coefficients(a, want_pairs=True)
