@@ -733,6 +733,29 @@ class MetricRadonIntermediate:
                                                                C.c_void_p(pairs.ctypes.data) if (want_pairs and pairs.size) else None))
         return (value.value, grad, pairs) if want_pairs else (value.value, grad)
 
+    def evaluate_view_hessian(self, n_channels, want_pairs=False, want_matrix=True):
+        """ecc_metric_evaluate_view_hessian: the quadratic form of per-view channel coefficients as a matrix.  The metric holds
+        n_channels * n_views Radon intermediates as for evaluate_view_coefficients.  Returns H, (n K, n K) float64 and symmetric bit
+        for bit, with the index c * n + i of coeffs.reshape(-1): metric(a) = view_hessian_value(H, a), gradient 2 H a -- with
+        want_pairs (H, blocks), blocks (n_pairs, K (K + 1) + K^2) float64 in the pair order of evaluate(cost): per pair i < j the upper
+        triangle of P00 (view i with itself) in evaluate_gram's entry order, the upper triangle of P11 (view j with itself), then P01
+        row-major, pair value = a_i^T P00 a_i + a_j^T P11 a_j + 2 a_i^T P01 a_j.  want_matrix=False (with want_pairs): the blocks alone
+        -- H is neither assembled nor copied, and n K may exceed ECC_VIEW_HESSIAN_MAX_DIM.  Every product of two samples is formed
+        exactly in float64, so the form keeps its digits where it is a small difference of large moments.  The current matrices and
+        everything the metric keeps stay."""
+        if not want_pairs and not want_matrix:
+            raise ValueError("nothing asked for: want_matrix or want_pairs")
+        K = int(n_channels)
+        n = 0 if self._Ps is None else len(self._Ps)  # (no matrices: the library reports it)
+        Kp = max(K, 0)
+        H = np.zeros((n * Kp, n * Kp) if n * Kp else (1, 1), np.float64) if want_matrix else None  # (never a null where one was asked for)
+        blocks = None
+        if want_pairs:
+            blocks = np.zeros((n * (n - 1) // 2, Kp * (Kp + 1) + Kp * Kp) if n > 1 and Kp else (1, 1), np.float64)
+        check(_lib.lib().ecc_metric_evaluate_view_hessian(self._h, K, C.c_void_p(H.ctypes.data) if want_matrix else None,
+                                                          C.c_void_p(blocks.ctypes.data) if want_pairs else None))
+        return (H, blocks) if (want_pairs and want_matrix) else (H if want_matrix else blocks)
+
     def evaluate_transforms(self, n_source, Ts, want_pairs=False):
         """ecc_metric_evaluate_transforms: the registration of two scans (ref: tools/Registration/Registration3D3D.hxx).  The
         current matrices are the base, views [0, n_source) the source scan, the rest the target scan; Ts: anything np.asarray
@@ -1294,3 +1317,32 @@ def minimize_view_coefficients(metric, K, start, free, tol=1e-4, max_iter=None):
         p = r + (rr_new / rr) * p
         rr = rr_new
     return a, metric.evaluate_view_coefficients(a)[0], iterations
+
+
+def view_hessian_value(H, a):
+    """a^T H a in float64: the metric of the per-view coefficients a, (K, n) or flat in the order c * n + i, under the matrix of
+    MetricRadonIntermediate.evaluate_view_hessian."""
+    H = np.asarray(H, np.float64)
+    a = np.asarray(a, np.float64).reshape(-1)
+    if H.ndim != 2 or H.shape != (len(a), len(a)):
+        raise ValueError("H must be (n K, n K) and a hold n K coefficients")
+    return float(a @ (H @ a))
+
+
+def view_hessian_minimizer(H, start, free):
+    """The minimiser of a^T H a over the free coefficients, the others kept at `start`: with F the free and X the fixed coordinates,
+    H[F, F] a_F = -H[F, X] a_X (one dense numpy.linalg.solve; H from MetricRadonIntermediate.evaluate_view_hessian).  start: (K, n)
+    coefficients; free: (K, n) boolean mask, as for minimize_view_coefficients.  Returns (a, a^T H a), a (K, n) float64 with the fixed
+    coefficients' bits.  Raises numpy.linalg.LinAlgError when H[F, F] is not positive definite -- the form has no minimum there."""
+    H = np.asarray(H, np.float64)
+    a = np.array(start, np.float64)
+    mask = np.asarray(free, bool)
+    if a.ndim != 2 or mask.shape != a.shape or H.shape != (a.size, a.size):
+        raise ValueError("start and free must be (K, n_views) and H (n K, n K)")
+    F = mask.reshape(-1)
+    if F.any():
+        flat = a.reshape(-1)  # (a view: a is contiguous)
+        HFF = 0.5 * (H[np.ix_(F, F)] + H[np.ix_(F, F)].T)
+        np.linalg.cholesky(HFF)  # raises LinAlgError unless positive definite
+        flat[F] = np.linalg.solve(HFF, -0.5 * (H[np.ix_(F, ~F)] + H[np.ix_(~F, F)].T) @ flat[~F])
+    return a, view_hessian_value(H, a)

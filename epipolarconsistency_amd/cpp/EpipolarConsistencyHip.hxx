@@ -837,6 +837,41 @@ public:
         return value;
     }
 
+    /// Not in the reference: ecc_metric_evaluate_view_hessian -- the quadratic form of the per-view channel coefficients as a matrix:
+    /// metric(a) = a^T H a, gradient 2 H a, with the index c * n_views + i of evaluateViewCoefficients' coeffs.  Intermediates as for
+    /// evaluateGram.  H: (n_views n_channels)^2, symmetric bit for bit; pair_blocks (nullable): n_pairs x (K (K + 1) + K^2) doubles,
+    /// pair-major, per pair i < j the upper triangle of P00, the upper triangle of P11, then P01 row-major (ecc_hip.h).  Every
+    /// product of two samples is exact in binary64.  Single device only.
+    void evaluateViewHessian(int n_channels, std::vector<double>& H, std::vector<double>* pair_blocks = 0x0)
+    {
+        view_hessian_call("evaluateViewHessian", n_channels, &H, pair_blocks);
+    }
+    /// The pair blocks of evaluateViewHessian alone: the matrix is neither assembled nor copied, and n_views * n_channels may exceed
+    /// ECC_VIEW_HESSIAN_MAX_DIM.
+    void evaluateViewPairBlocks(int n_channels, std::vector<double>& pair_blocks)
+    {
+        view_hessian_call("evaluateViewPairBlocks", n_channels, 0x0, &pair_blocks);
+    }
+
+private:
+    // evaluateViewHessian / evaluateViewPairBlocks: the outputs sized, one call.  The channel range is checked here because the
+    // sizes depend on it, the cap because the matrix would be allocated before the library could refuse it; the rest is the library's.
+    void view_hessian_call(const char* who, int n_channels, std::vector<double>* H, std::vector<double>* pair_blocks)
+    {
+        if (m_gh) throw std::runtime_error(std::string(who) + ": not available on a device group");
+        if (n_channels < 1 || n_channels > ECC_VIEW_HESSIAN_MAX_CHANNELS)
+            throw std::runtime_error(std::string(who) + ": n_channels outside [1, ECC_VIEW_HESSIAN_MAX_CHANNELS]");
+        const size_t n = Ps.size(), K = (size_t)n_channels, dim = n * K;
+        if (H && dim > ECC_VIEW_HESSIAN_MAX_DIM) throw std::runtime_error(std::string(who) + ": n_views * n_channels above ECC_VIEW_HESSIAN_MAX_DIM");
+        if (H) H->assign(dim * dim, 0.0);
+        if (pair_blocks) pair_blocks->assign(n * (n > 0 ? n - 1 : 0) / 2 * (K * (K + 1) + K * K), 0.0);
+        double none = 0.0;  // (an empty output: the library reports why, and wants a non-null pointer to get that far)
+        double* h = !H ? 0x0 : (H->empty() ? &none : H->data());
+        double* b = !pair_blocks ? 0x0 : (pair_blocks->empty() ? &none : pair_blocks->data());
+        detail::check(ecc_metric_evaluate_view_hessian(m_h, n_channels, h, b));
+    }
+
+public:
     /// The metric borrows the dtrs: "DO NOT delete or change _dtrs during lifetime" (ref: .h:45).
     MetricRadonIntermediate& setRadonIntermediates(const std::vector<RadonIntermediate*>& _dtrs)
     {

@@ -392,6 +392,11 @@ struct ecc_metric {
     // device and the per-(view, channel) sums of the gradient terms, K * n_views each
     DeviceArray<float> coeff_d;
     DeviceArray<double> coeff_sums_d;
+    // ecc_metric_evaluate_view_hessian (ecc_view_hessian.hip) shares gram_records_d and has float64 scratch of its own: the T2
+    // columns of pair-block entries (kept, like the Gram call's columns) and the (K n_views)^2 matrix (kept up to 64 MB, else freed
+    // when the call returns)
+    DeviceArray<double> view_moments_d;
+    DeviceArray<double> view_hessian_d;
     // ecc_metric_evaluate_transforms (ecc_transforms.hip) uses the scratch above (pose_lists_d: its value slots) and, under the
     // automatic object radius, one float per transform of a batch
     DeviceArray<float> transform_radii_d;

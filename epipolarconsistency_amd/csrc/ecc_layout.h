@@ -254,6 +254,16 @@ struct EccViewCoeffParams {
     const float* coeffs;           // K * n_views floats on the device: a[c * n_views + i]
 };
 
+// ---- the per-view form as a matrix: three moment blocks per pair (view_hessian_kernel.hip) ----------
+// The same channel-major intermediates and copies.  T2 = K (K + 1) + K^2 float64 entries per pair i < j -- P00's upper triangle
+// in the Gram form's entry order, P11's upper triangle, P01 row-major -- stored COLUMN-major with the Gram form's col_stride rule.
+struct EccViewMomentParams {
+    int64_t paired_channel_bytes;  // as in EccGramParams
+    int64_t quad_channel_bytes;
+    double* values;                // T2 columns of col_stride doubles
+    int64_t col_stride;
+};
+
 // ---- projection pre-processing ------------------------------------------------
 #define ECC_PRE_MAX_CHUNKS 32  // workgroups per image of the maximum search in front of PreProccess::process (normalize)
 struct EccPreprocessParams {

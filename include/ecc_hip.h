@@ -491,6 +491,54 @@ int ecc_metric_evaluate_gram(ecc_metric* m, int n_channels, float* pair_grams, d
 int ecc_metric_evaluate_view_coefficients(ecc_metric* m, int n_channels, const float* coeffs,
                                           double* value, double* grad, float* pair_terms);
 
+/* The quadratic form of PER-VIEW channel coefficients AS A MATRIX: f(a) = a^T H a, grad f = 2 H a, with the index
+ * k = c * n_views + i of ecc_metric_evaluate_view_coefficients' coeffs.  For the callers who need the form itself and not its
+ * products -- a direct constrained solve, a regularisation sweep, many gauge or constraint choices on one data set, an
+ * eigen-analysis of what the data do not determine: one call, then every coefficient vector in closed form on the host, which is
+ * what ecc_metric_evaluate_gram gives the shared case.  (Through ecc_metric_evaluate_view_coefficients the matrix costs n K calls
+ * at one-hot coefficients.)
+ *
+ * The metric holds n_channels * n_views Radon intermediates, channel-major, with the identity post-process, exactly as for
+ * ecc_metric_evaluate_gram and ecc_metric_evaluate_view_coefficients.  For the pair q = (i < j) with the signed samples v0_c(s),
+ * v1_c(s) of channel c in view i and in view j over the pair's +-kappa samples s -- positions, fold signs, kappa range and sampling
+ * mode of ecc_metric_evaluate_all -- and the weight w = K0[6] * dkappa formed in binary64 from the two float32 values:
+ *     P00[c][d] = w sum_s v0_c v0_d,   P11[c][d] = w sum_s v1_c v1_d,   P01[c][d] = -w sum_s v0_c v1_d   (P01 is not symmetric),
+ *     pair value(a_i, a_j) = a_i^T P00 a_i + a_j^T P11 a_j + 2 a_i^T P01 a_j,
+ *     H[(c,i),(d,i)] = (sum_{j>i} P00_ij[c][d] + sum_{w<i} P11_wi[c][d]) / N,   H[(c,i),(d,j)] = H[(d,j),(c,i)] = P01_ij[c][d] / N
+ * for i < j, N = n_views (n_views - 1) / 2.
+ *   hessian (host, nullable): (n_views * n_channels)^2 float64, the full symmetric matrix; n_views * n_channels must not exceed
+ *     ECC_VIEW_HESSIAN_MAX_DIM then (512 MB on the device and on the host).
+ *   pair_blocks (host, nullable): n_pairs x T2 float64, T2 = K (K + 1) + K^2, pair-major in the pair order of get_ij; per pair
+ *     P00's upper triangle in ecc_metric_evaluate_gram's entry order, then P11's upper triangle, then P01 row-major.
+ *   At least one of the two must be given.
+ *
+ * The contract (tests/test_gpu_view_hessian.py):
+ *   1. Accuracy by construction.  The form is used near its minimum, where f(a) is a small difference of large moments, so nothing
+ *      is rounded in float32 behind the samples: the kernels see the float32 sample values ecc_metric_evaluate_view_coefficients
+ *      sees, convert each to binary64 once, and every product of two samples is exact in binary64; an entry is
+ *      acc = fma(x, y, acc) for the + and then the - sample of a kappa step, per lane in the trip order of the other pair kernels,
+ *      reduced by the same wave tree, multiplied by w once and stored as float64.
+ *   2. Every off-diagonal entry of H and its transposed twin are written once as P01 / N; every diagonal-block entry is the float64
+ *      sum over the view's n_views - 1 pairs in ONE fixed order (partners ascending, as csrc/sum_kernel.hip's sum_view_terms_kernel
+ *      adds the gradient terms) divided by N.  No atomics: the same bits on every run, and H == H^T bit for bit.
+ *   3. The pair blocks agree with a float64 oracle and with the one-hot calls of ecc_metric_evaluate_view_coefficients to the
+ *      project's bars relative to the entries' Cauchy-Schwarz scales.
+ *   - The call changes nothing a later call can see: current matrices, kept records, the kept values of the pose-delta mode and
+ *     of the pose batch.  It shares ecc_metric_evaluate_gram's record scratch and has value scratch of its own, 8 T2 bytes per pair
+ *     (23 MB at 400 views and four channels), plus the matrix when it is asked for.  The value scratch stays with the metric until
+ *     it is destroyed, as ecc_metric_evaluate_gram's does; the matrix stays only while it is at most 64 MB and is freed before the
+ *     call returns otherwise.
+ *   - Errors before anything is launched or written, ECC_ERR_INVALID_ARGUMENT: m == NULL (checked first), hessian and pair_blocks
+ *     both NULL, n_channels outside [1, ECC_VIEW_HESSIAN_MAX_CHANNELS], no matrices set or fewer than two views,
+ *     n_dtrs != n_channels * n_views.  ECC_ERR_UNSUPPORTED: use_corr set; hessian given with n_views * n_channels above
+ *     ECC_VIEW_HESSIAN_MAX_DIM.
+ * Launches (csrc/ecc_view_hessian.hip, csrc/view_hessian_kernel.hip): the record kernel over all pairs, pairs_moments_kernel -- one
+ * wave per pair, the position arithmetic of a kappa step once, 4 K gathers and 2 T2 binary64 fused multiply-adds per step --, and
+ * assemble_view_hessian_kernel when the matrix is asked for.  No small-evaluation, range, group or sharded form. */
+#define ECC_VIEW_HESSIAN_MAX_CHANNELS 4
+#define ECC_VIEW_HESSIAN_MAX_DIM 8192   /* n_views * n_channels when hessian != NULL: 512 MB */
+int ecc_metric_evaluate_view_hessian(ecc_metric* m, int n_channels, double* hessian, double* pair_blocks);
+
 /* n_transforms rigid source-to-target transforms of two scans in one call: the registration of two scans (ref:
  * tools/Registration/Registration3D3D.hxx:56-62, :91-110 -- a cost call multiplies every source matrix by one 4x4 transform,
  * calls setProjectionMatrices and evaluates the index list of all source x target pairs).
