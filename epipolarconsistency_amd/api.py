@@ -756,6 +756,21 @@ class MetricRadonIntermediate:
                                                           C.c_void_p(blocks.ctypes.data) if want_pairs else None))
         return (H, blocks) if (want_pairs and want_matrix) else (H if want_matrix else blocks)
 
+    def evaluate_weighted(self, want_pairs=False):
+        """ecc_metric_evaluate_weighted: the metric with per-line weights in Radon space.  The metric holds 2 * n_views Radon
+        intermediates, channel-major: the data of every view, then the line weights of every view on the same bin grid (line_weights;
+        FILTER_NONE, values in [0, 1]).  Per +-kappa sample of the pair i < j the squared difference of evaluate() counts with
+        mu = W_i(sample) * W_j(sample).  Returns (value, coverage): value = sum c / sum u over the pairs, coverage = sum u / n_pairs --
+        with want_pairs (value, coverage, pairs), pairs (n_pairs, 2) float32 in the pair order of evaluate(cost): per pair c, its
+        weighted value, and u = (sum mu) / (number of samples), its coverage.  All weights 1: the bits of evaluate() and coverage 1.
+        The current matrices and everything the metric keeps stay."""
+        n = 0 if self._Ps is None else len(self._Ps)  # (no matrices: the library reports it)
+        value, coverage = C.c_double(0.0), C.c_double(0.0)
+        pairs = np.zeros((n * (n - 1) // 2, 2), np.float32) if want_pairs else None
+        check(_lib.lib().ecc_metric_evaluate_weighted(self._h, C.byref(value), C.byref(coverage),
+                                                      C.c_void_p(pairs.ctypes.data) if (want_pairs and pairs.size) else None))
+        return (value.value, coverage.value, pairs) if want_pairs else (value.value, coverage.value)
+
     def evaluate_transforms(self, n_source, Ts, want_pairs=False):
         """ecc_metric_evaluate_transforms: the registration of two scans (ref: tools/Registration/Registration3D3D.hxx).  The
         current matrices are the base, views [0, n_source) the source scan, the rest the target scan; Ts: anything np.asarray
@@ -1317,6 +1332,52 @@ def minimize_view_coefficients(metric, K, start, free, tol=1e-4, max_iter=None):
         p = r + (rr_new / rr) * p
         rr = rr_new
     return a, metric.evaluate_view_coefficients(a)[0], iterations
+
+
+def line_weights_from_lengths(lengths, zero_at_px=1.0, guard_bins=1):
+    """The host half of line_weights: lengths (n_t, n_alpha) float32, the length of every bin's line inside flagged pixels ->
+    float32 weights clip(1 - L / zero_at_px, 0, 1) (float32 operations), then the minimum over the (2 guard_bins + 1)^2 bin
+    neighbourhood, the grid's edges clamped as the bilinear taps clamp them."""
+    L = np.asarray(lengths, np.float32)
+    if L.ndim != 2:
+        raise ValueError("lengths must be (n_t, n_alpha)")
+    if not zero_at_px > 0:
+        raise ValueError("zero_at_px must be positive")
+    g = int(guard_bins)
+    if g < 0:
+        raise ValueError("guard_bins must not be negative")
+    w = np.clip(np.float32(1.0) - L / np.float32(zero_at_px), np.float32(0.0), np.float32(1.0)).astype(np.float32)
+    if g:
+        padded = np.pad(w, g, mode="edge")
+        n_t, n_alpha = w.shape
+        out = w
+        for dj in range(2 * g + 1):
+            for di in range(2 * g + 1):
+                out = np.minimum(out, padded[dj:dj + n_t, di:di + n_alpha])
+        w = out
+    return np.ascontiguousarray(w, np.float32)
+
+
+def line_weights(ctx, flagged, size_alpha, size_t, zero_at_px=1.0, guard_bins=1):
+    """Line weights for MetricRadonIntermediate.evaluate_weighted from an image of flagged pixels.  flagged: (n_v, n_u) float32, 1
+    where a pixel must not be trusted (an instrument, a collimator blade, a defective column) and 0 elsewhere -- or (n, n_v, n_u) /
+    a list of such images, for which a list is returned.  L, the FILTER_NONE / POST_IDENTITY Radon intermediate of `flagged` from the
+    Radon kernel, is the length in pixels of every bin's line inside flagged pixels; the weight is clip(1 - L / zero_at_px, 0, 1),
+    followed by the minimum over the (2 guard_bins + 1)^2 bin neighbourhood (line_weights_from_lengths), so that with guard_bins >= 1
+    a bilinear sample with a weight above 0 touches no bin with L >= zero_at_px.  Returns a RadonIntermediate with FILTER_NONE on
+    the same bin grid.  Runs once per data set: one readback, numpy on the host, one upload."""
+    arr = np.asarray(flagged, np.float32)
+    single = arr.ndim == 2
+    if arr.ndim not in (2, 3):
+        raise ValueError("flagged must be (n_v, n_u) or (n, n_v, n_u)")
+    stack = arr[None] if single else arr
+    n_v, n_u = stack.shape[1:]
+    out = []
+    for d in RadonIntermediate.compute_batch(ctx, stack, size_alpha, size_t, FILTER_NONE, POST_IDENTITY):
+        w = line_weights_from_lengths(d.readback(), zero_at_px, guard_bins)
+        d.close()
+        out.append(RadonIntermediate.from_host(ctx, w, n_u, n_v, FILTER_NONE))
+    return out[0] if single else out
 
 
 def view_hessian_value(H, a):

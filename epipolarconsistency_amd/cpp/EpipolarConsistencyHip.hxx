@@ -837,6 +837,21 @@ public:
         return value;
     }
 
+    /// Not in the reference (its weight slot is wired to 1.0f): ecc_metric_evaluate_weighted -- the metric with per-line weights in
+    /// Radon space.  The Radon intermediates are the data of the n_views views, then the line weights of the n_views views on the
+    /// same bin grid (no filter, values in [0, 1]): dtrs[n_views + i] weighs the lines of view i.  Returns sum c / sum u over the
+    /// pairs; coverage (nullable): sum u / n_pairs; pair_terms (nullable): n_pairs x 2 floats, pair-major, per pair i < j {c, u}: the
+    /// weighted value and the mean weight of its samples.  All weights 1: the bits of evaluate() (ecc_hip.h).  Single device only.
+    double evaluateWeighted(double* coverage = 0x0, std::vector<float>* pair_terms = 0x0)
+    {
+        if (m_gh) throw std::runtime_error("evaluateWeighted: not available on a device group");
+        const size_t n = Ps.size();
+        if (pair_terms) pair_terms->assign(n * (n > 0 ? n - 1 : 0), 0.f);
+        double value = 0.0;
+        detail::check(ecc_metric_evaluate_weighted(m_h, &value, coverage, (pair_terms && !pair_terms->empty()) ? pair_terms->data() : 0x0));
+        return value;
+    }
+
     /// Not in the reference: ecc_metric_evaluate_view_hessian -- the quadratic form of the per-view channel coefficients as a matrix:
     /// metric(a) = a^T H a, gradient 2 H a, with the index c * n_views + i of evaluateViewCoefficients' coeffs.  Intermediates as for
     /// evaluateGram.  H: (n_views n_channels)^2, symmetric bit for bit; pair_blocks (nullable): n_pairs x (K (K + 1) + K^2) doubles,

@@ -264,6 +264,16 @@ struct EccViewMomentParams {
     int64_t col_stride;
 };
 
+// ---- the metric with per-line weights in Radon space (weighted_kernel.hip) ---------------------------
+// 2 n_views channel-major intermediates and copies: channel 0 the data, channel 1 the line weights.  Two float32 entries per pair
+// i < j -- the weighted value c and the coverage u -- stored COLUMN-major with the Gram form's col_stride rule.
+struct EccWeightedParams {
+    int64_t paired_channel_bytes;  // as in EccGramParams
+    int64_t quad_channel_bytes;
+    float* values;                 // 2 columns of col_stride floats
+    int64_t col_stride;
+};
+
 // ---- projection pre-processing ------------------------------------------------
 #define ECC_PRE_MAX_CHUNKS 32  // workgroups per image of the maximum search in front of PreProccess::process (normalize)
 struct EccPreprocessParams {

@@ -539,6 +539,50 @@ int ecc_metric_evaluate_view_coefficients(ecc_metric* m, int n_channels, const f
 #define ECC_VIEW_HESSIAN_MAX_DIM 8192   /* n_views * n_channels when hessian != NULL: 512 MB */
 int ecc_metric_evaluate_view_hessian(ecc_metric* m, int n_channels, double* hessian, double* pair_blocks);
 
+/* The metric with PER-LINE WEIGHTS in Radon space: which redundant samples count.  An instrument in one view of a fluoroscopy
+ * sequence, a collimator blade, a defective detector column or a table edge present in some views only breaks exactly the epipolar
+ * lines that cross it and leaves every other line consistent; zeroing or feathering the region in the image changes the integral of
+ * every line through it and only moves the inconsistency.  The reference has a weight slot per sample for this, wired to 1.0f
+ * (ref: EpipolarConsistencyRadonIntermediate.cu:254), and its host epilogue already returns sum value w / sum w
+ * (ref: ...RadonIntermediate.cpp:197-224).
+ *
+ * The metric holds 2 * n_views Radon intermediates, channel-major as for ecc_metric_evaluate_gram: dtr i is the data of view i, dtr
+ * n_views + i the LINE WEIGHTS W_i of view i on the same bin grid, normally made without a filter and with values in [0, 1]; any
+ * finite float is taken as it is.  For the pair i < j a +-kappa sample has the positions, kappa range and sampling mode of
+ * ecc_metric_evaluate_all; d is that evaluation's difference of the two signed data samples, and mu = W_i(sample) * W_j(sample) one
+ * float32 multiply of two bilinear samples taken at the same taps as the data.  The fold sign is never applied to a weight sample.
+ * Per kappa step the value term is ecc_metric_evaluate_all's expression with mu multiplied into the first factor only --
+ *     polynomial loops             fmaf(mu_p * dp, dp, (mu_m * dm) * dm) * w06_dkappa
+ *     exact and reference loops    (((mu_p * dp) * dp + (mu_m * dm) * dm) * K0[6]) * dkappa
+ * -- accumulated in float64 per lane in the same trip order and reduced by the same wave tree; beside it each lane adds
+ * (double)(mu_p + mu_m), the weight mass, and 2.0, the sample count.  Per pair q:
+ *     c_q = the float32 value,
+ *     u_q = (float)(mass / count), the COVERAGE in [0, 1]; a pair without samples has c_q = 0, u_q = 1.0f.
+ *   value (required): sum c_q / sum u_q, both sums in the order of csrc/ecc_sum_order.h.  Dividing by sum u_q keeps an optimiser from
+ *     lowering the metric by pushing lines into masked regions; the unnormalised sums are in the pair terms.
+ *   coverage (nullable): sum u_q / n_pairs.  sum u_q == 0: value = 0.0, coverage = 0.0 and ECC_OK.
+ *   pair_terms (host, nullable): n_pairs x 2 float32, pair-major in the pair order of get_ij, each row {c_q, u_q}.
+ * All pairs over the current matrices; the sampling mode resolves from n (n - 1) / 2 as in ecc_metric_evaluate_all, and
+ * ECC_SAMPLING_POLYNOMIAL (with its per-pair fallback and exact tail), _PER_SAMPLE and _REFERENCE are all taken, as are a fixed or
+ * automatic object radius, a user dkappa, non-derivative data and row-paired and row-quad copies.
+ *
+ * The contract (tests/test_gpu_weighted.py):
+ *   1. With every weight 1.0f, value and the c column have the bits of ecc_metric_evaluate_all on the same metric, every u_q and
+ *      coverage are 1.0.
+ *   2. With W_v = 0 for one view and 1 elsewhere the pairs that contain v are {0, 0}, every other pair keeps its bits, and value is
+ *      the mean over the other pairs.
+ *   3. c_q and u_q agree with a float64 oracle (tests/weighted_terms.py) to the project's bars.
+ *   4. Data that differ only on lines whose weight is 0 give the same bits.
+ *   - The call changes nothing a later call can see: current matrices, kept records, the kept values of the pose-delta mode and of
+ *     the pose batch.  (It shares ecc_metric_evaluate_gram's scratch.)
+ *   - Errors before anything is launched or written, ECC_ERR_INVALID_ARGUMENT: m == NULL (checked first), value == NULL, no matrices
+ *     set or fewer than two views, n_dtrs != 2 * n_views.  use_corr set: ECC_ERR_UNSUPPORTED.
+ * Launches (csrc/ecc_weighted.hip, csrc/weighted_kernel.hip): the record kernel over all pairs, pairs_weighted_kernel -- one wave per
+ * pair, the position arithmetic of a kappa step once, 8 gathers --, one launch for the two sums.
+ * Out of scope: index lists, pose-delta, pose-batch, transform, range, group and RCCL forms; weights under use_corr; a
+ * 1 / (sigma0^2 + sigma1^2) variance form; a per-sample robust loss. */
+int ecc_metric_evaluate_weighted(ecc_metric* m, double* value, double* coverage, float* pair_terms);
+
 /* n_transforms rigid source-to-target transforms of two scans in one call: the registration of two scans (ref:
  * tools/Registration/Registration3D3D.hxx:56-62, :91-110 -- a cost call multiplies every source matrix by one 4x4 transform,
  * calls setProjectionMatrices and evaluates the index list of all source x target pairs).
