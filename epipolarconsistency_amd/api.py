@@ -350,6 +350,31 @@ class RadonIntermediate:
             pass
 
 
+def _pack_pose_lists(moved_views, moved_Ps):
+    """Per-pose sequences of moved views and their matrices -> the packed (moved_offsets, moved_views, moved_Ps) of the C calls."""
+    off = [0]
+    views = []
+    rows = []
+    for vk, Pk in zip(moved_views, moved_Ps):
+        vk = [int(v) for v in np.atleast_1d(vk)]
+        Pk = np.asarray(Pk, np.float64)
+        Pk = Pk.reshape(len(vk), 12) if (Pk.shape[-1] == 12 and Pk.ndim <= 2) else _Ps_colmajor(Pk)
+        views += vk
+        rows.append(Pk)
+        off.append(len(views))
+    flat = np.concatenate(rows) if rows and len(views) else np.zeros((0, 12))
+    return off, views, flat
+
+
+def _check_pose_lists(moved_offsets, moved_views, moved_Ps):
+    off = np.ascontiguousarray(moved_offsets, np.int32)
+    views = np.ascontiguousarray(moved_views, np.int32)
+    flat = np.ascontiguousarray(moved_Ps, np.float64).reshape(-1, 12)
+    if len(off) < 1 or int(off[-1]) != len(views) or len(flat) != len(views):
+        raise ValueError("moved_offsets / moved_views / moved_Ps disagree")
+    return off, views, flat
+
+
 class MetricRadonIntermediate:
     """ref: class MetricRadonIntermediate : public Metric."""
 
@@ -612,33 +637,50 @@ class MetricRadonIntermediate:
         """ecc_metric_evaluate_pose_deltas: pose k = the current matrices with the views moved_views[k] (a sequence of view
         indices, strictly ascending) replaced by moved_Ps[k] (the same number of 3x4 matrices, or (c, 12) column-major rows).
         Returns the means, every one bit-identical to setProjectionMatrices + evaluate of that pose; the current matrices stay."""
-        off = [0]
-        views = []
-        rows = []
-        for vk, Pk in zip(moved_views, moved_Ps):
-            vk = [int(v) for v in np.atleast_1d(vk)]
-            Pk = np.asarray(Pk, np.float64)
-            Pk = Pk.reshape(len(vk), 12) if (Pk.shape[-1] == 12 and Pk.ndim <= 2) else _Ps_colmajor(Pk)
-            views += vk
-            rows.append(Pk)
-            off.append(len(views))
-        flat = np.concatenate(rows) if rows and len(views) else np.zeros((0, 12))
-        return self.evaluate_pose_deltas_packed(off, views, flat)
+        return self.evaluate_pose_deltas_packed(*_pack_pose_lists(moved_views, moved_Ps))
 
     def evaluate_pose_deltas_packed(self, moved_offsets, moved_views, moved_Ps):
         """The C signature itself: moved_offsets (K + 1 int32, [0] = 0), moved_views (Q int32, ascending within a pose), moved_Ps
         ((Q, 12) float64, column-major per matrix).  No per-pose Python work."""
-        off = np.ascontiguousarray(moved_offsets, np.int32)
-        views = np.ascontiguousarray(moved_views, np.int32)
-        flat = np.ascontiguousarray(moved_Ps, np.float64).reshape(-1, 12)
-        if len(off) < 1 or int(off[-1]) != len(views) or len(flat) != len(views):
-            raise ValueError("moved_offsets / moved_views / moved_Ps disagree")
+        off, views, flat = _check_pose_lists(moved_offsets, moved_views, moved_Ps)
         means = np.zeros(len(off) - 1, np.float64)
         check(_lib.lib().ecc_metric_evaluate_pose_deltas(self._h, len(means), C.c_void_p(off.ctypes.data),
                                                          C.c_void_p(views.ctypes.data) if len(views) else None,
                                                          C.c_void_p(flat.ctypes.data) if len(views) else None,
                                                          C.c_void_p(means.ctypes.data)))
         return means
+
+    def evaluate_weighted_pose_deltas(self, moved_views, moved_Ps):
+        """ecc_metric_evaluate_weighted_pose_deltas: evaluate_pose_deltas for the metric with per-line weights (evaluate_weighted: the
+        metric holds the data of every view, then its line weights).  The same arguments; returns (values, coverages), every entry
+        bit-identical to setProjectionMatrices + evaluate_weighted of that pose; the current matrices stay."""
+        return self.evaluate_weighted_pose_deltas_packed(*_pack_pose_lists(moved_views, moved_Ps))
+
+    def evaluate_weighted_pose_deltas_packed(self, moved_offsets, moved_views, moved_Ps):
+        """The C signature itself, with the arguments of evaluate_pose_deltas_packed; returns (values, coverages)."""
+        off, views, flat = _check_pose_lists(moved_offsets, moved_views, moved_Ps)
+        values, coverages = np.zeros(len(off) - 1, np.float64), np.zeros(len(off) - 1, np.float64)
+        check(_lib.lib().ecc_metric_evaluate_weighted_pose_deltas(self._h, len(values), C.c_void_p(off.ctypes.data),
+                                                                  C.c_void_p(views.ctypes.data) if len(views) else None,
+                                                                  C.c_void_p(flat.ctypes.data) if len(views) else None,
+                                                                  C.c_void_p(values.ctypes.data), C.c_void_p(coverages.ctypes.data)))
+        return values, coverages
+
+    def evaluate_weighted_pairs(self, idx4, want_pairs=False):
+        """ecc_metric_evaluate_weighted_pairs: evaluate_weighted over an index list of (P0, P1, D0, D1) tuples -- matrices P*, data
+        intermediates D* in [0, n_views); the weights of a sample come from intermediate n_views + D*.  Returns (value, coverage) =
+        (sum c / sum u, sum u / n_pairs) over the list -- with want_pairs (value, coverage, pairs), pairs (n_pairs, 2) float32 rows
+        {c, u} in list order.  The sampling mode resolves from the list's length, as evaluate(indices) resolves it."""
+        idx = np.ascontiguousarray(idx4, np.int32)
+        if idx.size % 4 or (idx.ndim == 2 and idx.shape[1] != 4) or idx.ndim > 2:
+            raise ValueError("idx4 must hold (P0, P1, D0, D1) tuples")
+        idx = idx.reshape(-1, 4)
+        value, coverage = C.c_double(0.0), C.c_double(0.0)
+        pairs = np.zeros((len(idx), 2), np.float32) if want_pairs else None
+        check(_lib.lib().ecc_metric_evaluate_weighted_pairs(self._h, C.c_void_p(idx.ctypes.data) if len(idx) else None, len(idx),
+                                                            C.byref(value), C.byref(coverage),
+                                                            C.c_void_p(pairs.ctypes.data) if (want_pairs and pairs.size) else None))
+        return (value.value, coverage.value, pairs) if want_pairs else (value.value, coverage.value)
 
     def setPoseBatching(self, on=True):
         """ecc_metric_set_pose_batching: off = evaluate_poses runs every pose as its own stream-ordered evaluation."""

@@ -852,6 +852,50 @@ public:
         return value;
     }
 
+    /// Not in the reference: ecc_metric_evaluate_weighted_pairs -- evaluateWeighted over an index list of (P0, P1, D0, D1) tuples
+    /// (indices: 4 ints per tuple; matrices P*, data intermediates D* in [0, n_views), the weights of a sample come from
+    /// dtrs[n_views + D*]).  Returns sum c / sum u over the list; coverage (nullable): sum u / n_pairs; pair_terms (nullable):
+    /// n_pairs x 2 floats {c, u} in list order.  The sampling mode resolves from the list's length (ecc_hip.h).  Single device only.
+    double evaluateWeightedPairs(const std::vector<int>& indices, double* coverage = 0x0, std::vector<float>* pair_terms = 0x0)
+    {
+        if (m_gh) throw std::runtime_error("evaluateWeightedPairs: not available on a device group");
+        if (indices.size() % 4) throw std::runtime_error("evaluateWeightedPairs: four indices per tuple");
+        const std::vector<int32_t> idx(indices.begin(), indices.end());
+        if (pair_terms) pair_terms->assign(idx.size() / 2, 0.f);
+        double value = 0.0;
+        if (coverage) *coverage = 0.0;
+        detail::check(ecc_metric_evaluate_weighted_pairs(m_h, idx.empty() ? 0x0 : idx.data(), (int)(idx.size() / 4), &value, coverage,
+                                                         (pair_terms && !pair_terms->empty()) ? pair_terms->data() : 0x0));
+        return value;
+    }
+
+    /// Not in the reference: ecc_metric_evaluate_weighted_pose_deltas -- evaluatePoseDeltas for the metric with per-line weights
+    /// (intermediates as for evaluateWeighted).  values[k] and coverages[k] (coverages nullable) are bit-identical to replacing the
+    /// views moved_views[k] by moved_Ps[k], setProjectionMatrices and evaluateWeighted(); the current matrices stay.  Single device only.
+    void evaluateWeightedPoseDeltas(const std::vector<std::vector<int> >& moved_views,
+                                    const std::vector<std::vector<Geometry::ProjectionMatrix> >& moved_Ps, std::vector<double>& values,
+                                    std::vector<double>* coverages = 0x0)
+    {
+        if (m_gh) throw std::runtime_error("evaluateWeightedPoseDeltas: not available on a device group");
+        if (moved_views.size() != moved_Ps.size()) throw std::runtime_error("evaluateWeightedPoseDeltas: one matrix list per pose");
+        values.assign(moved_views.size(), 0.0);
+        if (coverages) coverages->assign(moved_views.size(), 0.0);
+        if (moved_views.empty()) return;
+        std::vector<int32_t> off(1, 0), views;
+        std::vector<double> flat;
+        for (size_t k = 0; k < moved_views.size(); ++k) {
+            if (moved_views[k].size() != moved_Ps[k].size()) throw std::runtime_error("evaluateWeightedPoseDeltas: one matrix per moved view");
+            for (size_t q = 0; q < moved_views[k].size(); ++q) {
+                views.push_back(moved_views[k][q]);
+                flat.insert(flat.end(), moved_Ps[k][q].data(), moved_Ps[k][q].data() + 12);
+            }
+            off.push_back((int32_t)views.size());
+        }
+        detail::check(ecc_metric_evaluate_weighted_pose_deltas(m_h, (int)moved_views.size(), off.data(), views.empty() ? 0x0 : views.data(),
+                                                               flat.empty() ? 0x0 : flat.data(), values.data(),
+                                                               coverages ? coverages->data() : 0x0));
+    }
+
     /// Not in the reference: ecc_metric_evaluate_view_hessian -- the quadratic form of the per-view channel coefficients as a matrix:
     /// metric(a) = a^T H a, gradient 2 H a, with the index c * n_views + i of evaluateViewCoefficients' coeffs.  Intermediates as for
     /// evaluateGram.  H: (n_views n_channels)^2, symmetric bit for bit; pair_blocks (nullable): n_pairs x (K (K + 1) + K^2) doubles,

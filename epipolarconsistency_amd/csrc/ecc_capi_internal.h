@@ -434,6 +434,18 @@ int evaluate_cached(ecc_metric* m, int64_t first, int64_t count, double* sum_d, 
 // (automatic) object radius
 int sum_poses(ecc_metric* m, const float* base_vals_d, int K, int Q, volatile uint64_t* out, double* out_dev, double* sums);
 bool pose_keeps_radius(const ecc_metric* m, double base_radius, int c, const int32_t* views, const double* moved_Ps);
+// ecc_poses.hip, for the batches of ecc_weighted_poses.hip as well: the lists' checks; the host half of a batch's grid (pinned block,
+// device arrays) and the launch of pose_list_kernel over it; the result slots' sentinel and the bounded wait for them
+int check_lists(const ecc_metric* m, int n_poses, const int32_t* off, const int32_t* views);
+int stage_pose_grid(ecc_metric* m, const double* base, int K, const int32_t* off, const int32_t* views, const double* moved_Ps,
+                    int result_words, volatile uint64_t** out, double** out_dev);
+hipError_t launch_pose_list(ecc_metric* m, int K, int Q, int result_words);
+void arm_pose_results(volatile uint64_t* out, int K);
+int wait_pose_results(ecc_ctx* ctx, volatile uint64_t* out, int K, double* sums);
+// ecc_weighted.hip: the argument checks of the weighted calls; {c, u} of all pairs at the current matrices into gram_values_d
+// (p, g: the launch as it was made)
+int weighted_check(const ecc_metric* m);
+int weighted_base_columns(ecc_metric* m, EccPairParams* p, EccWeightedParams* g);
 
 // The pair launch p -- or, with x, the one-launch evaluation -- on the context's stream between its timing events (ecc_ctx_enable_timing).
 inline hipError_t launch_pairs_timed(ecc_ctx* ctx, const EccPairParams* p, const EccSmallEval* x = nullptr)

@@ -184,27 +184,33 @@ constexpr uint64_t POSE_PENDING = 0x7ff8ecc0dead0002ull;  // the two-deep form's
 
 size_t align64(size_t x) { return (x + 63) & ~(size_t)63; }
 
+// the pinned block of a batch: extended matrices | results | off | views (byte offsets)
+struct PoseBlock {
+    size_t Ps, out, off, views, end;
+};
+PoseBlock pose_block(int64_t n, int K, int Q, int result_words)
+{
+    PoseBlock b;
+    b.Ps = 0;
+    b.out = align64(sizeof(double) * 12 * (size_t)(n + Q));
+    b.off = b.out + align64(sizeof(double) * (size_t)result_words);
+    b.views = b.off + align64(sizeof(int32_t) * (size_t)(K + 1));
+    b.end = b.views + align64(sizeof(int32_t) * (size_t)std::max(Q, 1));
+    return b;
+}
+
 }  // namespace
 namespace ecc_internal {
-// sum_poses_kernel (+ finish_poses_kernel) over K poses whose Q columns of pair values are in m->pose_values_d and whose lists
-// are in m->pose_lists_d by the time the stream gets here (pose_list_kernel; small_poses_kernel), then the wait for the K sums:
-// out / out_dev are the host and device address of K result words in pinned memory (m->pose_h).
-int sum_poses(ecc_metric* m, const float* base_vals_d, int K, int Q, volatile uint64_t* out, double* out_dev, double* sums)
+// K result words in pinned memory get the "pending" pattern, before the launch that will store into them.
+void arm_pose_results(volatile uint64_t* out, int K)
 {
-    ecc_ctx* ctx = m->ctx;
-    const int64_t n = m->n_views, n_pairs = n * (n - 1) / 2;
     for (int k = 0; k < K; ++k) out[k] = POSE_PENDING;
     std::atomic_thread_fence(std::memory_order_seq_cst);
-    // ecc_launch_sum_pairs' choice for the metric's own evaluations
-    const int slices = ecc_sum::slices(n_pairs, m->sum_scratch_d.ptr != nullptr);
-    hipLaunchKernelGGL(slices == 1 ? sum_poses_kernel<1> : sum_poses_kernel<SUM_SLICES>, dim3((unsigned)slices, (unsigned)K), dim3(SUM_THREADS), 0,
-                       ctx->stream, base_vals_d, (long long)n_pairs, (int)n, Q, m->pose_lists_d.ptr, K, m->pose_values_d.ptr,
-                       m->pose_partial_d.ptr, out_dev);
-    HIP_TRY(hipGetLastError());
-    if (slices > 1) {
-        hipLaunchKernelGGL(finish_poses_kernel, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, ctx->stream, m->pose_partial_d.ptr, slices, K, out_dev);
-        HIP_TRY(hipGetLastError());
-    }
+}
+
+// The K result words a launch on the stream stores into pinned memory (armed by arm_pose_results before the launch) -> sums.
+int wait_pose_results(ecc_ctx* ctx, volatile uint64_t* out, int K, double* sums)
+{
     // the results arrive in pinned memory a few microseconds before the stream is reported idle: poll the last one, then the rest
     double t0 = 0.0;
     for (unsigned spins = 0;; ++spins) {
@@ -230,6 +236,27 @@ int sum_poses(ecc_metric* m, const float* base_vals_d, int K, int Q, volatile ui
     return ECC_OK;
 }
 
+// sum_poses_kernel (+ finish_poses_kernel) over K poses whose Q columns of pair values are in m->pose_values_d and whose lists
+// are in m->pose_lists_d by the time the stream gets here (pose_list_kernel; small_poses_kernel), then the wait for the K sums:
+// out / out_dev are the host and device address of K result words in pinned memory (m->pose_h).
+int sum_poses(ecc_metric* m, const float* base_vals_d, int K, int Q, volatile uint64_t* out, double* out_dev, double* sums)
+{
+    ecc_ctx* ctx = m->ctx;
+    const int64_t n = m->n_views, n_pairs = n * (n - 1) / 2;
+    arm_pose_results(out, K);
+    // ecc_launch_sum_pairs' choice for the metric's own evaluations
+    const int slices = ecc_sum::slices(n_pairs, m->sum_scratch_d.ptr != nullptr);
+    hipLaunchKernelGGL(slices == 1 ? sum_poses_kernel<1> : sum_poses_kernel<SUM_SLICES>, dim3((unsigned)slices, (unsigned)K), dim3(SUM_THREADS), 0,
+                       ctx->stream, base_vals_d, (long long)n_pairs, (int)n, Q, m->pose_lists_d.ptr, K, m->pose_values_d.ptr,
+                       m->pose_partial_d.ptr, out_dev);
+    HIP_TRY(hipGetLastError());
+    if (slices > 1) {
+        hipLaunchKernelGGL(finish_poses_kernel, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, ctx->stream, m->pose_partial_d.ptr, slices, K, out_dev);
+        HIP_TRY(hipGetLastError());
+    }
+    return wait_pose_results(ctx, out, K, sums);
+}
+
 // The automatic object radius follows the FIRST matrix (ref: Metric::getObjectRadius, EpipolarConsistency.cpp:76-84): a pose
 // that moves view 0 may change it, and with it every pair's record.  Such a pose is not a delta of the base.
 bool pose_keeps_radius(const ecc_metric* m, double base_radius, int c, const int32_t* views, const double* moved_Ps)
@@ -237,6 +264,51 @@ bool pose_keeps_radius(const ecc_metric* m, double base_radius, int c, const int
     if (m->object_radius_mm > 0 || c < 1 || views[0] != 0) return true;
     // (the launches take the radius as a float: fill_pair_params)
     return (float)ecc_host::object_radius(moved_Ps, m->n_u, m->n_v) == (float)base_radius;
+}
+
+// The host half of a batch's grid: the pinned block -- extended matrices (the base's n, then the Q moved ones) | result_words
+// result slots | off | views -- is filled, and the device arrays of the extended geometry, the index grid, its records and the lists
+// have room.  *out / *out_dev: host and device address of the result slots.
+int stage_pose_grid(ecc_metric* m, const double* base, int K, const int32_t* off, const int32_t* views, const double* moved_Ps,
+                    int result_words, volatile uint64_t** out, double** out_dev)
+{
+    ecc_ctx* ctx = m->ctx;
+    const int64_t n = m->n_views;
+    const int Q = off[K];
+    const int64_t entries = n * (int64_t)Q;
+    const PoseBlock b = pose_block(n, K, Q, result_words);
+    int rc = m->pose_h.ensure((int64_t)b.end, 1 << 16, ctx->stream);
+    if (rc) return rc;
+    char* const pose_h = m->pose_h.host;
+    double* Ps_ext = reinterpret_cast<double*>(pose_h + b.Ps);
+    std::memcpy(Ps_ext, base, sizeof(double) * 12 * (size_t)n);
+    if (Q > 0) std::memcpy(Ps_ext + 12 * (size_t)n, moved_Ps, sizeof(double) * 12 * (size_t)Q);
+    std::memcpy(pose_h + b.off, off, sizeof(int32_t) * (size_t)(K + 1));
+    if (Q > 0) std::memcpy(pose_h + b.views, views, sizeof(int32_t) * (size_t)Q);
+    std::atomic_thread_fence(std::memory_order_seq_cst);
+    *out = reinterpret_cast<volatile uint64_t*>(pose_h + b.out);
+    *out_dev = reinterpret_cast<double*>(m->pose_h.dev + b.out);
+
+    rc = m->pose_PinvTs_d.ensure(12 * (n + Q), ctx->stream);
+    if (!rc) rc = m->pose_Cs_d.ensure(4 * (n + Q), ctx->stream);
+    if (!rc) rc = m->pose_idx_d.ensure(4 * std::max<int64_t>(entries, 1), ctx->stream);
+    if (!rc) rc = m->pose_records_d.ensure(std::max<int64_t>(entries, 1), ctx->stream);
+    if (!rc) rc = m->pose_lists_d.ensure((int64_t)K + 1 + std::max(Q, 1), ctx->stream);
+    return rc;
+}
+
+// pose_list_kernel over the block stage_pose_grid has just filled (the same K, Q and result_words): index tuples + lists
+// (K workgroups) and E1 of the n + Q extended matrices (the workgroups behind them) in one launch.
+hipError_t launch_pose_list(ecc_metric* m, int K, int Q, int result_words)
+{
+    const int64_t n = m->n_views;
+    const PoseBlock b = pose_block(n, K, Q, result_words);
+    const char* const pose_h_dev = m->pose_h.dev;
+    PoseLists in = {reinterpret_cast<const int32_t*>(pose_h_dev + b.off), reinterpret_cast<const int32_t*>(pose_h_dev + b.views)};
+    const unsigned e1_blocks = n * (int64_t)Q > 0 ? (unsigned)((n + Q + 63) / 64) : 0u;
+    hipLaunchKernelGGL(pose_list_kernel, dim3((unsigned)K + e1_blocks), dim3(256), 0, m->ctx->stream, in, (int)n, K, Q, m->pose_idx_d.ptr,
+                       m->pose_lists_d.ptr, reinterpret_cast<const double*>(pose_h_dev + b.Ps), m->pose_PinvTs_d.ptr, m->pose_Cs_d.ptr);
+    return hipGetLastError();
 }
 }  // namespace ecc_internal
 namespace {
@@ -251,39 +323,17 @@ int run_batch(ecc_metric* m, const double* base, const float* base_vals_d, int K
     const int64_t n = m->n_views, n_pairs = n * (n - 1) / 2;
     const int Q = off[K];
     const int64_t entries = n * (int64_t)Q;
-    // the pinned block: extended matrices | results | off | views
-    const size_t b_Ps = 0, b_out = align64(sizeof(double) * 12 * (size_t)(n + Q)), b_off = b_out + align64(sizeof(double) * (size_t)K),
-                 b_views = b_off + align64(sizeof(int32_t) * (size_t)(K + 1)), b_end = b_views + align64(sizeof(int32_t) * (size_t)std::max(Q, 1));
-    int rc = m->pose_h.ensure((int64_t)b_end, 1 << 16, ctx->stream);
-    if (rc) return rc;
-    char* const pose_h = m->pose_h.host;
-    const char* const pose_h_dev = m->pose_h.dev;
-    double* Ps_ext = reinterpret_cast<double*>(pose_h + b_Ps);
-    volatile uint64_t* out = reinterpret_cast<volatile uint64_t*>(pose_h + b_out);
-    std::memcpy(Ps_ext, base, sizeof(double) * 12 * (size_t)n);
-    if (Q > 0) std::memcpy(Ps_ext + 12 * (size_t)n, moved_Ps, sizeof(double) * 12 * (size_t)Q);
-    std::memcpy(pose_h + b_off, off, sizeof(int32_t) * (size_t)(K + 1));
-    if (Q > 0) std::memcpy(pose_h + b_views, views, sizeof(int32_t) * (size_t)Q);
-    std::atomic_thread_fence(std::memory_order_seq_cst);
-
-    rc = m->pose_PinvTs_d.ensure(12 * (n + Q), ctx->stream);
-    if (!rc) rc = m->pose_Cs_d.ensure(4 * (n + Q), ctx->stream);
-    if (!rc) rc = m->pose_idx_d.ensure(4 * std::max<int64_t>(entries, 1), ctx->stream);
-    if (!rc) rc = m->pose_records_d.ensure(std::max<int64_t>(entries, 1), ctx->stream);
+    volatile uint64_t* out = nullptr;
+    double* out_dev = nullptr;
+    int rc = stage_pose_grid(m, base, K, off, views, moved_Ps, K, &out, &out_dev);
     if (!rc) rc = m->pose_values_d.ensure(std::max<int64_t>(entries, 1), ctx->stream);
     if (!rc) rc = m->pose_partial_d.ensure((int64_t)K * SUM_SLICES, ctx->stream);
-    if (!rc) rc = m->pose_lists_d.ensure((int64_t)K + 1 + std::max(Q, 1), ctx->stream);
     if (rc) return rc;
 
     EccPairParams p;
     rc = fill_pair_params(m, &p, n_pairs, /*need_e1=*/false);  // the sampling mode of an all-pairs evaluation
     if (rc) return rc;
-    PoseLists in = {reinterpret_cast<const int32_t*>(pose_h_dev + b_off), reinterpret_cast<const int32_t*>(pose_h_dev + b_views)};
-    // index tuples + lists (K workgroups) and E1 of the n + Q extended matrices (the workgroups behind them): one launch
-    const unsigned e1_blocks = entries > 0 ? (unsigned)((n + Q + 63) / 64) : 0u;
-    hipLaunchKernelGGL(pose_list_kernel, dim3((unsigned)K + e1_blocks), dim3(256), 0, ctx->stream, in, (int)n, K, Q, m->pose_idx_d.ptr,
-                       m->pose_lists_d.ptr, reinterpret_cast<const double*>(pose_h_dev + b_Ps), m->pose_PinvTs_d.ptr, m->pose_Cs_d.ptr);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_pose_list(m, K, Q, K));
     if (entries > 0) {
         p.PinvTs = m->pose_PinvTs_d.ptr;
         p.Cs = m->pose_Cs_d.ptr;
@@ -295,7 +345,7 @@ int run_batch(ecc_metric* m, const double* base, const float* base_vals_d, int K
         HIP_TRY(ecc_launch_k01(&p, ctx->stream));
         HIP_TRY(launch_pairs_timed(ctx, &p));
     }
-    return sum_poses(m, base_vals_d, K, Q, out, reinterpret_cast<double*>(m->pose_h.dev + b_out), sums);
+    return sum_poses(m, base_vals_d, K, Q, out, out_dev, sums);
 }
 
 // The poses first, first + stride, ... of Ps_batch one after the other on the context's stream, two deep: pose k + 1's
@@ -427,6 +477,8 @@ int evaluate_deltas(ecc_metric* m, int n_poses, const int32_t* off, const int32_
     return ECC_OK;
 }
 
+}  // namespace
+namespace ecc_internal {
 int check_lists(const ecc_metric* m, int n_poses, const int32_t* off, const int32_t* views)
 {
     if (off[0] != 0) return fail(ECC_ERR_INVALID_ARGUMENT, "moved_offsets[0] must be 0");
@@ -440,8 +492,7 @@ int check_lists(const ecc_metric* m, int n_poses, const int32_t* off, const int3
     }
     return ECC_OK;
 }
-
-}  // namespace
+}  // namespace ecc_internal
 
 ECC_EXPORT int ecc_metric_set_pose_batching(ecc_metric* m, int on)
 {

@@ -7,7 +7,9 @@
 //
 // The launches: E1 (if the device geometry is behind the matrices), k01_kernel over all pairs into the Gram call's records (scratch
 // of the Gram-family calls alone), pairs_weighted_kernel, sum_gram_kernel over the two columns, the copies.  The metric's kept
-// records, kept values and pose-batch scratch are not touched.
+// records, kept values and pose-batch scratch are not touched.  The index-list and pose-delta forms are in ecc_weighted_poses.hip; they
+// take the base's columns from weighted_base_columns below.
+// Not here: base columns kept between calls; full-matrices, strided, group, RCCL and transform forms; an incremental mode.
 #include "ecc_capi_internal.h"
 #include "ecc_sum_order.h"
 
@@ -17,15 +19,23 @@ extern "C" hipError_t ecc_launch_pairs_weighted(const EccPairParams* p, const Ec
 extern "C" hipError_t ecc_launch_sum_gram(const float* values_d, long long col_stride, long long count, int n_columns, int n_slices,
                                           double* partial_d, hipStream_t stream);
 
-ECC_EXPORT int ecc_metric_evaluate_weighted(ecc_metric* m, double* value, double* coverage, float* pair_terms)
+namespace ecc_internal {
+// What every weighted call needs of the metric (after its own null checks), before the device is touched.
+int weighted_check(const ecc_metric* m)
 {
-    if (!m) return fail(ECC_ERR_INVALID_ARGUMENT, "metric is null");
-    if (!value) return fail(ECC_ERR_INVALID_ARGUMENT, "value is null");
     if (m->n_views < 1) return fail(ECC_ERR_INVALID_ARGUMENT, "projection matrices have not been set");
     if (m->n_views < 2) return fail(ECC_ERR_INVALID_ARGUMENT, "need at least two views (the reference divides 0/0 here)");
     if ((int64_t)m->dtrs.size() != (int64_t)2 * m->n_views)
         return fail(ECC_ERR_INVALID_ARGUMENT, "the metric must hold 2 * n_views Radon intermediates: the data of every view, then its line weights");
     if (m->use_corr) return fail(ECC_ERR_UNSUPPORTED, "line weights are not defined for the correlation cost");
+    return ECC_OK;
+}
+
+// {c, u} of all pairs at the current matrices: everything of ecc_metric_evaluate_weighted up to and including its pair launch.
+// The two columns are in m->gram_values_d, g->col_stride apart, once the stream gets there; *p and *g are the launch as it was made
+// (ecc_weighted_poses.hip launches the grids of its poses with the same parameters).
+int weighted_base_columns(ecc_metric* m, EccPairParams* p_out, EccWeightedParams* g_out)
+{
     ecc_ctx* ctx = m->ctx;
     int rc = set_device(ctx);
     if (rc) return rc;
@@ -35,7 +45,7 @@ ECC_EXPORT int ecc_metric_evaluate_weighted(ecc_metric* m, double* value, double
 
     // (as the first large all-pairs evaluation does: whether this scan's pairs would read row-quad copies; the same bits either way)
     if (!m->quads_decided && n_pairs >= 32768) decide_quad_copies(m);
-    EccPairParams p;
+    EccPairParams& p = *p_out;
     rc = fill_pair_params(m, &p, n_pairs, /*need_e1=*/false);  // the sampling mode of an all-pairs evaluation
     if (rc) return rc;
     rc = m->gram_records_d.ensure(n_pairs, ctx->stream);
@@ -50,7 +60,7 @@ ECC_EXPORT int ecc_metric_evaluate_weighted(ecc_metric* m, double* value, double
     p.records = m->gram_records_d.ptr;
     HIP_TRY(ecc_launch_k01(&p, ctx->stream));
     const int64_t paired_bytes = (int64_t)(m->n_alpha + 1) * m->pitch * 2 * (int64_t)sizeof(float);
-    EccWeightedParams g;
+    EccWeightedParams& g = *g_out;
     g.paired_channel_bytes = n * paired_bytes;
     g.quad_channel_bytes = n * m->quad_floats * (int64_t)sizeof(float);
     g.values = m->gram_values_d.ptr;
@@ -61,6 +71,24 @@ ECC_EXPORT int ecc_metric_evaluate_weighted(ecc_metric* m, double* value, double
         HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
         ctx->ev_valid[0] = true;
     }
+    return ECC_OK;
+}
+}  // namespace ecc_internal
+
+ECC_EXPORT int ecc_metric_evaluate_weighted(ecc_metric* m, double* value, double* coverage, float* pair_terms)
+{
+    if (!m) return fail(ECC_ERR_INVALID_ARGUMENT, "metric is null");
+    if (!value) return fail(ECC_ERR_INVALID_ARGUMENT, "value is null");
+    int rc = weighted_check(m);
+    if (rc) return rc;
+    ecc_ctx* ctx = m->ctx;
+    EccPairParams p;
+    EccWeightedParams g;
+    rc = weighted_base_columns(m, &p, &g);
+    if (rc) return rc;
+    const int T = 2;
+    const int64_t n = m->n_views, n_pairs = n * (n - 1) / 2;
+    const int64_t col_stride = g.col_stride;
     // both columns in the order an all-pairs evaluation of n_pairs values is added in (ecc_sum_order.h)
     const int n_slices = ecc_sum::slices(n_pairs, m->sum_scratch_d.ptr != nullptr);
     HIP_TRY(ecc_launch_sum_gram(m->gram_values_d.ptr, col_stride, n_pairs, T, n_slices, m->gram_partial_d.ptr, ctx->stream));

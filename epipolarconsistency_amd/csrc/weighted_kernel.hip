@@ -20,8 +20,9 @@
 // gathers: one wave per pair, the record in scalar registers, the same dispatch over the record's degree and the slab size, per-lane
 // float64 sums in the same trip order, the same wave tree.  Plain vector loads and stores only: no atomics, no inline assembly of
 // its own.
-// Not here (include/ecc_hip.h): index lists, pose-delta, pose-batch, transform, range, group and RCCL forms; weights under the
-// correlation cost; a 1 / (sigma0^2 + sigma1^2) variance form; a per-sample robust loss.
+// Index lists and pose deltas launch these kernels over their own records (ecc_weighted_poses.hip).
+// Not here (include/ecc_hip.h): full-matrices pose batches, transform, range, group and RCCL forms; weights under the correlation
+// cost; a 1 / (sigma0^2 + sigma1^2) variance form; a per-sample robust loss.
 #include <hip/hip_runtime.h>
 #include <float.h>
 
@@ -275,13 +276,14 @@ __global__ __launch_bounds__(PK_THREADS) void pairs_weighted_reference_kernel(Ec
 
 }  // namespace
 
-// The two entries {c, u} of every pair of the all-pairs launch p (records of ecc_launch_k01 for the same parameters, earlier on the
-// same stream; first = 0, no index list, no slots) into g->values; the metric's dtrs are the data of the n_views views, then their
-// line weights.
+// The two entries {c, u} of every pair of the launch p (records of ecc_launch_k01 for the same parameters, earlier on the same
+// stream; first = 0, no slots) into g->values; the metric's dtrs are the data of the n_views views, then their line weights.
+// p->indices may be set (an index list, a pose batch's grid): the kernels do not read it, the record carries both Radon-intermediate
+// indices, which must lie in [0, n_views) -- the weights of a sample come from dtr n_views + that index.
 extern "C" hipError_t ecc_launch_pairs_weighted(const EccPairParams* p, const EccWeightedParams* g, hipStream_t stream)
 {
     if (p->count <= 0) return hipSuccess;
-    if (p->use_corr || p->indices || p->record_slots || p->skip_enabled || !g->values || g->col_stride < p->count || (g->col_stride & 3))
+    if (p->use_corr || p->record_slots || p->skip_enabled || !g->values || g->col_stride < p->count || (g->col_stride & 3))
         return hipErrorInvalidValue;
     if (p->reference_arithmetic) {
         if (p->reference_split > 1)

@@ -579,9 +579,48 @@ int ecc_metric_evaluate_view_hessian(ecc_metric* m, int n_channels, double* hess
  *     set or fewer than two views, n_dtrs != 2 * n_views.  use_corr set: ECC_ERR_UNSUPPORTED.
  * Launches (csrc/ecc_weighted.hip, csrc/weighted_kernel.hip): the record kernel over all pairs, pairs_weighted_kernel -- one wave per
  * pair, the position arithmetic of a kappa step once, 8 gathers --, one launch for the two sums.
- * Out of scope: index lists, pose-delta, pose-batch, transform, range, group and RCCL forms; weights under use_corr; a
+ * Index lists and pose deltas: ecc_metric_evaluate_weighted_pairs, ecc_metric_evaluate_weighted_pose_deltas below.
+ * Out of scope: full-matrices pose batches, transform, range, group and RCCL forms; weights under use_corr; a
  * 1 / (sigma0^2 + sigma1^2) variance form; a per-sample robust loss. */
 int ecc_metric_evaluate_weighted(ecc_metric* m, double* value, double* coverage, float* pair_terms);
+
+/* The weighted metric for pose optimisers (csrc/ecc_weighted_poses.hip): a tracker that scores one frame against
+ * reference views has an index list, an optimiser step with a finite-difference gradient has a batch of poses that each move a few
+ * views.  Both need a metric as ecc_metric_evaluate_weighted does: n_dtrs == 2 * n_views (data, then line weights), no use_corr.
+ *
+ * ecc_metric_evaluate_weighted_pairs: idx4 holds n_pairs tuples (P0, P1, D0, D1) as for ecc_metric_evaluate_pairs.  P* index the
+ * current matrices.  D* index the DATA intermediates and must lie in [0, n_views); the weights of a sample come from dtr
+ * n_views + D* -- the weight follows the data index, never the matrix index.  A tuple with P0 == P1 has no samples: {c, u} =
+ * {0, 1}.  The sampling mode resolves from n_pairs of the LIST, as ecc_metric_evaluate_pairs resolves it (ECC_SAMPLING_AUTO: up to
+ * 512 tuples use the reference arithmetic).  Per tuple c and u are those of ecc_metric_evaluate_weighted's pair; pair_terms
+ * (nullable): n_pairs x 2 floats in list order.  *value = sum c / sum u, *coverage (nullable) = sum u / n_pairs, both sums in the
+ * order of csrc/ecc_sum_order.h for n_pairs values; sum u == 0: 0, 0 and ECC_OK.  n_pairs == 0: ECC_OK, nothing written.
+ * With tuples (i, j, i, j) the rows have the bits of ecc_metric_evaluate_weighted's rows of those pairs under the same resolved
+ * mode; with every weight 1.0f the c column and value have the bits of ecc_metric_evaluate_pairs of the same list.
+ * Launches: the record kernel with the list, the weighted pair kernel, one launch for the two sums, the copies.
+ *
+ * ecc_metric_evaluate_weighted_pose_deltas: the lists of ecc_metric_evaluate_pose_deltas -- pose k = the CURRENT matrices with the
+ * views moved_views[moved_offsets[k] .. moved_offsets[k + 1]) (strictly ascending) replaced by moved_Ps[12 q ..]; n_poses < 1:
+ * ECC_OK.  values[k] and coverages[k] (coverages nullable) have THE BITS of ecc_metric_set_projections(pose k) +
+ * ecc_metric_evaluate_weighted (tests/test_gpu_weighted_poses.py).  Per call: {c, u} of all pairs at the current matrices (the
+ * launches of ecc_metric_evaluate_weighted; recomputed on every call), then per batch ONE launch that lists the pairs and does E1
+ * of the moved matrices, ONE record launch and ONE weighted pair launch over the (pose, moved view) x partner grid, and ONE
+ * segmented sum that adds, per pose and column, the base's values with the pose's own substituted in the order of
+ * csrc/ecc_sum_order.h.  A pose with more than 32 moved views, one that moves view 0 under the automatic object radius and changes
+ * it, and every pose after ecc_metric_set_pose_batching(m, 0) is evaluated the sequential way inside the call (same bits);
+ * ecc_metric_last_batched_poses reports how many went through the batch.  Calls of more than 2^20 grid entries run as several
+ * batches over the same base columns.
+ *
+ * Both: errors are returned before anything is launched or written.  ECC_ERR_INVALID_ARGUMENT: m == NULL (checked first); a null
+ * value / values / moved_offsets / idx4 (with n_pairs > 0); null list arrays when moved_offsets[n_poses] > 0; no matrices set or
+ * fewer than two views; n_dtrs != 2 * n_views; a bad list or tuple.  ECC_ERR_UNSUPPORTED under use_corr.  The calls change nothing a
+ * later call can see: current matrices, kept records, the kept values of the pose-delta mode and of the pose batch.  (They rewrite
+ * the pose batch's per-batch scratch and ecc_metric_evaluate_gram's scratch, as every call of those families does.)
+ * Not built: base columns kept between calls; the full-matrices, strided, group and RCCL forms; the transform form; the
+ * incremental (ecc_metric_set_incremental) mode for the weighted value; a one-launch small path for weighted lists. */
+int ecc_metric_evaluate_weighted_pairs(ecc_metric* m, const int32_t* idx4, int n_pairs, double* value, double* coverage, float* pair_terms);
+int ecc_metric_evaluate_weighted_pose_deltas(ecc_metric* m, int n_poses, const int32_t* moved_offsets, const int32_t* moved_views,
+                                             const double* moved_Ps, double* values, double* coverages);
 
 /* n_transforms rigid source-to-target transforms of two scans in one call: the registration of two scans (ref:
  * tools/Registration/Registration3D3D.hxx:56-62, :91-110 -- a cost call multiplies every source matrix by one 4x4 transform,
