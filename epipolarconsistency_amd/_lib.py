@@ -88,6 +88,7 @@ SIGNATURES = {
     "ecc_metric_evaluate_weighted_pairs": (_i, [_vp, _vp, _i, _pd, _pd, _vp]),
     "ecc_metric_evaluate_weighted_pose_deltas": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "ecc_metric_evaluate_transforms": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
+    "ecc_metric_evaluate_weighted_transforms": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
     "ecc_metric_last_batched_transforms": (_i, [_vp, C.POINTER(_i64)]),
     "ecc_host_compose_transform": (None, [_vp, _vp, _vp]),
     "ecc_metric_evaluate_range": (_i, [_vp, _i64, _i64, _vp, _pd]),

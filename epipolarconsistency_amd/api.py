@@ -836,8 +836,32 @@ class MetricRadonIntermediate:
                                                         C.c_void_p(pairs.ctypes.data) if (want_pairs and pairs.size) else None))
         return (means, pairs) if want_pairs else means
 
+    def evaluate_weighted_transforms(self, n_source, Ts, want_pairs=False):
+        """ecc_metric_evaluate_weighted_transforms: evaluate_transforms for the metric with per-line weights (evaluate_weighted: the
+        metric holds the data of every view, then its line weights; the weights follow the data, not the transformed matrix).  n_source
+        and Ts as for evaluate_transforms.  Returns (values, coverages) = per transform (sum c / sum u, sum u / (n_source n_target))
+        over the cross pairs -- with want_pairs (values, coverages, pairs), pairs (K, n_target, n_source, 2) float32 rows {c, u}: every
+        number bit-identical to setProjectionMatrices(composed) + evaluate_weighted_pairs(the cross list) per transform; the current
+        matrices stay."""
+        T = np.asarray(Ts, dtype=np.float64)
+        if T.ndim == 2 and T.shape == (4, 4):
+            T = T[None]
+        if T.ndim != 3 or T.shape[1:] != (4, 4):
+            raise ValueError("Ts must be (K, 4, 4)")
+        flat = np.ascontiguousarray(T.transpose(0, 2, 1)).reshape(-1, 16)  # column-major per transform
+        n_source = int(n_source)
+        K, n = len(flat), self.getNumberOfProjetions()
+        values, coverages = np.zeros(K, np.float64), np.zeros(K, np.float64)
+        pairs = np.zeros((K, max(n - n_source, 0), max(n_source, 0), 2), np.float32) if want_pairs else None
+        check(_lib.lib().ecc_metric_evaluate_weighted_transforms(self._h, n_source, K, C.c_void_p(flat.ctypes.data if K else 0),
+                                                                 C.c_void_p(values.ctypes.data if K else 0),
+                                                                 C.c_void_p(coverages.ctypes.data if K else 0),
+                                                                 C.c_void_p(pairs.ctypes.data) if (want_pairs and pairs.size) else None))
+        return (values, coverages, pairs) if want_pairs else (values, coverages)
+
     def last_batched_transforms(self):
-        """Transforms of the last evaluate_transforms call that went through the batch (0: the sequential way)."""
+        """Transforms of the last evaluate_transforms / evaluate_weighted_transforms call that went through the batch (0: the
+        sequential way)."""
         v = C.c_int64(0)
         check(_lib.lib().ecc_metric_last_batched_transforms(self._h, C.byref(v)))
         return v.value

@@ -896,6 +896,25 @@ public:
                                                                coverages ? coverages->data() : 0x0));
     }
 
+    /// Not in the reference: ecc_metric_evaluate_weighted_transforms -- evaluateTransforms for the metric with per-line weights
+    /// (intermediates as for evaluateWeighted; n_source and Ts as for evaluateTransforms).  values[k] = sum c / sum u over the
+    /// n_source x n_target cross pairs under Ts[k]; coverages (nullable): sum u / (n_source n_target) per transform; pair_terms
+    /// (nullable): Ts.size() x n_target x n_source x 2 floats, per transform its rows {c, u} with the source index fast.  Every number
+    /// is bit-identical to Ps[i] * Ts[k] by ecc_host_compose_transform, setProjectionMatrices and evaluateWeightedPairs of the cross
+    /// list per transform; the current matrices stay (ecc_hip.h).  Single device only.
+    void evaluateWeightedTransforms(int n_source, const std::vector<Geometry::RP3Homography>& Ts, std::vector<double>& values,
+                                    std::vector<double>* coverages = 0x0, float* pair_terms = 0x0)
+    {
+        if (m_gh) throw std::runtime_error("evaluateWeightedTransforms: not available on a device group");
+        values.assign(Ts.size(), 0.0);
+        if (coverages) coverages->assign(Ts.size(), 0.0);
+        std::vector<double> flat(16 * Ts.size());
+        for (size_t k = 0; k < Ts.size(); ++k)
+            for (int q = 0; q < 16; ++q) flat[16 * k + q] = Ts[k].data()[q];
+        detail::check(ecc_metric_evaluate_weighted_transforms(m_h, n_source, (int)Ts.size(), flat.data(), values.data(),
+                                                              coverages ? coverages->data() : 0x0, pair_terms));
+    }
+
     /// Not in the reference: ecc_metric_evaluate_view_hessian -- the quadratic form of the per-view channel coefficients as a matrix:
     /// metric(a) = a^T H a, gradient 2 H a, with the index c * n_views + i of evaluateViewCoefficients' coeffs.  Intermediates as for
     /// evaluateGram.  H: (n_views n_channels)^2, symmetric bit for bit; pair_blocks (nullable): n_pairs x (K (K + 1) + K^2) doubles,

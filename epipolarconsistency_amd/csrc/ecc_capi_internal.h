@@ -57,6 +57,7 @@ extern "C" hipError_t ecc_launch_sum_pairs(const float* vals, long long count, d
 extern "C" hipError_t ecc_launch_sum_pairs_to_host(const float* vals, long long count, double* out, float* values_host, hipStream_t stream);
 extern "C" hipError_t ecc_launch_publish_scalar(const double* value_d, double* host_slot_dev, hipStream_t stream);
 extern "C" size_t ecc_sum_scratch_bytes();
+extern "C" hipError_t ecc_launch_pairs_weighted(const EccPairParams* p, const EccWeightedParams* g, hipStream_t stream);
 extern "C" hipError_t ecc_launch_e1(const double* Ps_d, int n, float* PinvTs_d, float* Cs_d, hipStream_t stream);
 
 #ifndef ECC_POSE_BATCH_MAX_ENTRIES
@@ -442,6 +443,12 @@ int stage_pose_grid(ecc_metric* m, const double* base, int K, const int32_t* off
 hipError_t launch_pose_list(ecc_metric* m, int K, int Q, int result_words);
 void arm_pose_results(volatile uint64_t* out, int K);
 int wait_pose_results(ecc_ctx* ctx, volatile uint64_t* out, int K, double* sums);
+// ecc_transforms.hip, for the batches of ecc_weighted_transforms.hip as well: the object radius the sequential calls would take for a
+// transform; the host half of a batch's grid (pinned block, device arrays) and the launch of transform_list_kernel over it
+float radius_of_transform(const ecc_metric* m, const double* base, const double* T);
+int stage_transform_grid(ecc_metric* m, const double* base, int n_source, int K, const double* Ts, int result_words,
+                         volatile uint64_t** out, double** out_dev);
+hipError_t launch_transform_list(ecc_metric* m, int n_source, int K, long long seg, int result_words);
 // ecc_weighted.hip: the argument checks of the weighted calls; {c, u} of all pairs at the current matrices into gram_values_d
 // (p, g: the launch as it was made)
 int weighted_check(const ecc_metric* m);
@@ -455,6 +462,20 @@ inline hipError_t launch_pairs_timed(ecc_ctx* ctx, const EccPairParams* p, const
         if (e != hipSuccess) return e;
     }
     const hipError_t e = x ? ecc_launch_small_eval(p, x, ctx->stream) : ecc_launch_pairs(p, ctx->stream);
+    if (e != hipSuccess || !ctx->timing) return e;
+    const hipError_t e1 = hipEventRecord(ctx->ev[1], ctx->stream);
+    if (e1 == hipSuccess) ctx->ev_valid[0] = true;
+    return e1;
+}
+
+// The weighted pair launch (weighted_kernel.hip) between the same events.
+inline hipError_t launch_weighted_timed(ecc_ctx* ctx, const EccPairParams* p, const EccWeightedParams* g)
+{
+    if (ctx->timing) {
+        const hipError_t e = hipEventRecord(ctx->ev[0], ctx->stream);
+        if (e != hipSuccess) return e;
+    }
+    const hipError_t e = ecc_launch_pairs_weighted(p, g, ctx->stream);
     if (e != hipSuccess || !ctx->timing) return e;
     const hipError_t e1 = hipEventRecord(ctx->ev[1], ctx->stream);
     if (e1 == hipSuccess) ctx->ev_valid[0] = true;

@@ -131,6 +131,23 @@ constexpr uint64_t TRANSFORM_PENDING = 0x7ff8ecc0dead0003ull;  // a NaN payload 
 
 size_t align64(size_t x) { return (x + 63) & ~(size_t)63; }
 
+// the pinned block of a batch: base matrices | transforms | results | radii (byte offsets)
+struct TransformBlock {
+    size_t Ps, Ts, out, radii, end;
+};
+TransformBlock transform_block(int64_t n, int K, int result_words)
+{
+    TransformBlock b;
+    b.Ps = 0;
+    b.Ts = align64(sizeof(double) * 12 * (size_t)n);
+    b.out = b.Ts + align64(sizeof(double) * 16 * (size_t)K);
+    b.radii = b.out + align64(sizeof(double) * (size_t)result_words);
+    b.end = b.radii + align64(sizeof(float) * (size_t)K);
+    return b;
+}
+
+}  // namespace
+namespace ecc_internal {
 // The float the launches of ecc_metric_set_projections(composed matrices) would take for their object radius
 // (fill_pair_params): the metric's fixed one, or the automatic one of the composed view 0.
 float radius_of_transform(const ecc_metric* m, const double* base, const double* T)
@@ -141,50 +158,78 @@ float radius_of_transform(const ecc_metric* m, const double* base, const double*
     return (float)ecc_host::object_radius(P0, m->n_u, m->n_v);
 }
 
-// One batch: K transforms Ts (16 doubles each) of the base matrices (n x 12).  sums[k]: the float64 total of transform k's
-// n_source n_target values; values (nullable, host): K x count floats.
-int run_batch(ecc_metric* m, const double* base, int n_source, int K, const double* Ts, double* sums, float* values)
+// The host half of a batch's grid: the pinned block -- base matrices | the K transforms | result_words result slots | under the
+// automatic object radius the K radii -- is filled, and the device arrays of the extended geometry, the index grid, its value slots
+// and records (and the radii) have room.  *out / *out_dev: host and device address of the result slots, which the caller arms.
+int stage_transform_grid(ecc_metric* m, const double* base, int n_source, int K, const double* Ts, int result_words,
+                         volatile uint64_t** out, double** out_dev)
 {
     ecc_ctx* ctx = m->ctx;
-    const int64_t n = m->n_views, n_target = n - n_source, count = (int64_t)n_source * n_target;
-    const int64_t seg = (count + 3) & ~(int64_t)3, entries = count * K, ext = n + (int64_t)K * n_source;
+    const int64_t n = m->n_views, entries = (int64_t)n_source * (n - n_source) * K, ext = n + (int64_t)K * n_source;
     const bool per_transform_radius = !(m->object_radius_mm > 0);
-    // the pinned block: base matrices | transforms | results | radii
-    const size_t b_Ps = 0, b_Ts = align64(sizeof(double) * 12 * (size_t)n), b_out = b_Ts + align64(sizeof(double) * 16 * (size_t)K),
-                 b_radii = b_out + align64(sizeof(double) * (size_t)K), b_end = b_radii + align64(sizeof(float) * (size_t)K);
-    int rc = m->pose_h.ensure((int64_t)b_end, 1 << 16, ctx->stream);
+    const TransformBlock b = transform_block(n, K, result_words);
+    int rc = m->pose_h.ensure((int64_t)b.end, 1 << 16, ctx->stream);
     if (rc) return rc;
     char* const h = m->pose_h.host;
-    const char* const h_dev = m->pose_h.dev;
-    volatile uint64_t* out = reinterpret_cast<volatile uint64_t*>(h + b_out);
-    float* radii_h = reinterpret_cast<float*>(h + b_radii);
-    std::memcpy(h + b_Ps, base, sizeof(double) * 12 * (size_t)n);
-    std::memcpy(h + b_Ts, Ts, sizeof(double) * 16 * (size_t)K);
+    float* radii_h = reinterpret_cast<float*>(h + b.radii);
+    std::memcpy(h + b.Ps, base, sizeof(double) * 12 * (size_t)n);
+    std::memcpy(h + b.Ts, Ts, sizeof(double) * 16 * (size_t)K);
     if (per_transform_radius)
         for (int k = 0; k < K; ++k) radii_h[k] = radius_of_transform(m, base, Ts + 16 * (size_t)k);
-    for (int k = 0; k < K; ++k) out[k] = TRANSFORM_PENDING;
     std::atomic_thread_fence(std::memory_order_seq_cst);
+    *out = reinterpret_cast<volatile uint64_t*>(h + b.out);
+    *out_dev = reinterpret_cast<double*>(m->pose_h.dev + b.out);
 
     rc = m->pose_PinvTs_d.ensure(12 * ext, ctx->stream);
     if (!rc) rc = m->pose_Cs_d.ensure(4 * ext, ctx->stream);
     if (!rc) rc = m->pose_idx_d.ensure(4 * entries, ctx->stream);
     if (!rc) rc = m->pose_lists_d.ensure(entries, ctx->stream);  // the value slots
     if (!rc) rc = m->pose_records_d.ensure(entries, ctx->stream);
-    if (!rc) rc = m->pose_values_d.ensure(seg * K, ctx->stream);
-    if (!rc) rc = m->pose_partial_d.ensure((int64_t)K * SUM_SLICES, ctx->stream);
     if (!rc && per_transform_radius) rc = m->transform_radii_d.ensure(K, ctx->stream);
+    return rc;
+}
+
+// transform_list_kernel over the block stage_transform_grid has just filled (the same n_source, K and result_words); seg: the
+// distance of two transforms' value slots.
+hipError_t launch_transform_list(ecc_metric* m, int n_source, int K, long long seg, int result_words)
+{
+    const int64_t n = m->n_views, n_target = n - n_source, entries = (int64_t)n_source * n_target * K, ext = n + (int64_t)K * n_source;
+    const bool per_transform_radius = !(m->object_radius_mm > 0);
+    const TransformBlock b = transform_block(n, K, result_words);
+    const char* const h_dev = m->pose_h.dev;
+    const unsigned e1_blocks = (unsigned)((ext + 63) / 64), idx_blocks = (unsigned)((entries + 255) / 256);
+    hipLaunchKernelGGL(transform_list_kernel, dim3(e1_blocks + idx_blocks), dim3(256), 0, m->ctx->stream,
+                       reinterpret_cast<const double*>(h_dev + b.Ps), reinterpret_cast<const double*>(h_dev + b.Ts), (int)n, n_source,
+                       (int)n_target, K, e1_blocks, seg, m->pose_idx_d.ptr, m->pose_lists_d.ptr, m->pose_PinvTs_d.ptr,
+                       m->pose_Cs_d.ptr, per_transform_radius ? reinterpret_cast<const float*>(h_dev + b.radii) : nullptr,
+                       m->transform_radii_d.ptr);
+    return hipGetLastError();
+}
+}  // namespace ecc_internal
+namespace {
+
+// One batch: K transforms Ts (16 doubles each) of the base matrices (n x 12).  sums[k]: the float64 total of transform k's
+// n_source n_target values; values (nullable, host): K x count floats.
+int run_batch(ecc_metric* m, const double* base, int n_source, int K, const double* Ts, double* sums, float* values)
+{
+    ecc_ctx* ctx = m->ctx;
+    const int64_t n = m->n_views, n_target = n - n_source, count = (int64_t)n_source * n_target;
+    const int64_t seg = (count + 3) & ~(int64_t)3, entries = count * K;
+    const bool per_transform_radius = !(m->object_radius_mm > 0);
+    volatile uint64_t* out = nullptr;
+    double* out_dev = nullptr;
+    int rc = stage_transform_grid(m, base, n_source, K, Ts, K, &out, &out_dev);
+    if (rc) return rc;
+    for (int k = 0; k < K; ++k) out[k] = TRANSFORM_PENDING;
+    std::atomic_thread_fence(std::memory_order_seq_cst);
+    rc = m->pose_values_d.ensure(seg * K, ctx->stream);
+    if (!rc) rc = m->pose_partial_d.ensure((int64_t)K * SUM_SLICES, ctx->stream);
     if (rc) return rc;
 
     EccPairParams p;
     rc = fill_pair_params(m, &p, count, /*need_e1=*/false);  // the sampling mode of a list of `count` pairs
     if (rc) return rc;
-    const unsigned e1_blocks = (unsigned)((ext + 63) / 64), idx_blocks = (unsigned)((entries + 255) / 256);
-    hipLaunchKernelGGL(transform_list_kernel, dim3(e1_blocks + idx_blocks), dim3(256), 0, ctx->stream,
-                       reinterpret_cast<const double*>(h_dev + b_Ps), reinterpret_cast<const double*>(h_dev + b_Ts), (int)n, n_source,
-                       (int)n_target, K, e1_blocks, (long long)seg, m->pose_idx_d.ptr, m->pose_lists_d.ptr, m->pose_PinvTs_d.ptr,
-                       m->pose_Cs_d.ptr, per_transform_radius ? reinterpret_cast<const float*>(h_dev + b_radii) : nullptr,
-                       m->transform_radii_d.ptr);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_transform_list(m, n_source, K, (long long)seg, K));
     p.PinvTs = m->pose_PinvTs_d.ptr;
     p.Cs = m->pose_Cs_d.ptr;
     p.indices = m->pose_idx_d.ptr;
@@ -198,7 +243,6 @@ int run_batch(ecc_metric* m, const double* base, int n_source, int K, const doub
     HIP_TRY(launch_pairs_timed(ctx, &p));
     // ecc_metric_evaluate_pairs' choice for a list of `count` values (its one-launch path's host sum is the one-slice order)
     const int slices = ecc_sum::slices(count, m->sum_scratch_d.ptr != nullptr);
-    double* out_dev = reinterpret_cast<double*>(m->pose_h.dev + b_out);
     hipLaunchKernelGGL(slices == 1 ? sum_transforms_kernel<1> : sum_transforms_kernel<SUM_SLICES>, dim3((unsigned)slices, (unsigned)K),
                        dim3(SUM_THREADS), 0, ctx->stream, m->pose_values_d.ptr, (long long)count, (long long)seg, m->pose_partial_d.ptr, out_dev);
     HIP_TRY(hipGetLastError());

@@ -9,13 +9,13 @@
 // of the Gram-family calls alone), pairs_weighted_kernel, sum_gram_kernel over the two columns, the copies.  The metric's kept
 // records, kept values and pose-batch scratch are not touched.  The index-list and pose-delta forms are in ecc_weighted_poses.hip; they
 // take the base's columns from weighted_base_columns below.
-// Not here: base columns kept between calls; full-matrices, strided, group, RCCL and transform forms; an incremental mode.
+// The transform form is in ecc_weighted_transforms.hip.
+// Not here: base columns kept between calls; full-matrices, strided, group and RCCL forms; an incremental mode.
 #include "ecc_capi_internal.h"
 #include "ecc_sum_order.h"
 
 using namespace ecc_internal;
 
-extern "C" hipError_t ecc_launch_pairs_weighted(const EccPairParams* p, const EccWeightedParams* g, hipStream_t stream);
 extern "C" hipError_t ecc_launch_sum_gram(const float* values_d, long long col_stride, long long count, int n_columns, int n_slices,
                                           double* partial_d, hipStream_t stream);
 

@@ -16,7 +16,7 @@
 // (tests/test_gpu_weighted_poses.py).  What the batch does not take is evaluated that way inside the call.
 // Not here: base columns kept between calls (a stale column is a silently wrong result; keeping them needs change tracking over
 // matrices, parameters, sampling mode, quad copies and ecc_metric_refresh_dtrs); the full-matrices, strided, group and RCCL forms;
-// the transform form; an incremental mode for the weighted value; a one-launch small path for weighted lists.
+// an incremental mode for the weighted value; a one-launch small path for weighted lists.
 #include "ecc_capi_internal.h"
 #include "ecc_sum_order.h"
 
@@ -26,7 +26,6 @@ using namespace ecc_internal;
 #define ECC_POSE_BATCH_MAX_MOVED 32  // (ecc_poses.hip)
 #endif
 
-extern "C" hipError_t ecc_launch_pairs_weighted(const EccPairParams* p, const EccWeightedParams* g, hipStream_t stream);
 extern "C" hipError_t ecc_launch_sum_gram(const float* values_d, long long col_stride, long long count, int n_columns, int n_slices,
                                           double* partial_d, hipStream_t stream);
 extern "C" hipError_t ecc_launch_sum_weighted_poses(const float* base_cols, long long base_stride, long long count, int n, int Q,
@@ -38,19 +37,6 @@ namespace {
 // poses per batch: the sum's grid is slices x poses x 2 columns, half a million workgroups at most
 constexpr size_t WEIGHTED_BATCH_MAX_POSES = (1 << 19) / (2 * ecc_sum::SLICES);
 static_assert(WEIGHTED_BATCH_MAX_POSES < 65536, "poses are the y dimension of sum_weighted_poses_kernel's grid");
-
-hipError_t launch_weighted_timed(ecc_ctx* ctx, const EccPairParams* p, const EccWeightedParams* g)
-{
-    if (ctx->timing) {
-        const hipError_t e = hipEventRecord(ctx->ev[0], ctx->stream);
-        if (e != hipSuccess) return e;
-    }
-    const hipError_t e = ecc_launch_pairs_weighted(p, g, ctx->stream);
-    if (e != hipSuccess || !ctx->timing) return e;
-    const hipError_t e1 = hipEventRecord(ctx->ev[1], ctx->stream);
-    if (e1 == hipSuccess) ctx->ev_valid[0] = true;
-    return e1;
-}
 
 // One batch: poses with off[0] = 0 ... off[K] = Q columns over the base matrices `base`, whose two columns are in m->gram_values_d
 // (base_g).  sums[2 k], sums[2 k + 1]: sum c and sum u of pose k over all pairs.

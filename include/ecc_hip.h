@@ -580,7 +580,8 @@ int ecc_metric_evaluate_view_hessian(ecc_metric* m, int n_channels, double* hess
  * Launches (csrc/ecc_weighted.hip, csrc/weighted_kernel.hip): the record kernel over all pairs, pairs_weighted_kernel -- one wave per
  * pair, the position arithmetic of a kappa step once, 8 gathers --, one launch for the two sums.
  * Index lists and pose deltas: ecc_metric_evaluate_weighted_pairs, ecc_metric_evaluate_weighted_pose_deltas below.
- * Out of scope: full-matrices pose batches, transform, range, group and RCCL forms; weights under use_corr; a
+ * The registration of two scans: ecc_metric_evaluate_weighted_transforms below.
+ * Out of scope: full-matrices pose batches, range, group and RCCL forms; weights under use_corr; a
  * 1 / (sigma0^2 + sigma1^2) variance form; a per-sample robust loss. */
 int ecc_metric_evaluate_weighted(ecc_metric* m, double* value, double* coverage, float* pair_terms);
 
@@ -616,7 +617,7 @@ int ecc_metric_evaluate_weighted(ecc_metric* m, double* value, double* coverage,
  * fewer than two views; n_dtrs != 2 * n_views; a bad list or tuple.  ECC_ERR_UNSUPPORTED under use_corr.  The calls change nothing a
  * later call can see: current matrices, kept records, the kept values of the pose-delta mode and of the pose batch.  (They rewrite
  * the pose batch's per-batch scratch and ecc_metric_evaluate_gram's scratch, as every call of those families does.)
- * Not built: base columns kept between calls; the full-matrices, strided, group and RCCL forms; the transform form; the
+ * Not built: base columns kept between calls; the full-matrices, strided, group and RCCL forms; the
  * incremental (ecc_metric_set_incremental) mode for the weighted value; a one-launch small path for weighted lists. */
 int ecc_metric_evaluate_weighted_pairs(ecc_metric* m, const int32_t* idx4, int n_pairs, double* value, double* coverage, float* pair_terms);
 int ecc_metric_evaluate_weighted_pose_deltas(ecc_metric* m, int n_poses, const int32_t* moved_offsets, const int32_t* moved_views,
@@ -657,6 +658,41 @@ int ecc_metric_last_batched_transforms(const ecc_metric* m, int64_t* transforms)
  * + P(r,3) T(3,c), every product and every sum rounded to binary64 on its own (no fused multiply-add) -- host, device and
  * tests agree on the bits.  out12 may be P12. */
 void ecc_host_compose_transform(const double* P12, const double* T16, double* out12);
+
+/* ecc_metric_evaluate_transforms for the metric with per-line weights (csrc/ecc_weighted_transforms.hip): the
+ * registration of two scans of which one is truncated or collimated, sees a table edge the other does not, or holds an instrument
+ * the other does not -- each breaks exactly the lines that cross it, in every cross pair of that view.  The metric is
+ * ecc_metric_evaluate_weighted's: n_dtrs == 2 * n_views (the data of every view, then its line weights), no use_corr.
+ *
+ * Views, transforms and the cross list are those of ecc_metric_evaluate_transforms: views [0, n_source) are the source scan, the
+ * rest the target scan; Ts + 16 k is a column-major 4x4 float64 transform; the source matrices become
+ * ecc_host_compose_transform(P_i, T_k); list entry q = j * n_source + i is the tuple (i, n_source + j, i, n_source + j);
+ * count = n_source * n_target.  The weights follow the DATA index (dtr n_views + D), never the extended matrix index.
+ *   values[k] (required): sum c / sum u over the list of transform k.
+ *   coverages[k] (nullable): sum u / count.  sum u == 0: value 0.0, coverage 0.0 and ECC_OK.
+ *   pair_terms (host, nullable): n_transforms x n_target x n_source x 2 float32, per transform its count rows {c, u} in list order.
+ * The contract (tests/test_gpu_weighted_transforms.py): all three have THE BITS of ecc_metric_set_projections(the composed
+ * matrices) + ecc_metric_evaluate_weighted_pairs(that list) on a metric with the same parameters.  So the sampling mode (and the
+ * reference arithmetic's wave split) resolves from a list of count tuples, under the automatic object radius every transform takes
+ * the radius of its composed view 0 (fix the radius for a sweep whose values are compared with each other), and each column's sum is
+ * added in the order of csrc/ecc_sum_order.h for count values, the slice sums -- the single one too -- added to 0.0 in slice order.
+ *
+ * Per batch: ecc_metric_evaluate_transforms' ONE launch that composes P_i T_k, does E1 of the n + K n_source extended matrices and
+ * writes the pair-major, transform-minor index grid, ONE record launch, ONE weighted pair launch over the grid and ONE segmented
+ * sum of both columns, which reads a transform's values K floats apart where the pair launch left them.  Calls of more than 2^20
+ * grid entries are cut into batches of whole transforms.  A transform whose list alone exceeds a batch, and every transform after
+ * ecc_metric_set_pose_batching(m, 0), is evaluated the sequential way inside the call (same bits, the base matrices set again);
+ * ecc_metric_last_batched_transforms counts what went through the batch.  The call leaves the metric as it found it: current
+ * matrices, kept records, the kept values of the pose-delta mode and of the pose batch.  (It rewrites the pose batch's per-batch
+ * scratch, and the sequential way ecc_metric_evaluate_gram's scratch.)
+ *
+ * Errors are returned before anything is launched or written, checked in this order: m == NULL; n_transforms < 0; null Ts or values
+ * with n_transforms > 0; no matrices set, fewer than two views, n_dtrs != 2 * n_views (ECC_ERR_INVALID_ARGUMENT) or use_corr
+ * (ECC_ERR_UNSUPPORTED); n_source outside [1, n_views).  After them n_transforms == 0 is ECC_OK with nothing written.
+ * Not built: the full-matrices and strided pose forms of the weighted metric; kept base columns; range, group and RCCL forms;
+ * weights under use_corr. */
+int ecc_metric_evaluate_weighted_transforms(ecc_metric* m, int n_source, int n_transforms, const double* Ts, double* values,
+                                            double* coverages, float* pair_terms);
 
 /* Multi-GPU building block: evaluate only pairs ij in [first, first+count) of the get_ij order
  * (ref: EpipolarConsistencyCommon.hxx:52-79); returns the partial sum (float64) -- the caller
