@@ -31,6 +31,11 @@ class PreprocessConfig(C.Structure):
                 ("n_blanks", C.c_int32), ("blanks", C.c_void_p)]
 
 
+class LineWeightsConfig(C.Structure):
+    """struct ecc_line_weights_config (include/ecc_hip.h)."""
+    _fields_ = [("dilate_px", C.c_int32), ("guard_bins", C.c_int32), ("zero_at_px", C.c_float)]
+
+
 _lib = None
 
 # name -> (restype, argtypes); every symbol declared in include/ecc_hip.h
@@ -58,6 +63,10 @@ SIGNATURES = {
     "ecc_dtr_slab_floats": (_i64, [_i, _i]),
     "ecc_dtr_wrap_device": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
     "ecc_dtr_destroy": (_i, [_vp]),
+    "ecc_line_weights_defaults": (None, [_vp]),
+    "ecc_radon_line_weights": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, C.POINTER(_vp)]),
+    "ecc_radon_line_weights_into": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "ecc_dtr_line_weights": (_i, [_vp, _vp, _vp, C.POINTER(_vp)]),
     "ecc_metric_create": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp)]),
     "ecc_metric_destroy": (_i, [_vp]),
     "ecc_metric_refresh_dtrs": (_i, [_vp, _i, _i]),

@@ -211,6 +211,18 @@ class RadonIntermediate:
         return cls(ctx, h)
 
     @classmethod
+    def line_weights_from(cls, lengths_dtr, zero_at_px=1.0, guard_bins=1, ctx=None):
+        """ecc_dtr_line_weights: the clip and the guard minimum of line_weights_device alone, on the device, for a FILTER_NONE
+        intermediate of lengths that exists already (e.g. loaded from a file); bit-identical to
+        from_host(line_weights_from_lengths(lengths_dtr.readback(), zero_at_px, guard_bins)).  ctx: a context on the same device
+        (default: the intermediate's own)."""
+        ctx = lengths_dtr.ctx if ctx is None else ctx
+        cfg = _line_weights_config(zero_at_px, guard_bins, 0)
+        h = C.c_void_p()
+        check(_lib.lib().ecc_dtr_line_weights(ctx._h, lengths_dtr._h, C.byref(cfg), C.byref(h)))
+        return cls(ctx, h)
+
+    @classmethod
     def load(cls, ctx, path):
         """ref: RadonIntermediate(const std::string path): a dtr NRRD written by the reference's tools
         (or by save()); returns (RadonIntermediate, info) where info carries the optional
@@ -1444,6 +1456,52 @@ def line_weights(ctx, flagged, size_alpha, size_t, zero_at_px=1.0, guard_bins=1)
         d.close()
         out.append(RadonIntermediate.from_host(ctx, w, n_u, n_v, FILTER_NONE))
     return out[0] if single else out
+
+
+def _line_weights_config(zero_at_px, guard_bins, dilate_px):
+    cfg = _lib.LineWeightsConfig()
+    _lib.lib().ecc_line_weights_defaults(C.byref(cfg))
+    cfg.zero_at_px, cfg.guard_bins, cfg.dilate_px = float(zero_at_px), int(guard_bins), int(dilate_px)
+    return cfg
+
+
+def line_weights_device(ctx, flagged, size_alpha, size_t, zero_at_px=1.0, guard_bins=1, dilate_px=0, out=None):
+    """line_weights without the host round trip (ecc_radon_line_weights / ecc_radon_line_weights_into): the flagged
+    image is dilated by dilate_px pixels (the maximum over the (2 dilate_px + 1)^2 square, edges clamped; 0: not at all), transformed
+    by the Radon kernel, clipped and put through the guard minimum on the device.  Bit-identical to line_weights on the dilated
+    image.  flagged: (n_v, n_u) or (n, n_v, n_u) float32, numpy on the host or torch on ctx's device, as compute_batch accepts; a 2-D
+    input returns one RadonIntermediate, a stack a list.  out: a torch (n, slab_floats(size_alpha, size_t)) float32 tensor on ctx's
+    device selects the asynchronous form for caller-owned slabs (flagged must be on the device too) and the returned handles alias
+    it, as compute_into's do -- a tracker whose mask moves follows it with metric.refreshRadonIntermediates(n_views + i, 1).
+    0 <= dilate_px <= 16, 0 <= guard_bins <= 8, zero_at_px finite and positive."""
+    cfg = _line_weights_config(zero_at_px, guard_bins, dilate_px)
+    if _is_torch(flagged):
+        import torch
+        assert flagged.dtype == torch.float32 and flagged.is_contiguous() and flagged.is_cuda
+        stack, on_dev = flagged, 1
+    else:
+        stack, on_dev = np.ascontiguousarray(flagged, np.float32), 0
+    if len(stack.shape) not in (2, 3):
+        raise ValueError("flagged must be (n_v, n_u) or (n, n_v, n_u)")
+    single = len(stack.shape) == 2
+    if single:
+        stack = stack[None]
+    n, n_v, n_u = (int(v) for v in stack.shape)
+    ptr = stack.data_ptr() if on_dev else stack.ctypes.data
+    if out is not None:
+        if not on_dev:
+            raise ValueError("out= needs flagged on the device")
+        assert out.is_contiguous() and out.is_cuda and tuple(out.shape) == (n, slab_floats(size_alpha, size_t))
+        check(_lib.lib().ecc_radon_line_weights_into(ctx._h, C.c_void_p(ptr), n, n_u, n_v, size_alpha, size_t, C.byref(cfg),
+                                                     C.c_void_p(out.data_ptr())))
+        made = [RadonIntermediate.wrap_device(ctx, out[k], size_alpha, size_t, n_u, n_v, FILTER_NONE) for k in range(n)]
+    else:
+        hs = (C.c_void_p * n)()
+        check(_lib.lib().ecc_radon_line_weights(ctx._h, C.c_void_p(ptr), on_dev, n, n_u, n_v, size_alpha, size_t, C.byref(cfg), hs))
+        if on_dev:
+            ctx.synchronize()  # the input tensor may be freed by the caller right after
+        made = [RadonIntermediate(ctx, C.c_void_p(h)) for h in hs]
+    return made[0] if single else made
 
 
 def view_hessian_value(H, a):

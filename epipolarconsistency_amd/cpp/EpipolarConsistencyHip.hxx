@@ -316,6 +316,31 @@ public:
     explicit RadonIntermediate(ecc_dtr* handle) : m_h(handle) {}
     ~RadonIntermediate() { ecc_dtr_destroy(m_h); }
 
+    /// The line weights of evaluateWeighted* for one view, made on the device (ecc_radon_line_weights): `flagged` holds n_u * n_v
+    /// floats on the host, 1 where a pixel must not be trusted and 0 elsewhere.  The image is dilated by dilate_px pixels, transformed
+    /// (Filter None), clipped to min(max(1 - L / zero_at_px, 0), 1) and put through the minimum over the (2 guard_bins + 1)^2 bin
+    /// neighbourhood.  The caller owns the result.
+    static RadonIntermediate* lineWeights(const float* flagged, int n_u, int n_v, int size_alpha, int size_t, float zero_at_px = 1.0f,
+                                          int guard_bins = 1, int dilate_px = 0, ecc_ctx* ctx = nullptr)
+    {
+        ecc_line_weights_config cfg;
+        ecc_line_weights_defaults(&cfg);
+        cfg.zero_at_px = zero_at_px;
+        cfg.guard_bins = guard_bins;
+        cfg.dilate_px = dilate_px;
+        ecc_dtr* h = nullptr;
+        detail::check(ecc_radon_line_weights(ctx ? ctx : detail::default_context(), flagged, 0, 1, n_u, n_v, size_alpha, size_t, &cfg, &h));
+        return new RadonIntermediate(h);
+    }
+#ifdef ECC_ADAPTER_HAVE_NRRD
+    static RadonIntermediate* lineWeights(const NRRD::ImageView<float>& flagged, int size_alpha, int size_t, float zero_at_px = 1.0f,
+                                          int guard_bins = 1, int dilate_px = 0, ecc_ctx* ctx = nullptr)
+    {
+        return lineWeights((const float*)flagged, flagged.size(0), flagged.size(1), size_alpha, size_t, zero_at_px, guard_bins, dilate_px,
+                           ctx);
+    }
+#endif
+
     Filter getFilter() const { return (Filter)info().filter; }
     bool isDerivative() const { return getFilter() == Derivative; }
     /// 0: angle bins, 1: distance bins (ref: RadonIntermediate.cpp:165-168)

@@ -248,6 +248,7 @@ ECC_EXPORT int ecc_ctx_destroy(ecc_ctx* ctx)
         if (b) (void)hipFree(b);
     if (ctx->radon_T_d) (void)hipFree(ctx->radon_T_d);
     if (ctx->linear_scratch_d) (void)hipFree(ctx->linear_scratch_d);
+    if (ctx->line_weights_scratch_d) (void)hipFree(ctx->line_weights_scratch_d);
     for (auto& e : ctx->ev)
         if (e) (void)hipEventDestroy(e);
     delete ctx;

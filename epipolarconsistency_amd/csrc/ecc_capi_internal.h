@@ -58,6 +58,10 @@ extern "C" hipError_t ecc_launch_sum_pairs_to_host(const float* vals, long long 
 extern "C" hipError_t ecc_launch_publish_scalar(const double* value_d, double* host_slot_dev, hipStream_t stream);
 extern "C" size_t ecc_sum_scratch_bytes();
 extern "C" hipError_t ecc_launch_pairs_weighted(const EccPairParams* p, const EccWeightedParams* g, hipStream_t stream);
+extern "C" hipError_t ecc_launch_dilate_max(const float* src, float* dst, int64_t stride, int n_img, int n_u, int n_v, int radius,
+                                            hipStream_t stream);
+extern "C" hipError_t ecc_launch_clip_min(const float* lengths, int64_t lengths_stride, float* dst, int64_t dst_stride, int n_img,
+                                          int n_alpha, int n_t, int pitch, int radius, float zero_at_px, hipStream_t stream);
 extern "C" hipError_t ecc_launch_e1(const double* Ps_d, int n, float* PinvTs_d, float* Cs_d, hipStream_t stream);
 
 #ifndef ECC_POSE_BATCH_MAX_ENTRIES
@@ -129,6 +133,9 @@ struct ecc_ctx {
     // one slab of scratch for ecc_radon_compute_linear
     float* linear_scratch_d = nullptr;
     size_t linear_scratch_cap = 0;  // floats
+    // scratch of ecc_radon_line_weights*: the lengths of one sub-batch (at most 64 slabs), then its dilated images (dilate_px > 0)
+    float* line_weights_scratch_d = nullptr;
+    size_t line_weights_scratch_cap = 0;  // floats
 };
 
 struct ecc_dtr {
@@ -419,6 +426,11 @@ inline void ecc_stamp(ecc_metric* m, int k)
 
 namespace ecc_internal {
 
+// ecc_radon_api.hip, for ecc_line_weights.hip: the range checks of the Radon calls; the Radon launches of a stack on the context's stream
+int radon_check_args(ecc_ctx* ctx, const float* image, int n, int n_u, int n_v, int n_alpha, int n_t, int filter, int post,
+                     ecc_dtr** out);
+int radon_launch_stack(ecc_ctx* ctx, const float* images_d, int n, int n_u, int n_v, int n_alpha, int n_t, int filter, int post,
+                       float* slabs, int64_t slab_stride);
 void arm_result(ecc_metric* m);
 hipError_t wait_result(ecc_metric* m, hipStream_t stream, double* value);
 int set_device(const ecc_ctx* ctx);

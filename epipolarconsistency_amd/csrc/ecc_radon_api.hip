@@ -165,6 +165,20 @@ int check_radon_args(ecc_ctx* ctx, const float* image, int n, int n_u, int n_v, 
 
 }  // namespace
 
+// The two above for ecc_line_weights.hip, whose lengths come from this file's launches unchanged.
+namespace ecc_internal {
+int radon_check_args(ecc_ctx* ctx, const float* image, int n, int n_u, int n_v, int n_alpha, int n_t, int filter, int post,
+                     ecc_dtr** out)
+{
+    return check_radon_args(ctx, image, n, n_u, n_v, n_alpha, n_t, filter, post, out);
+}
+int radon_launch_stack(ecc_ctx* ctx, const float* images_d, int n, int n_u, int n_v, int n_alpha, int n_t, int filter, int post,
+                       float* slabs, int64_t slab_stride)
+{
+    return radon_launch(ctx, images_d, n, n_u, n_v, n_alpha, n_t, filter, post, slabs, slab_stride);
+}
+}  // namespace ecc_internal
+
 // ---- Radon intermediate ------------------------------------------------------------------------
 ECC_EXPORT int64_t ecc_dtr_slab_floats(int n_alpha, int n_t) { return ecc_layout_floats(n_alpha, n_t); }
 

@@ -150,6 +150,40 @@ int ecc_dtr_wrap_device(ecc_ctx* ctx, float* base, int n_alpha, int n_t, int n_u
                         ecc_dtr** out);
 int ecc_dtr_destroy(ecc_dtr* dtr);
 
+/* ---- line weights from a flagged-pixel image, made on the device ----------------------------- */
+/* The weight intermediates of ecc_metric_evaluate_weighted (below) from images that are 1 where a pixel must not be trusted and 0
+ * elsewhere, without a host round trip (csrc/ecc_line_weights.hip, csrc/line_weights_kernel.hip).  For one flagged
+ * image F of n_v x n_u:
+ *   1. D = F if dilate_px = 0, else D(y, x) = the maximum of F over the (2 dilate_px + 1)^2 square around (y, x), indices clamped
+ *      to the image;
+ *   2. L = the ECC_FILTER_NONE / ECC_POST_IDENTITY Radon intermediate of D on n_alpha x n_t bins -- the launches of
+ *      ecc_radon_compute_batch in the context's arithmetic mode: the length in pixels of every bin's line inside flagged pixels;
+ *   3. w = min(max(1.0f - L / zero_at_px, 0.0f), 1.0f): one binary32 division, one subtraction, no reciprocal, no contraction;
+ *   4. W(ix, iy) = the minimum of w over the (2 guard_bins + 1)^2 bins around (ix, iy), indices clamped to the grid: with
+ *      guard_bins >= 1 a bilinear sample with a weight above 0 touches no bin with L >= zero_at_px;
+ *   5. W is written as a complete slab of the private layout: elements, replicated border, zeros in the pitch padding.
+ * Caps: 0 <= dilate_px <= 16, 0 <= guard_bins <= 8, zero_at_px finite and positive.  Inputs are finite; NaNs are unspecified.
+ * The results have the bits of the Python layer's line_weights (readback, numpy, ecc_dtr_from_host) on the dilated image. */
+typedef struct ecc_line_weights_config { int32_t dilate_px; int32_t guard_bins; float zero_at_px; } ecc_line_weights_config;
+void ecc_line_weights_defaults(ecc_line_weights_config* cfg);          /* 0, 1, 1.0f: line_weights' defaults */
+/* cfg == NULL means the defaults.
+ * ecc_radon_line_weights: n flagged images on the host (on_device = 0) or on ctx's device (= 1) -> n handles in out[0..n) that share
+ *   one slab stack, as ecc_radon_compute_batch's do; they report ECC_FILTER_NONE.
+ * ecc_radon_line_weights_into: the asynchronous device-to-device form for caller-owned slabs, with the argument shape and semantics
+ *   of ecc_radon_compute_into -- the per-frame path of a tracker whose mask moves: follow it with
+ *   ecc_metric_refresh_dtrs(m, n_views + i, 1).  Every float of the n slabs is written.
+ * ecc_dtr_line_weights: steps 3 to 5 alone, for a caller who already holds a length intermediate (e.g. from a file); dilate_px is
+ *   not applied (the caps of the whole config are still checked).  `lengths` must have ECC_FILTER_NONE and live on ctx's device.
+ * Errors, before any launch, allocation or write, ECC_ERR_INVALID_ARGUMENT: ctx == NULL (checked first); null images, output or
+ * slabs; the range checks of ecc_radon_compute_batch; a config outside the caps (a NaN or non-positive zero_at_px included).
+ * Scratch (kept in the context): the lengths, and with dilate_px > 0 the dilated images, of at most 64 views; larger stacks go
+ * through it 64 views at a time on the context's stream. */
+int ecc_radon_line_weights(ecc_ctx* ctx, const float* flagged, int on_device, int n, int n_u, int n_v,
+                           int n_alpha, int n_t, const ecc_line_weights_config* cfg, ecc_dtr** out);
+int ecc_radon_line_weights_into(ecc_ctx* ctx, const float* flagged_d, int n, int n_u, int n_v,
+                                int n_alpha, int n_t, const ecc_line_weights_config* cfg, float* slabs_d);
+int ecc_dtr_line_weights(ecc_ctx* ctx, const ecc_dtr* lengths, const ecc_line_weights_config* cfg, ecc_dtr** out);
+
 /* ---- projection pre-processing (the step in front of R1) ------------------------------------- */
 /* ref: struct EpipolarConsistency::PreProccess (Gui/PreProccess.h:14-50), same fields and defaults
  * (ecc_preprocess_defaults).  Offsets in zero/feather are left, right, bottom, top; blanks are
