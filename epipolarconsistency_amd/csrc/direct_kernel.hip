@@ -76,8 +76,13 @@ __global__ __launch_bounds__(256) void direct_pair_kernel(EccDirectParams p)
     const double mom = sqrt(B[3] * B[3] + B[1] * B[1] + B[0] * B[0]);
     const double dir = sqrt(B[2] * B[2] + B[4] * B[4] + B[5] * B[5]);
     const double baseline_dist = mom / dir;
+    // The range comes from the host where it is given: the device's asin may differ from the host's in the last bit, which
+    // moves the grid's middle angle between 0 and 1e-16 and, for a detector with an integer diagonal, the line count by one.
     double k_first, k_second;
-    if (baseline_dist <= radius) {
+    if (p.k_second) {
+        k_second = p.k_second[local];
+        k_first = -k_second;
+    } else if (baseline_dist <= radius) {
         k_first = -0.5 * Pi;
         k_second = 0.5 * Pi;
     } else {

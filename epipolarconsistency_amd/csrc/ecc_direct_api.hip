@@ -28,6 +28,10 @@ struct ecc_direct {
     double* total_d = nullptr;
     float* cost_d = nullptr;
     int cost_capacity = 0;
+    // per view: source position (4) and object radius, on the host; per pair: the plane-angle range (see direct_ranges)
+    std::vector<double> centers, radii, ranges;
+    double* ranges_d = nullptr;
+    int64_t ranges_capacity = 0;
 };
 
 namespace {
@@ -65,6 +69,48 @@ int direct_scratch(ecc_direct* d, int64_t batch, int n_max)
     HIP_TRY(hipMalloc((void**)&d->pair_metric_d, sizeof(double) * (size_t)batch));
     d->batch_capacity = batch;
     d->n_max_capacity = n_max;
+    return ECC_OK;
+}
+
+// ref: estimateAngularRange (EpipolarConsistency.cpp:49-59) as computeForImagePair calls it (...Direct.cpp:84-96): the
+// upper end of the plane-angle range of `count` pairs (idx2, or get_ij order from `first`), in the arithmetic of
+// direct_pair_kernel but with the host's asin -- the library the reference and the oracle compute it with.  Left on
+// the device in d->ranges_d (stream-ordered; d->ranges is the staging copy and lives as long as d).
+int direct_ranges(ecc_direct* d, int64_t first, int64_t count, const int* idx2)
+{
+    if (count > d->ranges_capacity) {
+        HIP_TRY(hipStreamSynchronize(d->ctx->stream));
+        if (d->ranges_d) HIP_TRY(hipFree(d->ranges_d));
+        d->ranges_d = nullptr;
+        d->ranges_capacity = 0;
+        HIP_TRY(hipMalloc((void**)&d->ranges_d, sizeof(double) * (size_t)count));
+        d->ranges_capacity = count;
+    }
+    d->ranges.resize((size_t)count);
+    const int n = d->n_images;
+    const double user_radius = direct_radius(d);
+    const double Pi = 3.14159265358979323846264338327950288419716939937510582;
+    int i = 0, j = 1;
+    if (!idx2) ecc_get_ij(first, n, &i, &j);
+    for (int64_t q = 0; q < count; ++q) {
+        if (idx2) {
+            i = idx2[2 * q];
+            j = idx2[2 * q + 1];
+        }
+        double B[6];
+        ecc_host::join_points(&d->centers[4 * (size_t)i], &d->centers[4 * (size_t)j], B);
+        double radius = user_radius;
+        if (radius <= 0) radius = d->radii[i] > d->radii[j] ? d->radii[i] : d->radii[j];
+        const double mom = std::sqrt(B[3] * B[3] + B[1] * B[1] + B[0] * B[0]);
+        const double dir = std::sqrt(B[2] * B[2] + B[4] * B[4] + B[5] * B[5]);
+        const double baseline_dist = mom / dir;
+        d->ranges[(size_t)q] = baseline_dist <= radius ? 0.5 * Pi : std::fabs(std::asin(radius / baseline_dist));
+        if (!idx2 && ++j >= n) {
+            ++i;
+            j = i + 1;
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(d->ranges_d, d->ranges.data(), sizeof(double) * (size_t)count, hipMemcpyHostToDevice, d->ctx->stream));
     return ECC_OK;
 }
 
@@ -127,6 +173,7 @@ ECC_EXPORT int ecc_direct_destroy(ecc_direct* d)
     if (d->pair_metric_d) (void)hipFree(d->pair_metric_d);
     if (d->total_d) (void)hipFree(d->total_d);
     if (d->cost_d) (void)hipFree(d->cost_d);
+    if (d->ranges_d) (void)hipFree(d->ranges_d);
     delete d;
     return ECC_OK;
 }
@@ -152,6 +199,12 @@ ECC_EXPORT int ecc_direct_set_projections(ecc_direct* d, const double* Ps, int n
     HIP_TRY(hipStreamSynchronize(ctx->stream));  // Ps is the caller's pageable memory
     d->n_views = n_views;
     d->P_first.assign(Ps, Ps + 12);
+    d->centers.resize(4 * (size_t)n_views);
+    d->radii.resize((size_t)n_views);
+    for (int v = 0; v < n_views; ++v) {
+        ecc_host::camera_center(Ps + 12 * (size_t)v, &d->centers[4 * (size_t)v]);
+        d->radii[(size_t)v] = ecc_host::object_radius(Ps + 12 * (size_t)v, d->n_u, d->n_v);
+    }
     return ECC_OK;
 }
 
@@ -213,6 +266,8 @@ ECC_EXPORT int ecc_direct_evaluate(ecc_direct* d, float* cost_nxn, double* cost_
         if (batch > n_pairs) batch = n_pairs;
         rc = direct_scratch(d, batch, n_max);
         if (rc) return rc;
+        rc = direct_ranges(d, 0, n_pairs, nullptr);
+        if (rc) return rc;
         for (int64_t first = 0; first < n_pairs; first += batch) {
             EccDirectParams p;
             std::memset(&p, 0, sizeof(p));
@@ -233,6 +288,7 @@ ECC_EXPORT int ecc_direct_evaluate(ecc_direct* d, float* cost_nxn, double* cost_
             p.object_radius_mm = direct_radius(d);
             p.dkappa = d->dkappa;
             p.use_fbcc = d->use_fbcc ? 1 : 0;
+            p.k_second = d->ranges_d + first;
             HIP_TRY(ecc_launch_direct_batch(&p, d->total_d, ctx->stream));
         }
     }
@@ -281,6 +337,9 @@ int direct_pair_impl(ecc_direct* d, int i, int j, int capacity, int* n_lines, fl
     rc = direct_scratch(d, 1, std::max(n_max, n_kappas_in));
     if (rc) return rc;
     n_max = d->n_max_capacity;
+    const int idx[2] = {i, j};
+    rc = direct_ranges(d, 0, 1, idx);
+    if (rc) return rc;
     // debug outputs of pair 0: 6 floats per kappa (lines) + kappa grid + line count + the (i, j) tuple; the grid
     // buffer doubles as the input of a caller-provided grid
     char* dbg = nullptr;
@@ -291,7 +350,6 @@ int direct_pair_impl(ecc_direct* d, int i, int j, int capacity, int* n_lines, fl
     float* kap_in_d = reinterpret_cast<float*>(dbg + lines_b + kap_b);
     int* count_d = reinterpret_cast<int*>(dbg + lines_b + 2 * kap_b);
     int* idx_d = count_d + 1;
-    const int idx[2] = {i, j};
     EccDirectParams p;
     std::memset(&p, 0, sizeof(p));
     p.images = d->images_d;
@@ -316,6 +374,7 @@ int direct_pair_impl(ecc_direct* d, int i, int j, int capacity, int* n_lines, fl
     p.use_fbcc = d->use_fbcc ? 1 : 0;
     p.user_kappas = kappas_in ? kap_in_d : nullptr;
     p.n_user_kappas = n_kappas_in;
+    p.k_second = d->ranges_d;
     std::vector<float> v((size_t)n_max * 2), L((size_t)n_max * 6), K((size_t)n_max);
     int n = 0;
     double m = 0;

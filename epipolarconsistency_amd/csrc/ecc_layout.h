@@ -334,6 +334,8 @@ struct EccDirectParams {
     int use_fbcc;               // MetricDirect::setFanBeamConsistency
     const float* user_kappas;   // optional caller-provided kappa grid (ref: EpipolarConsistencyDirect.cpp:105-117), device
     int n_user_kappas;
+    const double* k_second;     // optional, per pair of the batch: the upper end of the plane-angle range from the HOST's
+                                // libm (ecc_direct_api.hip, direct_ranges), so that the grid is the reference's bit for bit
 };
 
 // ---- evaluateForImagePair (E7, visualisation) -------------------------------------------------

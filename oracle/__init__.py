@@ -22,11 +22,27 @@ def build(native=False):
     subprocess.run(["make", "-s", "-C", _HERE] + target, check=True)
 
 
+# the entry point added last to ecc_oracle.c: a library without it was built from an older source
+_NEWEST_SYMBOL = "eccor_direct_pair_with"
+
+
 def _load(name, native=False):
     path = os.environ.get("ECC_ORACLE_LIB") or os.path.join(_HERE, name)  # override: the sanitizer build (scripts/sanitize.sh)
     if not os.path.exists(path):
         build(native=native)
-    return C.CDLL(path)
+    L = C.CDLL(path)
+    if not hasattr(L, _NEWEST_SYMBOL):
+        # a library from before the current ecc_oracle.c: never let it answer for the current one
+        if os.environ.get("ECC_ORACLE_LIB"):
+            raise RuntimeError("%s is stale: it lacks %s; rebuild it from oracle/ecc_oracle.c" % (path, _NEWEST_SYMBOL))
+        import _ctypes
+        _ctypes.dlclose(L._handle)  # or the loader hands the stale image back under the same name
+        del L
+        subprocess.run(["make", "-s", "-C", _HERE, "-W", os.path.join(_HERE, "ecc_oracle.c"), path], check=True)
+        L = C.CDLL(path)
+        if not hasattr(L, _NEWEST_SYMBOL):
+            raise RuntimeError("%s still lacks %s after a rebuild from oracle/ecc_oracle.c" % (path, _NEWEST_SYMBOL))
+    return L
 
 
 _lib = None
@@ -345,26 +361,50 @@ def intrinsics(P):
     return a.value, b.value, c.value
 
 
-def direct_pair(P0, P1, img0, img1, dkappa=0.0, object_radius_mm=0.0, fbcc=False):
+def direct_pair(P0, P1, img0, img1, dkappa=0.0, object_radius_mm=0.0, fbcc=False, kappas=None, lines=None):
     """MetricDirect for one pair (ref: EpipolarConsistencyDirect.cpp:67-219; fbcc: the rectified fan-beam
-    weighting of :133-196 instead of the derivative).  Returns dict(metric, samples0, samples1, kappas, lines (n,6))."""
+    weighting of :133-196 instead of the derivative).  Returns dict(metric, samples0, samples1, kappas, lines (n,6)).
+    kappas: a float32 grid taken as the plane angles (ref: :105-117; dkappa of the metric is unchanged).  lines: (n, 6)
+    float32 used INSTEAD of the lines of the plane angles (clipping, the 0.4-px loop and the line-level fan-beam part run
+    on them); with both, the angles are only reported back."""
     L = lib()
     L.eccor_set_direct_fbcc.argtypes = [C.c_int]
     L.eccor_set_direct_fbcc(1 if fbcc else 0)
-    L.eccor_direct_pair.argtypes = [_f64p, _f64p, _f32p, _f32p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
-                                    _f32p, _f32p, _f32p, _f32p, C.POINTER(C.c_double)]
-    L.eccor_direct_pair.restype = C.c_int
     a = np.ascontiguousarray(img0, np.float32)
     b = np.ascontiguousarray(img1, np.float32)
     n_v, n_u = a.shape
     cap = (int(2 * np.sqrt(float(n_u * n_u + n_v * n_v))) if dkappa <= 0 else int(np.pi / dkappa)) + 16
+    uk = ul = None
+    if kappas is not None:
+        uk = np.ascontiguousarray(kappas, np.float32).reshape(-1)
+        if len(uk) == 0:
+            raise ValueError("empty kappa grid")
+        cap = max(cap, len(uk))
+    if lines is not None:
+        ul = np.ascontiguousarray(lines, np.float32).reshape(-1, 6)
+        cap = max(cap, len(ul))
     v0, v1, kap = (np.zeros(cap, np.float32) for _ in range(3))
-    lines = np.zeros(6 * cap, np.float32)
+    out_lines = np.zeros(6 * cap, np.float32)
     m = C.c_double()
-    n = L.eccor_direct_pair(_P(P0), _P(P1), a, b, n_u, n_v, float(dkappa), float(object_radius_mm), cap, v0, v1, kap,
-                            lines, C.byref(m))
+    if uk is None and ul is None:
+        L.eccor_direct_pair.argtypes = [_f64p, _f64p, _f32p, _f32p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
+                                        _f32p, _f32p, _f32p, _f32p, C.POINTER(C.c_double)]
+        L.eccor_direct_pair.restype = C.c_int
+        n = L.eccor_direct_pair(_P(P0), _P(P1), a, b, n_u, n_v, float(dkappa), float(object_radius_mm), cap, v0, v1, kap,
+                                out_lines, C.byref(m))
+    else:
+        L.eccor_direct_pair_with.argtypes = [_f64p, _f64p, _f32p, _f32p, C.c_int, C.c_int, C.c_double, C.c_double,
+                                             C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                             _f32p, _f32p, _f32p, _f32p, C.POINTER(C.c_double)]
+        L.eccor_direct_pair_with.restype = C.c_int
+        n = L.eccor_direct_pair_with(_P(P0), _P(P1), a, b, n_u, n_v, float(dkappa), float(object_radius_mm),
+                                     0 if uk is None else len(uk), None if uk is None else uk.ctypes.data,
+                                     0 if ul is None else len(ul), None if ul is None else ul.ctypes.data,
+                                     cap, v0, v1, kap, out_lines, C.byref(m))
+        if n < 0:
+            raise ValueError("kappas and lines must have the same length")
     assert n <= cap
-    return dict(metric=m.value, samples0=v0[:n], samples1=v1[:n], kappas=kap[:n], lines=lines[:6 * n].reshape(n, 6))
+    return dict(metric=m.value, samples0=v0[:n], samples1=v1[:n], kappas=kap[:n], lines=out_lines[:6 * n].reshape(n, 6))
 
 
 def direct_evaluate(Ps, imgs, dkappa=0.0, object_radius_mm=0.0, fbcc=False):

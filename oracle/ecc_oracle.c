@@ -1301,9 +1301,10 @@ ECCOR_API void eccor_set_direct_fbcc(int v) { g_direct_fbcc = v; }
  * (:23-65) and estimateAngularRange (EpipolarConsistency.cpp:49-59).  object_radius_mm <= 0: the larger of the
  * two views' estimates (:88-90).  Output arrays hold `capacity` entries (nullable); lines01: 6 floats per kappa.
  * Returns n_lines; *metric = sum (v0-v1)^2 dkappa (float difference and square, double sum, :206-208). */
-ECCOR_API int eccor_direct_pair(const double *P0, const double *P1, const float *img0, const float *img1,
-                                int n_u, int n_v, double dkappa, double object_radius_mm, int capacity,
-                                float *v0s, float *v1s, float *kappas, float *lines01, double *metric)
+static int or_direct_pair_body(const double *P0, const double *P1, const float *img0, const float *img1,
+                               int n_u, int n_v, double dkappa, double object_radius_mm, int n_user_kappas,
+                               const float *user_kappas, int n_user_lines, const float *user_lines, int capacity,
+                               float *v0s, float *v1s, float *kappas, float *lines01, double *metric)
 {
     const double Pi = 3.14159265358979323846264338327950288419716939937510582;
     double C0[4], C1[4], B[6], E0[4], E90[4], origin3[4] = {0, 0, 0, 1};
@@ -1327,7 +1328,12 @@ ECCOR_API int eccor_direct_pair(const double *P0, const double *P1, const float 
         double diag = sqrt((double)(n_u * n_u + n_v * n_v));
         dkappa = 0.5 * (k_second - k_first) / diag;
     }
-    n_lines = (int)((k_second - k_first) / dkappa);
+    {
+        double nl = (k_second - k_first) / dkappa;
+        n_lines = nl >= 0 ? (nl < 2147483000.0 ? (int)nl : 2147483000) : 0; /* NaN (coincident source positions): no lines */
+    }
+    if (user_kappas) n_lines = n_user_kappas; /* ref: :105-106, a non-empty `kappas` is taken as the grid */
+    if (user_lines) n_lines = n_user_lines;
     or_join_line_point(B, origin3, E0);
     or_join_line_point(B, E0, E90);
     n0 = sqrt(E0[0] * E0[0] + E0[1] * E0[1] + E0[2] * E0[2]);
@@ -1347,17 +1353,21 @@ ECCOR_API int eccor_direct_pair(const double *P0, const double *P1, const float 
     float *dv = (float *)malloc(sizeof(float) * 2 * (size_t)(n_lines > 0 ? n_lines : 1));
 #pragma omp parallel for schedule(dynamic, 16)
     for (i = 0; i < n_lines; i++) {
-        float kf = (float)(k_first + dkappa * i);
+        float kf = user_kappas && i < n_user_kappas ? user_kappas[i] : (float)(k_first + dkappa * i);
         double kappa = kf, c = cos(kappa), s = sin(kappa), E[4], l0[3], l1[3], nn;
         float lf[6], v0, v1;
         int k;
-        for (k = 0; k < 4; k++) E[k] = c * E0[k] + s * E90[k];
-        or_plane_to_line(&f0, E, l0);
-        or_plane_to_line(&f1, E, l1);
-        nn = sqrt(l0[0] * l0[0] + l0[1] * l0[1]);
-        for (k = 0; k < 3; k++) lf[k] = (float)(l0[k] / nn);
-        nn = sqrt(l1[0] * l1[0] + l1[1] * l1[1]);
-        for (k = 0; k < 3; k++) lf[3 + k] = (float)(l1[k] / nn);
+        if (user_lines) {
+            memcpy(lf, user_lines + 6 * (size_t)i, sizeof(lf));
+        } else {
+            for (k = 0; k < 4; k++) E[k] = c * E0[k] + s * E90[k];
+            or_plane_to_line(&f0, E, l0);
+            or_plane_to_line(&f1, E, l1);
+            nn = sqrt(l0[0] * l0[0] + l0[1] * l0[1]);
+            for (k = 0; k < 3; k++) lf[k] = (float)(l0[k] / nn);
+            nn = sqrt(l1[0] * l1[0] + l1[1] * l1[1]);
+            for (k = 0; k < 3; k++) lf[3 + k] = (float)(l1[k] / nn);
+        }
         if (g_direct_fbcc) {
             or_fbcc_info i0, i1;
             or_fbcc_line_info(P0, C0, H0, dvec, Eplane, lf, &i0);
@@ -1382,6 +1392,33 @@ ECCOR_API int eccor_direct_pair(const double *P0, const double *P1, const float 
     free(dv);
     if (metric) *metric = acc;
     return n_lines;
+}
+
+ECCOR_API int eccor_direct_pair(const double *P0, const double *P1, const float *img0, const float *img1,
+                                int n_u, int n_v, double dkappa, double object_radius_mm, int capacity,
+                                float *v0s, float *v1s, float *kappas, float *lines01, double *metric)
+{
+    return or_direct_pair_body(P0, P1, img0, img1, n_u, n_v, dkappa, object_radius_mm, 0, NULL, 0, NULL, capacity, v0s, v1s,
+                               kappas, lines01, metric);
+}
+
+/* The same with a caller's grid and / or a caller's lines.  user_kappas (n_user_kappas floats, or NULL): taken as the plane
+ * angles (ref: EpipolarConsistencyDirect.cpp:105-117); dkappa of the metric is unchanged.  user_lines (6 floats per line:
+ * image 0's line, image 1's; or NULL): used INSTEAD of the lines of the plane angles -- clipping, the 0.4-px loop and the
+ * line-level fan-beam weighting run on them as on lines computed here.  With both, the counts must agree and the angles are
+ * only reported.  With lines alone the reported angles are the automatic grid's.  Returns n_lines, or -1 for such a
+ * mismatch or a negative count. */
+ECCOR_API int eccor_direct_pair_with(const double *P0, const double *P1, const float *img0, const float *img1,
+                                     int n_u, int n_v, double dkappa, double object_radius_mm, int n_user_kappas,
+                                     const float *user_kappas, int n_user_lines, const float *user_lines, int capacity,
+                                     float *v0s, float *v1s, float *kappas, float *lines01, double *metric)
+{
+    if (!user_kappas) n_user_kappas = 0;
+    if (!user_lines) n_user_lines = 0;
+    if (n_user_kappas < 0 || n_user_lines < 0) return -1;
+    if (user_kappas && user_lines && n_user_kappas != n_user_lines) return -1;
+    return or_direct_pair_body(P0, P1, img0, img1, n_u, n_v, dkappa, object_radius_mm, n_user_kappas, user_kappas,
+                               n_user_lines, user_lines, capacity, v0s, v1s, kappas, lines01, metric);
 }
 
 ECCOR_API void eccor_set_num_threads(int n)

@@ -3,6 +3,8 @@
 import numpy as np
 import pytest
 
+import direct_terms
+
 pytestmark = pytest.mark.gpu
 
 
@@ -26,6 +28,10 @@ def test_pair_signals_and_metric(gpu_ctx, oracle_mod, small_scan, dkappa):
         assert np.array_equal(got["kappas"], want["kappas"])
         # lines: float64 geometry rounded to float on both sides (sin/cos of two libms)
         assert np.abs(got["lines"] - want["lines"]).max() <= 2e-6 * np.abs(want["lines"]).max()
+        # ... so a component moves to the neighbouring float32 at most (tests/direct_terms.py)
+        bars = direct_terms.line_difference_in_bars(got["lines"], want["lines"])
+        print("pair (%d, %d): worst line difference %.3f bars" % (i, j, bars.max()))
+        assert bars.max() <= 1.0
         scale = max(np.abs(want["samples0"]).max(), np.abs(want["samples1"]).max())
         same = np.all(got["lines"] == want["lines"], axis=1)
         assert same.mean() > 0.9
