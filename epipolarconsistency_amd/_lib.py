@@ -15,6 +15,7 @@ FILTER_DERIVATIVE, FILTER_RAMP, FILTER_NONE = 0, 1, 2
 POST_IDENTITY, POST_SQUARE_ROOT, POST_LOGARITHM = 0, 1, 2
 RADON_EXACT, RADON_FMA = 0, 1
 SAMPLING_AUTO, SAMPLING_POLYNOMIAL, SAMPLING_PER_SAMPLE, SAMPLING_REFERENCE = 0, 1, 2, 3
+LOSS_HUBER, LOSS_TRUNCATED, LOSS_GEMAN_MCCLURE = 0, 1, 2
 
 
 class EccError(RuntimeError):
@@ -98,6 +99,9 @@ SIGNATURES = {
     "ecc_metric_evaluate_weighted_pose_deltas": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "ecc_metric_evaluate_transforms": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "ecc_metric_evaluate_weighted_transforms": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "ecc_metric_evaluate_robust": (_i, [_vp, _i, C.c_float, _pd, _pd, _vp]),
+    "ecc_metric_evaluate_robust_pairs": (_i, [_vp, _vp, _i, _i, C.c_float, _pd, _pd, _vp]),
+    "ecc_host_robust_scale": (_d, [_vp, _i64, _d]),
     "ecc_metric_last_batched_transforms": (_i, [_vp, C.POINTER(_i64)]),
     "ecc_host_compose_transform": (None, [_vp, _vp, _vp]),
     "ecc_metric_evaluate_range": (_i, [_vp, _i64, _i64, _vp, _pd]),

@@ -825,6 +825,36 @@ class MetricRadonIntermediate:
                                                       C.c_void_p(pairs.ctypes.data) if (want_pairs and pairs.size) else None))
         return (value.value, coverage.value, pairs) if want_pairs else (value.value, coverage.value)
 
+    def evaluate_robust(self, loss, delta, want_pairs=False):
+        """ecc_metric_evaluate_robust: the metric under a per-sample robust loss rho(d) = w(d) d^2 -- loss one of LOSS_HUBER,
+        LOSS_TRUNCATED, LOSS_GEMAN_MCCLURE, delta > 0 its scale in the units of the data (float32; inf down-weights nothing and
+        gives the bits of evaluate()).  For data in which nobody has said which lines are bad.  Returns (value, inlier_mass): value =
+        sum c / n_pairs, inlier_mass = sum u / n_pairs -- with want_pairs (value, inlier_mass, pairs), pairs (n_pairs, 3) float32 in
+        the pair order of evaluate(cost): per pair c, its value, u, the mean IRLS weight of its samples in (0, 1], and r, their mean
+        squared raw residual (robust_scale takes delta from it).  The current matrices and everything the metric keeps stay."""
+        n = 0 if self._Ps is None else len(self._Ps)  # (no matrices: the library reports it)
+        value, mass = C.c_double(0.0), C.c_double(0.0)
+        pairs = np.zeros((n * (n - 1) // 2, 3), np.float32) if want_pairs else None
+        check(_lib.lib().ecc_metric_evaluate_robust(self._h, int(loss), float(delta), C.byref(value), C.byref(mass),
+                                                    C.c_void_p(pairs.ctypes.data) if (want_pairs and pairs.size) else None))
+        return (value.value, mass.value, pairs) if want_pairs else (value.value, mass.value)
+
+    def evaluate_robust_pairs(self, idx4, loss, delta, want_pairs=False):
+        """ecc_metric_evaluate_robust_pairs: evaluate_robust over an index list of (P0, P1, D0, D1) tuples, as evaluate(indices)
+        takes them.  Returns (value, inlier_mass) over the list -- with want_pairs (value, inlier_mass, pairs), pairs (n_pairs, 3)
+        float32 rows {c, u, r} in list order.  The sampling mode resolves from the list's length; an empty list writes nothing
+        (0.0, 0.0)."""
+        idx = np.ascontiguousarray(idx4, np.int32)
+        if idx.size % 4 or (idx.ndim == 2 and idx.shape[1] != 4) or idx.ndim > 2:
+            raise ValueError("idx4 must hold (P0, P1, D0, D1) tuples")
+        idx = idx.reshape(-1, 4)
+        value, mass = C.c_double(0.0), C.c_double(0.0)
+        pairs = np.zeros((len(idx), 3), np.float32) if want_pairs else None
+        check(_lib.lib().ecc_metric_evaluate_robust_pairs(self._h, C.c_void_p(idx.ctypes.data) if len(idx) else None, len(idx),
+                                                          int(loss), float(delta), C.byref(value), C.byref(mass),
+                                                          C.c_void_p(pairs.ctypes.data) if (want_pairs and pairs.size) else None))
+        return (value.value, mass.value, pairs) if want_pairs else (value.value, mass.value)
+
     def evaluate_transforms(self, n_source, Ts, want_pairs=False):
         """ecc_metric_evaluate_transforms: the registration of two scans (ref: tools/Registration/Registration3D3D.hxx).  The
         current matrices are the base, views [0, n_source) the source scan, the rest the target scan; Ts: anything np.asarray
@@ -1456,6 +1486,16 @@ def line_weights(ctx, flagged, size_alpha, size_t, zero_at_px=1.0, guard_bins=1)
         d.close()
         out.append(RadonIntermediate.from_host(ctx, w, n_u, n_v, FILTER_NONE))
     return out[0] if single else out
+
+
+def robust_scale(pair_terms, k=1.0):
+    """ecc_host_robust_scale: a scale delta for evaluate_robust from the pair rows {c, u, r} of an earlier call (normally the one
+    with delta = inf) -- k x the median over the pairs with r > 0 of sqrt(r), the pair's rms residual; 0.0 without such a pair.  A
+    minority of corrupted views reaches a minority of the pairs, so the median stays put where the pooled rms does not."""
+    rows = np.ascontiguousarray(pair_terms, np.float32)
+    if rows.ndim != 2 or rows.shape[1] != 3:
+        raise ValueError("pair_terms must be (n_pairs, 3) rows {c, u, r}")
+    return float(_lib.lib().ecc_host_robust_scale(C.c_void_p(rows.ctypes.data) if len(rows) else None, len(rows), float(k)))
 
 
 def _line_weights_config(zero_at_px, guard_bins, dilate_px):

@@ -894,6 +894,59 @@ public:
         return value;
     }
 
+    /// Not in the reference: ecc_metric_evaluate_robust -- the metric under a per-sample robust loss rho(d) = w(d) d^2, for data in
+    /// which nobody has said which lines are bad.  loss: ECC_LOSS_HUBER, ECC_LOSS_TRUNCATED or ECC_LOSS_GEMAN_MCCLURE; delta > 0:
+    /// its scale in the units of the data (infinity down-weights nothing: the bits of evaluate()).  Returns sum c / n_pairs;
+    /// inlier_mass (nullable): sum u / n_pairs; pair_terms (nullable): n_pairs x 3 floats, pair-major, per pair i < j {c, u, r}: the
+    /// value, the mean IRLS weight of its samples and their mean squared raw residual (robustScale takes delta from r).  One Radon
+    /// intermediate per view, as for evaluate() (ecc_hip.h).  Single device only.
+    double evaluateRobust(int loss, float delta, double* inlier_mass = 0x0, std::vector<float>* pair_terms = 0x0)
+    {
+        if (m_gh) throw std::runtime_error("evaluateRobust: not available on a device group");
+        const size_t n = Ps.size();
+        if (pair_terms) pair_terms->assign(3 * (n * (n > 0 ? n - 1 : 0) / 2), 0.f);
+        double value = 0.0;
+        detail::check(ecc_metric_evaluate_robust(m_h, loss, delta, &value, inlier_mass,
+                                                 (pair_terms && !pair_terms->empty()) ? pair_terms->data() : 0x0));
+        return value;
+    }
+
+    /// Not in the reference: ecc_metric_evaluate_robust_pairs -- evaluateRobust over an index list of (P0, P1, D0, D1) tuples as
+    /// evaluate(indices) takes them (4 ints per tuple).  Returns sum c / n_pairs over the list; inlier_mass (nullable): sum u /
+    /// n_pairs; pair_terms (nullable): n_pairs x 3 floats {c, u, r} in list order.  The sampling mode resolves from the list's length
+    /// (ecc_hip.h).  Single device only.
+    double evaluateRobustPairs(const std::vector<int>& indices, int loss, float delta, double* inlier_mass = 0x0,
+                               std::vector<float>* pair_terms = 0x0)
+    {
+        if (m_gh) throw std::runtime_error("evaluateRobustPairs: not available on a device group");
+        if (indices.size() % 4) throw std::runtime_error("evaluateRobustPairs: four indices per tuple");
+        const std::vector<int32_t> idx(indices.begin(), indices.end());
+        if (pair_terms) pair_terms->assign(3 * (idx.size() / 4), 0.f);
+        double value = 0.0;
+        if (inlier_mass) *inlier_mass = 0.0;
+        detail::check(ecc_metric_evaluate_robust_pairs(m_h, idx.empty() ? 0x0 : idx.data(), (int)(idx.size() / 4), loss, delta, &value,
+                                                       inlier_mass, (pair_terms && !pair_terms->empty()) ? pair_terms->data() : 0x0));
+        return value;
+    }
+#ifdef ECC_ADAPTER_HAVE_EIGEN
+    double evaluateRobustPairs(const std::vector<Eigen::Vector4i>& indices, int loss, float delta, double* inlier_mass = 0x0,
+                               std::vector<float>* pair_terms = 0x0)
+    {
+        std::vector<int> idx(4 * indices.size());
+        for (size_t i = 0; i < indices.size(); ++i)
+            for (int k = 0; k < 4; ++k) idx[4 * i + k] = indices[i][k];
+        return evaluateRobustPairs(idx, loss, delta, inlier_mass, pair_terms);
+    }
+#endif
+
+    /// ecc_host_robust_scale: a scale delta for evaluateRobust from the rows {c, u, r} of an earlier call (normally the one with
+    /// delta = infinity): k x the median over the pairs with r > 0 of sqrt(r); 0.0 without such a pair.  Touches no device.
+    static double robustScale(const std::vector<float>& pair_terms, double k = 1.0)
+    {
+        if (pair_terms.size() % 3) throw std::runtime_error("robustScale: three floats per pair");
+        return ecc_host_robust_scale(pair_terms.empty() ? 0x0 : pair_terms.data(), (int64_t)(pair_terms.size() / 3), k);
+    }
+
     /// Not in the reference: ecc_metric_evaluate_weighted_pose_deltas -- evaluatePoseDeltas for the metric with per-line weights
     /// (intermediates as for evaluateWeighted).  values[k] and coverages[k] (coverages nullable) are bit-identical to replacing the
     /// views moved_views[k] by moved_Ps[k], setProjectionMatrices and evaluateWeighted(); the current matrices stay.  Single device only.

@@ -274,6 +274,18 @@ struct EccWeightedParams {
     int64_t col_stride;
 };
 
+// ---- the metric under a per-sample robust loss (robust_kernel.hip) --------------------------------------
+// One intermediate per view, as for pairs_kernel.  Three float32 entries per pair -- the value c, the inlier mass u and the mean
+// squared raw residual r -- stored COLUMN-major with the Gram form's col_stride rule.
+enum { ECC_ROBUST_HUBER = 0, ECC_ROBUST_TRUNCATED = 1, ECC_ROBUST_GEMAN_MCCLURE = 2 };  // == ECC_LOSS_* of include/ecc_hip.h (ecc_robust.hip asserts it)
+struct EccRobustParams {
+    float* values;                 // 3 columns of col_stride floats
+    int64_t col_stride;
+    int loss;                      // ECC_ROBUST_*, launch-uniform
+    float delta;                   // the scale, > 0; +infinity: no sample is down-weighted
+    float inv_delta;               // (float)(1.0 / (double)delta), formed on the host
+};
+
 // ---- projection pre-processing ------------------------------------------------
 #define ECC_PRE_MAX_CHUNKS 32  // workgroups per image of the maximum search in front of PreProccess::process (normalize)
 struct EccPreprocessParams {

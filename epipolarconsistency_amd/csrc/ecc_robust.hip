@@ -1,0 +1,163 @@
+// ecc_robust.hip -- ecc_metric_evaluate_robust[_pairs], ecc_host_robust_scale: the metric under a per-sample robust loss (host
+// code; include/ecc_hip.h states the contract, robust_kernel.hip has the pair kernels, sum_kernel.hip the sums).  Line weights
+// (ecc_weighted.hip) need a caller who knows where the bad lines are; a fluoroscopy tracker or an FD-CT motion correction often
+// does not -- an instrument nobody flagged, a truncated view, a detector defect that appears mid-scan -- and the squared difference
+// then lets a few percent of the samples decide the value.  Every loss here is rho(d) = w(d) d^2, so the kernel is the weighted
+// kernel with its per-sample factor computed from the residual instead of gathered.
+//
+// The launches: E1 (if the device geometry is behind the matrices), k01_kernel over all pairs or the list into the Gram call's
+// records (scratch of the Gram-family calls alone), pairs_robust_kernel, sum_gram_kernel over the columns c and u, the copies.  The
+// metric's kept records, kept values and pose-batch values are not touched (the list form stages its tuples in the pose batch's
+// index scratch, as ecc_metric_evaluate_weighted_pairs does).
+// Not here: pose-delta, transform, range, group and RCCL forms; the loss combined with line weights on a 2 n metric; the loss under
+// use_corr; Tukey's biweight (not d^2 near zero: no bit link to ecc_metric_evaluate_all).
+#include "ecc_capi_internal.h"
+#include "ecc_sum_order.h"
+
+using namespace ecc_internal;
+
+static_assert(ECC_LOSS_HUBER == ECC_ROBUST_HUBER && ECC_LOSS_TRUNCATED == ECC_ROBUST_TRUNCATED &&
+                  ECC_LOSS_GEMAN_MCCLURE == ECC_ROBUST_GEMAN_MCCLURE,
+              "the kernels' loss codes are the header's");
+
+extern "C" hipError_t ecc_launch_sum_gram(const float* values_d, long long col_stride, long long count, int n_columns, int n_slices,
+                                          double* partial_d, hipStream_t stream);
+extern "C" hipError_t ecc_launch_pairs_robust(const EccPairParams* p, const EccRobustParams* g, hipStream_t stream);
+
+namespace {
+
+constexpr int T = 3;  // columns: c, u, r
+
+// What both calls need of their arguments and of the metric (after the null check of m), before the device is touched.
+int robust_check(const ecc_metric* m, const double* value, int loss, float delta)
+{
+    if (!value) return fail(ECC_ERR_INVALID_ARGUMENT, "value is null");
+    if (loss < ECC_LOSS_HUBER || loss > ECC_LOSS_GEMAN_MCCLURE) return fail(ECC_ERR_INVALID_ARGUMENT, "loss is none of ECC_LOSS_*");
+    if (!(delta > 0.f)) return fail(ECC_ERR_INVALID_ARGUMENT, "delta must be positive (+infinity allowed)");
+    if (m->n_views < 1) return fail(ECC_ERR_INVALID_ARGUMENT, "projection matrices have not been set");
+    if (m->n_views < 2) return fail(ECC_ERR_INVALID_ARGUMENT, "need at least two views (the reference divides 0/0 here)");
+    if (m->use_corr) return fail(ECC_ERR_UNSUPPORTED, "the robust loss is not defined for the correlation cost");
+    return ECC_OK;
+}
+
+// The robust pair launch (robust_kernel.hip) between the context's timing events, as launch_weighted_timed.
+hipError_t launch_robust_timed(ecc_ctx* ctx, const EccPairParams* p, const EccRobustParams* g)
+{
+    if (ctx->timing) {
+        const hipError_t e = hipEventRecord(ctx->ev[0], ctx->stream);
+        if (e != hipSuccess) return e;
+    }
+    const hipError_t e = ecc_launch_pairs_robust(p, g, ctx->stream);
+    if (e != hipSuccess || !ctx->timing) return e;
+    const hipError_t e1 = hipEventRecord(ctx->ev[1], ctx->stream);
+    if (e1 == hipSuccess) ctx->ev_valid[0] = true;
+    return e1;
+}
+
+// Everything behind the checks: `count` pairs -- all pairs (idx4 null) or the list -- under the sampling mode of that many values.
+int robust_run(ecc_metric* m, const int32_t* idx4, int64_t count, int loss, float delta, double* value, double* inlier_mass, float* pair_terms)
+{
+    ecc_ctx* ctx = m->ctx;
+    int rc = set_device(ctx);
+    if (rc) return rc;
+    const int64_t col_stride = (count + 3) & ~(int64_t)3;
+    // (as the first large all-pairs evaluation does: whether this scan's pairs would read row-quad copies; the same bits either way)
+    if (!idx4 && !m->quads_decided && count >= 32768) decide_quad_copies(m);
+    EccPairParams p;
+    rc = fill_pair_params(m, &p, count, /*need_e1=*/false);
+    if (rc) return rc;
+    rc = m->gram_records_d.ensure(count, ctx->stream);
+    if (!rc) rc = m->gram_values_d.ensure((int64_t)T * col_stride, ctx->stream);
+    if (!rc) rc = m->gram_partial_d.ensure((int64_t)2 * ecc_sum::SLICES, ctx->stream);
+    if (!rc && idx4) rc = m->pose_idx_d.ensure(4 * count, ctx->stream);
+    if (rc) return rc;
+    ecc_mark_busy(m);
+    rc = ensure_e1(m);  // (see ecc_metric_evaluate_gram)
+    if (rc) return rc;
+    if (idx4) {
+        HIP_TRY(hipMemcpyAsync(m->pose_idx_d.ptr, idx4, sizeof(int32_t) * 4 * (size_t)count, hipMemcpyHostToDevice, ctx->stream));
+        p.indices = m->pose_idx_d.ptr;
+    }
+    p.first = 0;
+    p.count = count;
+    p.records = m->gram_records_d.ptr;
+    HIP_TRY(ecc_launch_k01(&p, ctx->stream));
+    EccRobustParams g;
+    g.values = m->gram_values_d.ptr;
+    g.col_stride = col_stride;
+    g.loss = loss;
+    g.delta = delta;
+    g.inv_delta = (float)(1.0 / (double)delta);
+    HIP_TRY(launch_robust_timed(ctx, &p, &g));
+    // c and u in the order an evaluation of `count` values is added in (ecc_sum_order.h); r is not summed
+    const int n_slices = ecc_sum::slices(count, m->sum_scratch_d.ptr != nullptr);
+    HIP_TRY(ecc_launch_sum_gram(m->gram_values_d.ptr, col_stride, count, 2, n_slices, m->gram_partial_d.ptr, ctx->stream));
+    std::vector<double> partial((size_t)2 * ecc_sum::SLICES);
+    HIP_TRY(hipMemcpyAsync(partial.data(), m->gram_partial_d.ptr, sizeof(double) * partial.size(), hipMemcpyDeviceToHost, ctx->stream));
+    std::vector<float> cols;
+    if (pair_terms) {
+        cols.resize((size_t)T * (size_t)col_stride);
+        HIP_TRY(hipMemcpyAsync(cols.data(), m->gram_values_d.ptr, sizeof(float) * cols.size(), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(wait_stream_spin(ctx->stream));
+    m->done_generation = m->set_generation;
+    m->quiet = true;  // the copies are the last thing this call queued, and they have landed
+    double sum_c = 0.0, sum_u = 0.0;
+    for (int s = 0; s < n_slices; ++s) sum_c += partial[(size_t)s];
+    for (int s = 0; s < n_slices; ++s) sum_u += partial[(size_t)ecc_sum::SLICES + s];
+    // a mean over the pairs, ref: ...RadonIntermediate.cpp:224 with all weights 1 -- NOT divided by the inlier mass: that would reward
+    // pushing samples into the tails
+    *value = sum_c / (double)count;
+    if (inlier_mass) *inlier_mass = sum_u / (double)count;
+    if (pair_terms)
+        for (int64_t q = 0; q < count; ++q)
+            for (int u = 0; u < T; ++u) pair_terms[(size_t)q * T + u] = cols[(size_t)u * col_stride + q];
+    return ECC_OK;
+}
+
+}  // namespace
+
+ECC_EXPORT int ecc_metric_evaluate_robust(ecc_metric* m, int loss, float delta, double* value, double* inlier_mass, float* pair_terms)
+{
+    if (!m) return fail(ECC_ERR_INVALID_ARGUMENT, "metric is null");
+    int rc = robust_check(m, value, loss, delta);
+    if (rc) return rc;
+    const int64_t n = m->n_views;
+    if ((int64_t)m->dtrs.size() < n) return fail(ECC_ERR_INVALID_ARGUMENT, "fewer Radon intermediates than projection matrices");
+    return robust_run(m, nullptr, n * (n - 1) / 2, loss, delta, value, inlier_mass, pair_terms);
+}
+
+ECC_EXPORT int ecc_metric_evaluate_robust_pairs(ecc_metric* m, const int32_t* idx4, int n_pairs, int loss, float delta, double* value,
+                                                double* inlier_mass, float* pair_terms)
+{
+    if (!m) return fail(ECC_ERR_INVALID_ARGUMENT, "metric is null");
+    if (n_pairs < 0) return fail(ECC_ERR_INVALID_ARGUMENT, "negative list length");
+    if (n_pairs > 0 && !idx4) return fail(ECC_ERR_INVALID_ARGUMENT, "index list is null");
+    int rc = robust_check(m, value, loss, delta);
+    if (rc) return rc;
+    // range check as ecc_metric_evaluate_pairs: P index the current matrices, D the Radon intermediates
+    const int nP = m->n_views, nD = (int)m->dtrs.size();
+    for (int q = 0; q < n_pairs; ++q) {
+        const int32_t* t = idx4 + 4 * (size_t)q;
+        if (t[0] < 0 || t[0] >= nP || t[1] < 0 || t[1] >= nP || t[2] < 0 || t[2] >= nD || t[3] < 0 || t[3] >= nD)
+            return fail(ECC_ERR_INVALID_ARGUMENT, "index array contains invalid indices");
+    }
+    if (n_pairs == 0) return ECC_OK;
+    return robust_run(m, idx4, n_pairs, loss, delta, value, inlier_mass, pair_terms);
+}
+
+// k x the median of sqrt(r_q) over the rows {c, u, r} with r_q > 0 (even count: the mean of the two middle values); 0.0 with no such
+// row.  Host only.
+ECC_EXPORT double ecc_host_robust_scale(const float* pair_terms, int64_t n_pairs, double k)
+{
+    std::vector<double> rms;
+    if (pair_terms)
+        for (int64_t q = 0; q < n_pairs; ++q) {
+            const float r = pair_terms[(size_t)q * T + 2];
+            if (r > 0.f) rms.push_back(std::sqrt((double)r));
+        }
+    if (rms.empty()) return 0.0;
+    std::sort(rms.begin(), rms.end());
+    const size_t h = rms.size() / 2;
+    return k * (rms.size() & 1 ? rms[h] : (rms[h - 1] + rms[h]) / 2.0);
+}

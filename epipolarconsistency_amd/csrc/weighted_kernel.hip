@@ -22,7 +22,7 @@
 // its own.
 // Index lists and pose deltas launch these kernels over their own records (ecc_weighted_poses.hip).
 // Not here (include/ecc_hip.h): full-matrices pose batches, transform, range, group and RCCL forms; weights under the correlation
-// cost; a 1 / (sigma0^2 + sigma1^2) variance form; a per-sample robust loss.
+// cost; a 1 / (sigma0^2 + sigma1^2) variance form.  A per-sample robust loss is robust_kernel.hip (not combined with these weights).
 #include <hip/hip_runtime.h>
 #include <float.h>
 

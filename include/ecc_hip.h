@@ -616,7 +616,8 @@ int ecc_metric_evaluate_view_hessian(ecc_metric* m, int n_channels, double* hess
  * Index lists and pose deltas: ecc_metric_evaluate_weighted_pairs, ecc_metric_evaluate_weighted_pose_deltas below.
  * The registration of two scans: ecc_metric_evaluate_weighted_transforms below.
  * Out of scope: full-matrices pose batches, range, group and RCCL forms; weights under use_corr; a
- * 1 / (sigma0^2 + sigma1^2) variance form; a per-sample robust loss. */
+ * 1 / (sigma0^2 + sigma1^2) variance form.  A per-sample robust loss, for callers who do not know where the bad lines are:
+ * ecc_metric_evaluate_robust below (on a metric of n_views intermediates; not combined with line weights). */
 int ecc_metric_evaluate_weighted(ecc_metric* m, double* value, double* coverage, float* pair_terms);
 
 /* The weighted metric for pose optimisers (csrc/ecc_weighted_poses.hip): a tracker that scores one frame against
@@ -727,6 +728,68 @@ void ecc_host_compose_transform(const double* P12, const double* T16, double* ou
  * weights under use_corr. */
 int ecc_metric_evaluate_weighted_transforms(ecc_metric* m, int n_source, int n_transforms, const double* Ts, double* values,
                                             double* coverages, float* pair_terms);
+
+/* The metric under a PER-SAMPLE ROBUST LOSS (csrc/ecc_robust.hip, csrc/robust_kernel.hip): for callers who do NOT
+ * know where the bad lines are -- an instrument nobody flagged, a truncated view, a detector defect that appears mid-scan.  The
+ * squared difference lets a few percent of the samples decide the value; line weights (above) need somebody to say which.  Every
+ * loss here is rho(d) = w(d) d^2 with an IRLS weight w in (0, 1], so the kernel is the weighted kernel with its per-sample factor
+ * computed from the residual instead of gathered: four gathers per kappa step instead of eight, and the same bit-for-bit link to
+ * ecc_metric_evaluate_all.
+ *
+ * For a pair a +-kappa sample has the positions, kappa range and sampling mode of ecc_metric_evaluate_all; d is that evaluation's
+ * difference of the two signed data samples.  delta is a float32 > 0; +infinity is allowed and down-weights nothing;
+ * inv_delta = (float)(1.0 / (double)delta) is formed on the host.  Per sample, every operation one float32 operation, nothing
+ * contracted unless written as fmaf, the division the IEEE one:
+ *     a = fabsf(d)        t = fminf(1.0f, delta / a)                       (a == 0: +inf -> 1)
+ *     ECC_LOSS_HUBER           w = t * (2.0f - t)                          rho = d^2 inside delta, 2 delta |d| - delta^2 outside
+ *     ECC_LOSS_TRUNCATED       w = t * t                                   rho = min(d^2, delta^2)
+ *     ECC_LOSS_GEMAN_MCCLURE   s = a * inv_delta; w = 1.0f / fmaf(s, s, 1.0f)   rho = d^2 delta^2 / (delta^2 + d^2)
+ * Per kappa step the value term is the weighted call's expression with w in place of mu --
+ *     polynomial loops             fmaf(w_p * dp, dp, (w_m * dm) * dm) * w06_dkappa
+ *     exact and reference loops    (((w_p * dp) * dp + (w_m * dm) * dm) * K0[6]) * dkappa
+ * -- accumulated in float64 per lane in the same trip order and reduced by the same wave tree, so w == 1.0f gives
+ * ecc_metric_evaluate_all's bits.  Beside it each lane adds (double)(w_p + w_m), the weight mass, (double)(dp * dp) +
+ * (double)(dm * dm), the raw squares (products in float32), and 2.0, the sample count.  Per pair q, three float32 columns:
+ *     c_q = the value,
+ *     u_q = (float)(mass / count), the mean IRLS weight: the INLIER MASS in (0, 1],
+ *     r_q = (float)(raw / count), the mean squared raw residual, independent of loss and delta;
+ *     a pair without samples, or a list tuple with P0 == P1, has {0, 1, 0}.
+ *   value (required): sum c_q / n_pairs, the sum in the order of csrc/ecc_sum_order.h for that many values, then the division an
+ *     all-pairs or list evaluation makes.  A mean, NOT divided by the inlier mass: dividing would reward pushing samples into the tails.
+ *   inlier_mass (nullable): sum u_q / n_pairs.
+ *   pair_terms (host, nullable): n_pairs x 3 float32, pair-major, rows {c_q, u_q, r_q}; get_ij order (all pairs), list order (list).
+ * ecc_metric_evaluate_robust takes whatever metric ecc_metric_evaluate_all takes; the sampling mode resolves from n (n - 1) / 2 as
+ * there.  ecc_metric_evaluate_robust_pairs takes (P0, P1, D0, D1) tuples as ecc_metric_evaluate_pairs does; its mode resolves from
+ * the list's length; n_pairs == 0: ECC_OK, nothing written.  Both take ECC_SAMPLING_POLYNOMIAL (with its per-pair fallback and exact
+ * tail), _PER_SAMPLE and _REFERENCE (one or four waves per pair), a fixed or automatic object radius, a user dkappa, non-derivative
+ * data and row-paired and row-quad copies.
+ *
+ * ecc_host_robust_scale: k x the median of sqrt((double)r_q) over the rows with r_q > 0 (even count: the mean of the two middle
+ * values); no such row: 0.0.  Touches no device.  The intended use: one call with delta = INFINITY -- which is also
+ * ecc_metric_evaluate_all's value --, then delta = ecc_host_robust_scale(terms, n_pairs, k).  A minority of corrupted views reaches
+ * a minority of the pairs, so the median over pairs stays put where the pooled rms does not.
+ *
+ * The contract (tests/test_gpu_robust.py):
+ *   1. delta = +infinity or FLT_MAX: the c column and value have the bits of ecc_metric_evaluate_all (the list form: of
+ *      ecc_metric_evaluate_pairs of that list), every u_q and inlier_mass are 1.0.
+ *   2. {c, u, r} agree with a float64 oracle (tests/robust_terms.py) to the project's bars.
+ *   3. A block pasted into one view: the pairs without that view keep their bits; corrupted / clean is ordered
+ *      truncated < Huber < ecc_metric_evaluate_all and Geman-McClure < Huber.
+ *   - The calls change nothing a later call can see: current matrices, kept records, the kept values of the pose-delta mode and of
+ *     the pose batch.  (They share ecc_metric_evaluate_gram's scratch; the list form stages its tuples in the pose batch's index
+ *     scratch.)
+ *   - Errors before anything is launched or written, ECC_ERR_INVALID_ARGUMENT: m == NULL (checked first); value == NULL; idx4 == NULL
+ *     with n_pairs > 0; n_pairs < 0; loss outside 0..2; delta NaN or <= 0; no matrices set or fewer than two views (the all-pairs
+ *     call: fewer intermediates than views); a bad tuple.  ECC_ERR_UNSUPPORTED under use_corr.
+ * Launches: the record kernel over all pairs or the list, pairs_robust_kernel -- one wave per pair, the position arithmetic of a
+ * kappa step once, 4 gathers --, one launch for the sums of c and u (r is not summed), the copies.
+ * Not built: pose-delta, transform, range, group and RCCL forms; the loss combined with line weights on a 2 n metric; the loss under
+ * use_corr; Tukey's biweight (not d^2 near zero, so no bit link to ecc_metric_evaluate_all). */
+enum { ECC_LOSS_HUBER = 0, ECC_LOSS_TRUNCATED = 1, ECC_LOSS_GEMAN_MCCLURE = 2 };
+int ecc_metric_evaluate_robust(ecc_metric* m, int loss, float delta, double* value, double* inlier_mass, float* pair_terms);
+int ecc_metric_evaluate_robust_pairs(ecc_metric* m, const int32_t* idx4, int n_pairs, int loss, float delta, double* value,
+                                     double* inlier_mass, float* pair_terms);
+double ecc_host_robust_scale(const float* pair_terms, int64_t n_pairs, double k);
 
 /* Multi-GPU building block: evaluate only pairs ij in [first, first+count) of the get_ij order
  * (ref: EpipolarConsistencyCommon.hxx:52-79); returns the partial sum (float64) -- the caller
