@@ -466,32 +466,31 @@ hipError_t launch_transform_list(ecc_metric* m, int n_source, int K, long long s
 int weighted_check(const ecc_metric* m);
 int weighted_base_columns(ecc_metric* m, EccPairParams* p, EccWeightedParams* g);
 
-// The pair launch p -- or, with x, the one-launch evaluation -- on the context's stream between its timing events (ecc_ctx_enable_timing).
-inline hipError_t launch_pairs_timed(ecc_ctx* ctx, const EccPairParams* p, const EccSmallEval* x = nullptr)
+// launch(stream) on the context's stream between its timing events (ecc_ctx_enable_timing).
+template <class Launch>
+inline hipError_t launch_timed(ecc_ctx* ctx, Launch&& launch)
 {
     if (ctx->timing) {
         const hipError_t e = hipEventRecord(ctx->ev[0], ctx->stream);
         if (e != hipSuccess) return e;
     }
-    const hipError_t e = x ? ecc_launch_small_eval(p, x, ctx->stream) : ecc_launch_pairs(p, ctx->stream);
+    const hipError_t e = launch(ctx->stream);
     if (e != hipSuccess || !ctx->timing) return e;
     const hipError_t e1 = hipEventRecord(ctx->ev[1], ctx->stream);
     if (e1 == hipSuccess) ctx->ev_valid[0] = true;
     return e1;
 }
 
+// The pair launch p -- or, with x, the one-launch evaluation -- between those events.
+inline hipError_t launch_pairs_timed(ecc_ctx* ctx, const EccPairParams* p, const EccSmallEval* x = nullptr)
+{
+    return launch_timed(ctx, [&](hipStream_t s) { return x ? ecc_launch_small_eval(p, x, s) : ecc_launch_pairs(p, s); });
+}
+
 // The weighted pair launch (weighted_kernel.hip) between the same events.
 inline hipError_t launch_weighted_timed(ecc_ctx* ctx, const EccPairParams* p, const EccWeightedParams* g)
 {
-    if (ctx->timing) {
-        const hipError_t e = hipEventRecord(ctx->ev[0], ctx->stream);
-        if (e != hipSuccess) return e;
-    }
-    const hipError_t e = ecc_launch_pairs_weighted(p, g, ctx->stream);
-    if (e != hipSuccess || !ctx->timing) return e;
-    const hipError_t e1 = hipEventRecord(ctx->ev[1], ctx->stream);
-    if (e1 == hipSuccess) ctx->ev_valid[0] = true;
-    return e1;
+    return launch_timed(ctx, [&](hipStream_t s) { return ecc_launch_pairs_weighted(p, g, s); });
 }
 
 }  // namespace ecc_internal

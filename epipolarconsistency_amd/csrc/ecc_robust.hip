@@ -40,20 +40,6 @@ int robust_check(const ecc_metric* m, const double* value, int loss, float delta
     return ECC_OK;
 }
 
-// The robust pair launch (robust_kernel.hip) between the context's timing events, as launch_weighted_timed.
-hipError_t launch_robust_timed(ecc_ctx* ctx, const EccPairParams* p, const EccRobustParams* g)
-{
-    if (ctx->timing) {
-        const hipError_t e = hipEventRecord(ctx->ev[0], ctx->stream);
-        if (e != hipSuccess) return e;
-    }
-    const hipError_t e = ecc_launch_pairs_robust(p, g, ctx->stream);
-    if (e != hipSuccess || !ctx->timing) return e;
-    const hipError_t e1 = hipEventRecord(ctx->ev[1], ctx->stream);
-    if (e1 == hipSuccess) ctx->ev_valid[0] = true;
-    return e1;
-}
-
 // Everything behind the checks: `count` pairs -- all pairs (idx4 null) or the list -- under the sampling mode of that many values.
 int robust_run(ecc_metric* m, const int32_t* idx4, int64_t count, int loss, float delta, double* value, double* inlier_mass, float* pair_terms)
 {
@@ -88,7 +74,7 @@ int robust_run(ecc_metric* m, const int32_t* idx4, int64_t count, int loss, floa
     g.loss = loss;
     g.delta = delta;
     g.inv_delta = (float)(1.0 / (double)delta);
-    HIP_TRY(launch_robust_timed(ctx, &p, &g));
+    HIP_TRY(launch_timed(ctx, [&](hipStream_t s) { return ecc_launch_pairs_robust(&p, &g, s); }));  // (robust_kernel.hip)
     // c and u in the order an evaluation of `count` values is added in (ecc_sum_order.h); r is not summed
     const int n_slices = ecc_sum::slices(count, m->sum_scratch_d.ptr != nullptr);
     HIP_TRY(ecc_launch_sum_gram(m->gram_values_d.ptr, col_stride, count, 2, n_slices, m->gram_partial_d.ptr, ctx->stream));

@@ -65,12 +65,7 @@ int weighted_base_columns(ecc_metric* m, EccPairParams* p_out, EccWeightedParams
     g.quad_channel_bytes = n * m->quad_floats * (int64_t)sizeof(float);
     g.values = m->gram_values_d.ptr;
     g.col_stride = col_stride;
-    if (ctx->timing) HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
-    HIP_TRY(ecc_launch_pairs_weighted(&p, &g, ctx->stream));
-    if (ctx->timing) {
-        HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
-        ctx->ev_valid[0] = true;
-    }
+    HIP_TRY(launch_weighted_timed(ctx, &p, &g));
     return ECC_OK;
 }
 }  // namespace ecc_internal

@@ -7,9 +7,10 @@
 //   value = sum_kappa (delta+^2 + delta-^2) K0[6] dkappa,
 //   h0[c] = sum_kappa (delta+ v0+_c + delta- v0-_c) K0[6] dkappa = 1/2 d value / d a_c,i,
 //   h1[c] = -sum_kappa (delta+ v1+_c + delta- v1-_c) K0[6] dkappa = 1/2 d value / d a_c,j.
-// pairs_coeff_kernel<DERIV, NC> is pairs_gram_kernel (gram_kernel.hip) with other products behind the same 4 NC gathers: one wave per
-// pair, the record and the pair's 2 NC coefficients in scalar registers, the same dispatch over the record's degree and the slab
-// size, per-lane float64 sums in the same trip order, the same wave tree.  A side's combined sample is formed in channel order,
+// pairs_coeff_kernel<DERIV, NC> runs on the frames of ecc_pair_forms.h: form_accumulate, form_loop_poly,
+// form_loop_exact.  CoeffForm's trip gathers NC footprints at each of the four taps and keeps all 4 NC samples, combines each side with
+// the pair's 2 NC coefficients (scalar registers), and adds the value and the 2 NC gradient products to per-lane float64 sums in trip
+// order; the kernel body and the reference kernels stay here.  A side's combined sample is formed in channel order,
 // s = a_0 v_0, then s = fmaf(a_c, v_c, s); the two differences and the value term are pairs_kernel's expressions:
 //   polynomial loops   fmaf(dp, dp, dm * dm) * w06_dkappa       (unsigned samples; the folds' relative sign in the differences)
 //   exact loop         ((dp * dp + dm * dm) * K0[6]) * dkappa   (signed samples)
@@ -24,7 +25,7 @@
 #include <float.h>
 
 #include "ecc_layout.h"
-#include "ecc_pairs_device.h"
+#include "ecc_pair_forms.h"
 
 namespace {
 
@@ -52,47 +53,29 @@ __device__ __forceinline__ void pair_coefficients(const float* __restrict__ coef
     }
 }
 
-// gram_loop_poly (gram_kernel.hip) with the coefficient products: returns the lane's first sample index past the fit's range.
-// chan: bytes from a view's copy to the same view's copy of the next channel (wave-uniform).
-template <bool DERIV, int NC, int PITCH4, int DEG, bool NOCLAMP>
-__device__ __forceinline__ int coeff_loop_poly(int lane, int k_limit, const EccPairRecord* __restrict__ rec, float dkappa,
-                                               float kappa_fit, float w06, const SlabView sv0, const SlabView sv1, long long chan,
-                                               float n_alpha_f, float n_t_f, float pitch4_f, const float (&a0)[NC], const float (&a1)[NC],
-                                               double (&acc)[coeff_entries(NC)])
-{
-    float ca[2][ECC_POLY_DEG + 3], cd[2][ECC_POLY_DEG + 2];
-    unsigned fold[2];
-#pragma unroll
-    for (int v = 0; v < 2; ++v) {
-        fold[v] = (unsigned)__builtin_amdgcn_readfirstlane((int)rec->fold[v]);
-#pragma unroll
-        for (int k = 0; k <= ECC_POLY_DEG + 1; ++k) {
-            if (k > DEG && k <= ECC_POLY_DEG) continue;
-            ca[v][k] = uniformf(rec->ca[v][k]);
-            cd[v][k] = uniformf(rec->cd[v][k]);
-        }
-        ca[v][ECC_POLY_DEG + 2] = uniformf(rec->ca[v][ECC_POLY_DEG + 2]);
+// the trips of the polynomial and the exact loops (form_loop_poly, form_loop_exact, ecc_pair_forms.h): NC gathers at each of the four
+// taps, every sample kept, the two combined differences, the 1 + 2 NC products
+template <int NC>
+struct CoeffForm : ChannelForm<EccViewCoeffParams> {
+    const float (&a0)[NC];
+    const float (&a1)[NC];
+    double (&acc)[coeff_entries(NC)];
+    float w1;  // view j's terms in a polynomial loop: the weight with the relative sign (header comment)
+
+    __device__ __forceinline__ CoeffForm(const EccViewCoeffParams& g, const float (&a0)[NC], const float (&a1)[NC], double (&acc)[coeff_entries(NC)])
+        : ChannelForm(g), a0(a0), a1(a1), acc(acc)
+    {
     }
-    const float xs = uniformf(rec->x_scale);
-    const float xa_max = n_alpha_f + 0.5f;
-    const float rel_sign = (DERIV && ((fold[0] ^ fold[1]) & 0x80000000u)) ? 1.0f : -1.0f;  // see kappa_loop_poly
-    const float w06_dkappa = w06 * dkappa;
-    const float w1 = rel_sign * w06_dkappa;  // view j's terms: the weight with the relative sign (header comment)
-    float kf = (float)lane;
-    int k = lane;
-    for (; k < k_limit; k += 64, kf += 64.f) {
-        const float kappa = dkappa * 0.5f + dkappa * kf;  // ref: ...RadonIntermediate.cu:259 (same fp32 ops)
-        if (kappa >= kappa_fit) break;
-        const float x = kappa * xs, z = x * x;
-        float xa0p, xa0m, yd0p, yd0m, xa1p, xa1m, yd1p, yd1m;
-        poly_pm<DEG>(ca[0], ca[0][ECC_POLY_DEG + 1], ca[0][ECC_POLY_DEG + 2], false, x, z, xa0p, xa0m);
-        poly_pm<DEG>(cd[0], cd[0][ECC_POLY_DEG + 1], 0.f, true, x, z, yd0p, yd0m);
-        poly_pm<DEG>(ca[1], ca[1][ECC_POLY_DEG + 1], ca[1][ECC_POLY_DEG + 2], false, x, z, xa1p, xa1m);
-        poly_pm<DEG>(cd[1], cd[1][ECC_POLY_DEG + 1], 0.f, true, x, z, yd1p, yd1m);
-        const SampleTap t0p = sample_tap<PITCH4, NOCLAMP>(xa0p, yd0p, sv0, n_t_f, pitch4_f, xa_max);
-        const SampleTap t1p = sample_tap<PITCH4, NOCLAMP>(xa1p, yd1p, sv1, n_t_f, pitch4_f, xa_max);
-        const SampleTap t0m = sample_tap<PITCH4, NOCLAMP>(xa0m, yd0m, sv0, n_t_f, pitch4_f, xa_max);
-        const SampleTap t1m = sample_tap<PITCH4, NOCLAMP>(xa1m, yd1m, sv1, n_t_f, pitch4_f, xa_max);
+
+    __device__ __forceinline__ void poly_begin(const SlabView sv0, const SlabView sv1, float rel_sign, float w06_dkappa)
+    {
+        w1 = rel_sign * w06_dkappa;
+        ChannelForm::poly_begin(sv0, sv1, rel_sign, w06_dkappa);
+    }
+
+    __device__ __forceinline__ void poly_trip(const SlabView sv0, const SlabView sv1, const SampleTap t0p, const SampleTap t1p,
+                                              const SampleTap t0m, const SampleTap t1m, float rel_sign, float w06_dkappa)
+    {
         float v0p[NC], v1p[NC], v0m[NC], v1m[NC];
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
@@ -111,99 +94,32 @@ __device__ __forceinline__ int coeff_loop_poly(int lane, int k_limit, const EccP
             acc[1 + NC + c] += (double)(fmaf(dp, v1p[c], dm * v1m[c]) * w1);
         }
     }
-    return k;
-}
 
-// gram_loop_exact (gram_kernel.hip) with the coefficient products: kappa_step's expressions on the signed samples.
-template <bool DERIV, int NC, bool REDUCE, int PITCH4>
-__device__ __forceinline__ void coeff_loop_exact(int k_first, int k_limit, const float (&K0)[8], const float (&K1)[8], const SlabView sv0,
-                                                 const SlabView sv1, long long chan, float n_alpha_f, float n_t_f, float dist_scale,
-                                                 float dist_bias, float pitch4_f, const float (&a0)[NC], const float (&a1)[NC],
-                                                 double (&acc)[coeff_entries(NC)])
-{
-    const float dkappa = K1[6], kappa_max = K1[7];
-    for (int k = k_first; k < k_limit; k += 64) {
-        const float kappa = dkappa * 0.5f + dkappa * k;  // ref: ...RadonIntermediate.cu:259 (same fp32 ops)
-        if (kappa >= kappa_max) return;
-        float sn, cs;
-        sincos_quadrant<REDUCE>(kappa, sn, cs);
-        const float a00 = K0[0] * cs, a01 = K0[1] * cs, a02 = K0[2] * cs;
-        const float b00 = K0[3] * sn, b01 = K0[4] * sn, b02 = K0[5] * sn;
-        const float a10 = K1[0] * cs, a11 = K1[1] * cs, a12 = K1[2] * cs;
-        const float b10 = K1[3] * sn, b11 = K1[4] * sn, b12 = K1[5] * sn;
-        const LineTap t0p = sample_line_prep<PITCH4>(b00 + a00, b01 + a01, b02 + a02, sv0, n_alpha_f, n_t_f, dist_scale, dist_bias, pitch4_f);
-        const LineTap t1p = sample_line_prep<PITCH4>(b10 + a10, b11 + a11, b12 + a12, sv1, n_alpha_f, n_t_f, dist_scale, dist_bias, pitch4_f);
-        const LineTap t0m = sample_line_prep<PITCH4>(b00 - a00, b01 - a01, b02 - a02, sv0, n_alpha_f, n_t_f, dist_scale, dist_bias, pitch4_f);
-        const LineTap t1m = sample_line_prep<PITCH4>(b10 - a10, b11 - a11, b12 - a12, sv1, n_alpha_f, n_t_f, dist_scale, dist_bias, pitch4_f);
-        // the taps' byte offsets inside a copy (the prepared pointer minus the origin it was formed from: folded away)
-        const unsigned o0p = (unsigned)((GlobalBytes)t0p.ptr - sv0.origin), o1p = (unsigned)((GlobalBytes)t1p.ptr - sv1.origin);
-        const unsigned o0m = (unsigned)((GlobalBytes)t0m.ptr - sv0.origin), o1m = (unsigned)((GlobalBytes)t1m.ptr - sv1.origin);
+    template <bool DERIV, int PITCH4>
+    __device__ __forceinline__ void exact_trip(const SlabView sv0, const SlabView sv1, const LineTap t0p, const LineTap t1p, const LineTap t0m,
+                                               const LineTap t1m, float w06, float dkappa)
+    {
+        const unsigned o0p = line_tap_offset(t0p, sv0), o1p = line_tap_offset(t1p, sv1);
+        const unsigned o0m = line_tap_offset(t0m, sv0), o1m = line_tap_offset(t1m, sv1);
         float v0p[NC], v1p[NC], v0m[NC], v1m[NC];
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             const GlobalBytes o0 = sv0.origin + chan * c, o1 = sv1.origin + chan * c;
-            const auto tap = [](GlobalBytes origin, unsigned off, const LineTap t) {
-                const ecc_v4f_a4 q4 = *(GlobalF4)(origin + off);
-                const F4 q = {q4.x, q4.y, q4.z, q4.w};
-                return line_tap_finish<DERIV>(q, t);
-            };
-            v0p[c] = tap(o0, o0p, t0p);
-            v1p[c] = tap(o1, o1p, t1p);
-            v0m[c] = tap(o0, o0m, t0m);
-            v1m[c] = tap(o1, o1m, t1m);
+            v0p[c] = line_tap_finish<DERIV>(line_footprint(o0, o0p), t0p);
+            v1p[c] = line_tap_finish<DERIV>(line_footprint(o1, o1p), t1p);
+            v0m[c] = line_tap_finish<DERIV>(line_footprint(o0, o0m), t0m);
+            v1m[c] = line_tap_finish<DERIV>(line_footprint(o1, o1m), t1m);
         }
         const float dp = combine_channels<NC>(a0, v0p) - combine_channels<NC>(a1, v1p);
         const float dm = combine_channels<NC>(a0, v0m) - combine_channels<NC>(a1, v1m);
-        acc[0] += (double)(((dp * dp + dm * dm) * K0[6]) * dkappa);  // ref: ...RadonIntermediate.cu:112,269
+        acc[0] += (double)(((dp * dp + dm * dm) * w06) * dkappa);  // ref: ...RadonIntermediate.cu:112,269
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
-            acc[1 + c] += (double)(((dp * v0p[c] + dm * v0m[c]) * K0[6]) * dkappa);
-            acc[1 + NC + c] -= (double)(((dp * v1p[c] + dm * v1m[c]) * K0[6]) * dkappa);  // the minus of v0 - v1
+            acc[1 + c] += (double)(((dp * v0p[c] + dm * v0m[c]) * w06) * dkappa);
+            acc[1 + NC + c] -= (double)(((dp * v1p[c] + dm * v1m[c]) * w06) * dkappa);  // the minus of v0 - v1
         }
     }
-}
-
-// gram_accumulate (gram_kernel.hip): the same choice of loop for the same record, made by the same helpers.
-template <bool DERIV, int NC>
-__device__ __forceinline__ void coeff_accumulate(const EccPairParams& p, const EccViewCoeffParams& g, const EccPairRecord* __restrict__ rec,
-                                                 int iD0, int iD1, int lane, const float (&a0)[NC], const float (&a1)[NC],
-                                                 double (&acc)[coeff_entries(NC)])
-{
-    const unsigned pitch4 = (unsigned)p.pitch * 8u;
-    const SlabView sv0 = {(GlobalBytes)p.dtrs[iD0], pitch4};
-    const SlabView sv1 = {(GlobalBytes)p.dtrs[iD1], pitch4};
-    const long long chan = g.paired_channel_bytes;
-    const float n_alpha_f = (float)p.n_alpha, n_t_f = (float)p.n_t;
-    const float pitch4_f = (float)pitch4;
-    const float kappa_max = uniformf(rec->K1[7]);
-
-    const bool reduce = kappa_max > 0.785398163397448f;  // wave-uniform
-    const int poly_raw = __builtin_amdgcn_readfirstlane(rec->poly_ok);
-    const int poly_ok = poly_raw & ~1;
-    const bool in_range = (poly_raw & 1) != 0;
-    int k_first = lane;
-    if (poly_ok) {
-        const float kappa_fit = ecc_kappa_fit(kappa_max), dkappa = uniformf(rec->K1[6]), w06 = uniformf(rec->K0[6]);
-        poly_loop_dispatch(p.wide_offsets != 0, pitch4, poly_ok, in_range, [&](auto P4, auto DEG, auto NOCL) {
-            k_first = coeff_loop_poly<DERIV, NC, decltype(P4)::value, decltype(DEG)::value, decltype(NOCL)::value>(
-                lane, p.k_limit, rec, dkappa, kappa_fit, w06, sv0, sv1, chan, n_alpha_f, n_t_f, pitch4_f, a0, a1, acc);
-        });
-        if (!(kappa_fit < kappa_max)) return;  // wave-uniform: the polynomials covered the whole range (the normal case)
-        asm volatile("" : "+s"(rec));  // what follows is read from the record afterwards (as in pair_accumulate)
-    }
-    float K0[8], K1[8];
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        K0[i] = uniformf(rec->K0[i]);
-        K1[i] = uniformf(rec->K1[i]);
-    }
-    const float dist_scale = n_t_f / p.range_t, dist_bias = fmaf(0.5f, n_t_f, 0.5f);
-    exact_loop_dispatch(p, reduce, pitch4, sv0, sv1, iD0, iD1, [&](auto REDUCE, auto P4, const SlabView v0, const SlabView v1) {
-        const long long chan_here = decltype(P4)::value == ECC_QUAD_LAYOUT ? g.quad_channel_bytes : chan;
-        coeff_loop_exact<DERIV, NC, decltype(REDUCE)::value, decltype(P4)::value>(k_first, p.k_limit, K0, K1, v0, v1, chan_here, n_alpha_f, n_t_f,
-                                                                                dist_scale, dist_bias, pitch4_f, a0, a1, acc);
-    });
-}
+};
 
 // One wave per pair, on pairs_kernel's workgroup -> pairs mapping (main_pair_of_wave, ecc_pairs_device.h).
 // Registers: the 4 NC gathers of a kappa step as in pairs_gram_kernel, all 4 NC samples kept for the gradient
@@ -223,7 +139,7 @@ __global__ __launch_bounds__(PK_MAIN_THREADS) void pairs_coeff_kernel(EccPairPar
     double acc[T];
 #pragma unroll
     for (int t = 0; t < T; ++t) acc[t] = 0.0;
-    coeff_accumulate<DERIV, NC>(p, g, rec, iD0, iD1, lane, a0, a1, acc);
+    form_accumulate_local<DERIV, true, CoeffForm<NC>>(p, rec, iD0, iD1, lane, g, a0, a1, acc);
 #pragma unroll
     for (int t = 0; t < T; ++t) ecc_sum::wave_sum(acc[t]);
     if (lane == 0) {
@@ -233,7 +149,7 @@ __global__ __launch_bounds__(PK_MAIN_THREADS) void pairs_coeff_kernel(EccPairPar
 }
 
 // ---- ECC_SAMPLING_REFERENCE -------------------------------------------------------------------------
-// gram_reference_loop (gram_kernel.hip) with the coefficient products: reference_loop's expressions on the signed samples.
+// reference_loop<false> (ecc_pairs_device.h) for NC channels and their coefficients: its expressions on the signed samples.
 template <int NC>
 __device__ __forceinline__ void coeff_reference_loop(const EccPairParams& p, const float (&K0)[8], const float (&K1)[8],
                                                      const GlobalFloats (&d0)[NC], const GlobalFloats (&d1)[NC], const float (&a0)[NC],
@@ -271,7 +187,7 @@ __device__ __forceinline__ void coeff_reference_loop(const EccPairParams& p, con
     }
 }
 
-// pairs_gram_reference_kernel (gram_kernel.hip) with the coefficient products: SPLIT = 1 one wave per pair, SPLIT = 4 the
+// pairs_reference_kernel<false, SPLIT> for NC channels and their coefficients: SPLIT = 1 one wave per pair, SPLIT = 4 the
 // workgroup's four waves on one pair with the wave sums added in wave order (the grouping the metric's mode fixes).
 template <int NC, int SPLIT>
 __global__ __launch_bounds__(PK_THREADS) void pairs_coeff_reference_kernel(EccPairParams p, EccViewCoeffParams g)
@@ -329,17 +245,8 @@ __global__ __launch_bounds__(PK_THREADS) void pairs_coeff_reference_kernel(EccPa
 template <int NC>
 hipError_t launch_coeff_nc(const EccPairParams& p, const EccViewCoeffParams& g, hipStream_t stream)
 {
-    if (p.reference_arithmetic) {
-        if (p.reference_split > 1)
-            hipLaunchKernelGGL((pairs_coeff_reference_kernel<NC, 4>), dim3((unsigned)p.count), dim3(PK_THREADS), 0, stream, p, g);
-        else
-            hipLaunchKernelGGL((pairs_coeff_reference_kernel<NC, 1>), dim3((unsigned)((p.count + 3) / 4)), dim3(PK_THREADS), 0, stream, p, g);
-        return hipGetLastError();
-    }
-    const dim3 grid = main_pairs_grid(p.count), block(PK_MAIN_THREADS);
-    if (p.is_derivative) hipLaunchKernelGGL((pairs_coeff_kernel<true, NC>), grid, block, 0, stream, p, g);
-    else hipLaunchKernelGGL((pairs_coeff_kernel<false, NC>), grid, block, 0, stream, p, g);
-    return hipGetLastError();
+    return launch_pair_form(p, g, stream, pairs_coeff_reference_kernel<NC, 4>, pairs_coeff_reference_kernel<NC, 1>, pairs_coeff_kernel<true, NC>,
+                            pairs_coeff_kernel<false, NC>);
 }
 
 }  // namespace

@@ -8,11 +8,12 @@
 // binary64 once, every product of two samples is exact in binary64 (24 + 24 bits), and an entry is acc = fma(x, y, acc) for the +
 // and then the - sample of a kappa step, per lane in float64 in pairs_coeff_kernel's trip order, reduced by the same wave tree,
 // multiplied by w = (double)K0[6] * (double)dkappa by lane 0 and stored as float64.
-// pairs_moments_kernel<DERIV, NC> is pairs_coeff_kernel (view_coeff_kernel.hip) with other products behind the same 4 NC gathers:
-// one wave per pair, the record in scalar registers, the same dispatch over the record's degree and the slab size, the same float32
-// sample values.  The polynomial loops see unsigned samples u with the fold signs s0, s1 of the two views: P00 and P11 need no sign
-// (s^2 = 1), and -v0 v1 = -s0 s1 u0 u1 = rel_sign u0 u1 with coeff_loop_poly's rel_sign, applied to the lane's sums of u0 u1 when the
-// loop ends -- an exact negation, which commutes with every rounding after it.  The exact and the reference loop see signed samples
+// pairs_moments_kernel<DERIV, NC> runs on form_loop_poly and form_loop_exact of ecc_pair_forms.h; its choice of loop
+// (moment_accumulate: no pair weight inside the loops), the kernel body and the reference kernels stay here.  MomentForm's trip gathers
+// NC footprints at each of the four taps (the float32 sample values of pairs_coeff_kernel), converts them to binary64 and adds the T2
+// exact products.  The polynomial loops see unsigned samples u with the fold signs s0, s1 of the two views: P00 and P11 need no sign
+// (s^2 = 1), and -v0 v1 = -s0 s1 u0 u1 = rel_sign u0 u1 with the frame's rel_sign, applied to the lane's sums of u0 u1 when the
+// loop ends (poly_end) -- an exact negation, which commutes with every rounding after it.  The exact and the reference loop see signed samples
 // and accumulate fma(-v0, v1, acc).  T2 = NC (NC + 1) + NC^2 columns: P00's upper triangle in the Gram form's entry order, P11's
 // upper triangle, P01 row-major.
 // assemble_view_hessian_kernel writes H (index k = c * n + i) from the columns: off-diagonal blocks and their transposed twins as
@@ -21,7 +22,7 @@
 #include <float.h>
 
 #include "ecc_layout.h"
-#include "ecc_pairs_device.h"
+#include "ecc_pair_forms.h"
 #include "ecc_sum_order.h"
 
 namespace {
@@ -51,44 +52,18 @@ __device__ __forceinline__ void moment_add(double (&acc)[moment_entries(NC)], co
             acc[t] = SIGNED ? fma(-x0m[c], x1m[d], fma(-x0p[c], x1p[d], acc[t])) : fma(x0m[c], x1m[d], fma(x0p[c], x1p[d], acc[t]));
 }
 
-// coeff_loop_poly (view_coeff_kernel.hip) with the moment products: returns the lane's first sample index past the fit's range.
-// chan: bytes from a view's copy to the same view's copy of the next channel (wave-uniform).
-template <bool DERIV, int NC, int PITCH4, int DEG, bool NOCLAMP>
-__device__ __forceinline__ int moment_loop_poly(int lane, int k_limit, const EccPairRecord* __restrict__ rec, float dkappa,
-                                                float kappa_fit, const SlabView sv0, const SlabView sv1, long long chan, float n_alpha_f,
-                                                float n_t_f, float pitch4_f, double (&acc)[moment_entries(NC)])
-{
-    float ca[2][ECC_POLY_DEG + 3], cd[2][ECC_POLY_DEG + 2];
-    unsigned fold[2];
-#pragma unroll
-    for (int v = 0; v < 2; ++v) {
-        fold[v] = (unsigned)__builtin_amdgcn_readfirstlane((int)rec->fold[v]);
-#pragma unroll
-        for (int k = 0; k <= ECC_POLY_DEG + 1; ++k) {
-            if (k > DEG && k <= ECC_POLY_DEG) continue;
-            ca[v][k] = uniformf(rec->ca[v][k]);
-            cd[v][k] = uniformf(rec->cd[v][k]);
-        }
-        ca[v][ECC_POLY_DEG + 2] = uniformf(rec->ca[v][ECC_POLY_DEG + 2]);
-    }
-    const float xs = uniformf(rec->x_scale);
-    const float xa_max = n_alpha_f + 0.5f;
-    const bool opposite = DERIV && ((fold[0] ^ fold[1]) & 0x80000000u);  // rel_sign = +1 (see coeff_loop_poly): -v0 v1 = u0 u1
-    float kf = (float)lane;
-    int k = lane;
-    for (; k < k_limit; k += 64, kf += 64.f) {
-        const float kappa = dkappa * 0.5f + dkappa * kf;  // ref: ...RadonIntermediate.cu:259 (same fp32 ops)
-        if (kappa >= kappa_fit) break;
-        const float x = kappa * xs, z = x * x;
-        float xa0p, xa0m, yd0p, yd0m, xa1p, xa1m, yd1p, yd1m;
-        poly_pm<DEG>(ca[0], ca[0][ECC_POLY_DEG + 1], ca[0][ECC_POLY_DEG + 2], false, x, z, xa0p, xa0m);
-        poly_pm<DEG>(cd[0], cd[0][ECC_POLY_DEG + 1], 0.f, true, x, z, yd0p, yd0m);
-        poly_pm<DEG>(ca[1], ca[1][ECC_POLY_DEG + 1], ca[1][ECC_POLY_DEG + 2], false, x, z, xa1p, xa1m);
-        poly_pm<DEG>(cd[1], cd[1][ECC_POLY_DEG + 1], 0.f, true, x, z, yd1p, yd1m);
-        const SampleTap t0p = sample_tap<PITCH4, NOCLAMP>(xa0p, yd0p, sv0, n_t_f, pitch4_f, xa_max);
-        const SampleTap t1p = sample_tap<PITCH4, NOCLAMP>(xa1p, yd1p, sv1, n_t_f, pitch4_f, xa_max);
-        const SampleTap t0m = sample_tap<PITCH4, NOCLAMP>(xa0m, yd0m, sv0, n_t_f, pitch4_f, xa_max);
-        const SampleTap t1m = sample_tap<PITCH4, NOCLAMP>(xa1m, yd1m, sv1, n_t_f, pitch4_f, xa_max);
+// the trips of the polynomial and the exact loops (form_loop_poly, form_loop_exact, ecc_pair_forms.h): NC gathers at each of the four
+// taps, every sample converted to binary64 once, the T2 exact products
+template <int NC>
+struct MomentForm : ChannelForm<EccViewMomentParams> {
+    double (&acc)[moment_entries(NC)];
+
+    __device__ __forceinline__ MomentForm(const EccViewMomentParams& g, double (&acc)[moment_entries(NC)]) : ChannelForm(g), acc(acc) {}
+
+    // unsigned samples: P01 accumulates u0 u1, signed when the loop ends
+    __device__ __forceinline__ void poly_trip(const SlabView sv0, const SlabView sv1, const SampleTap t0p, const SampleTap t1p,
+                                              const SampleTap t0m, const SampleTap t1m, float, float)
+    {
         double x0p[NC], x1p[NC], x0m[NC], x1m[NC];
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
@@ -100,55 +75,37 @@ __device__ __forceinline__ int moment_loop_poly(int lane, int k_limit, const Ecc
         }
         moment_add<NC, false>(acc, x0p, x0m, x1p, x1m);
     }
-    if (!opposite) {  // wave-uniform: rel_sign = -1
-#pragma unroll
-        for (int t = 2 * tri_entries(NC); t < moment_entries(NC); ++t) acc[t] = -acc[t];
-    }
-    return k;
-}
 
-// coeff_loop_exact (view_coeff_kernel.hip) with the moment products on the signed samples.
-template <bool DERIV, int NC, bool REDUCE, int PITCH4>
-__device__ __forceinline__ void moment_loop_exact(int k_first, int k_limit, const float (&K0)[8], const float (&K1)[8], const SlabView sv0,
-                                                  const SlabView sv1, long long chan, float n_alpha_f, float n_t_f, float dist_scale,
-                                                  float dist_bias, float pitch4_f, double (&acc)[moment_entries(NC)])
-{
-    const float dkappa = K1[6], kappa_max = K1[7];
-    for (int k = k_first; k < k_limit; k += 64) {
-        const float kappa = dkappa * 0.5f + dkappa * k;  // ref: ...RadonIntermediate.cu:259 (same fp32 ops)
-        if (kappa >= kappa_max) return;
-        float sn, cs;
-        sincos_quadrant<REDUCE>(kappa, sn, cs);
-        const float a00 = K0[0] * cs, a01 = K0[1] * cs, a02 = K0[2] * cs;
-        const float b00 = K0[3] * sn, b01 = K0[4] * sn, b02 = K0[5] * sn;
-        const float a10 = K1[0] * cs, a11 = K1[1] * cs, a12 = K1[2] * cs;
-        const float b10 = K1[3] * sn, b11 = K1[4] * sn, b12 = K1[5] * sn;
-        const LineTap t0p = sample_line_prep<PITCH4>(b00 + a00, b01 + a01, b02 + a02, sv0, n_alpha_f, n_t_f, dist_scale, dist_bias, pitch4_f);
-        const LineTap t1p = sample_line_prep<PITCH4>(b10 + a10, b11 + a11, b12 + a12, sv1, n_alpha_f, n_t_f, dist_scale, dist_bias, pitch4_f);
-        const LineTap t0m = sample_line_prep<PITCH4>(b00 - a00, b01 - a01, b02 - a02, sv0, n_alpha_f, n_t_f, dist_scale, dist_bias, pitch4_f);
-        const LineTap t1m = sample_line_prep<PITCH4>(b10 - a10, b11 - a11, b12 - a12, sv1, n_alpha_f, n_t_f, dist_scale, dist_bias, pitch4_f);
-        // the taps' byte offsets inside a copy (the prepared pointer minus the origin it was formed from: folded away)
-        const unsigned o0p = (unsigned)((GlobalBytes)t0p.ptr - sv0.origin), o1p = (unsigned)((GlobalBytes)t1p.ptr - sv1.origin);
-        const unsigned o0m = (unsigned)((GlobalBytes)t0m.ptr - sv0.origin), o1m = (unsigned)((GlobalBytes)t1m.ptr - sv1.origin);
+    // -v0 v1 = -s0 s1 u0 u1 = rel_sign u0 u1: rel_sign = -1 negates the lane's P01 sums (exact; wave-uniform)
+    __device__ __forceinline__ void poly_end(float rel_sign)
+    {
+        if (rel_sign < 0.f) {
+#pragma unroll
+            for (int t = 2 * tri_entries(NC); t < moment_entries(NC); ++t) acc[t] = -acc[t];
+        }
+    }
+
+    template <bool DERIV, int PITCH4>
+    __device__ __forceinline__ void exact_trip(const SlabView sv0, const SlabView sv1, const LineTap t0p, const LineTap t1p, const LineTap t0m,
+                                               const LineTap t1m, float, float)
+    {
+        const unsigned o0p = line_tap_offset(t0p, sv0), o1p = line_tap_offset(t1p, sv1);
+        const unsigned o0m = line_tap_offset(t0m, sv0), o1m = line_tap_offset(t1m, sv1);
         double x0p[NC], x1p[NC], x0m[NC], x1m[NC];
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
             const GlobalBytes o0 = sv0.origin + chan * c, o1 = sv1.origin + chan * c;
-            const auto tap = [](GlobalBytes origin, unsigned off, const LineTap t) {
-                const ecc_v4f_a4 q4 = *(GlobalF4)(origin + off);
-                const F4 q = {q4.x, q4.y, q4.z, q4.w};
-                return (double)line_tap_finish<DERIV>(q, t);
-            };
-            x0p[c] = tap(o0, o0p, t0p);
-            x1p[c] = tap(o1, o1p, t1p);
-            x0m[c] = tap(o0, o0m, t0m);
-            x1m[c] = tap(o1, o1m, t1m);
+            x0p[c] = (double)line_tap_finish<DERIV>(line_footprint(o0, o0p), t0p);
+            x1p[c] = (double)line_tap_finish<DERIV>(line_footprint(o1, o1p), t1p);
+            x0m[c] = (double)line_tap_finish<DERIV>(line_footprint(o0, o0m), t0m);
+            x1m[c] = (double)line_tap_finish<DERIV>(line_footprint(o1, o1m), t1m);
         }
         moment_add<NC, true>(acc, x0p, x0m, x1p, x1m);
     }
-}
+};
 
-// coeff_accumulate (view_coeff_kernel.hip): the same choice of loop for the same record, made by the same helpers.
+// form_accumulate (ecc_pair_forms.h) without the pair weight: the same choice of loop for the same record, made by the same helpers.
+// (Kept here: on form_accumulate the four plain-data kernels change their instruction streams, see CHANGELOG.)
 template <bool DERIV, int NC>
 __device__ __forceinline__ void moment_accumulate(const EccPairParams& p, const EccViewMomentParams& g, const EccPairRecord* __restrict__ rec,
                                                   int iD0, int iD1, int lane, double (&acc)[moment_entries(NC)])
@@ -156,7 +113,7 @@ __device__ __forceinline__ void moment_accumulate(const EccPairParams& p, const 
     const unsigned pitch4 = (unsigned)p.pitch * 8u;
     const SlabView sv0 = {(GlobalBytes)p.dtrs[iD0], pitch4};
     const SlabView sv1 = {(GlobalBytes)p.dtrs[iD1], pitch4};
-    const long long chan = g.paired_channel_bytes;
+    MomentForm<NC> form(g, acc);
     const float n_alpha_f = (float)p.n_alpha, n_t_f = (float)p.n_t;
     const float pitch4_f = (float)pitch4;
     const float kappa_max = uniformf(rec->K1[7]);
@@ -167,10 +124,10 @@ __device__ __forceinline__ void moment_accumulate(const EccPairParams& p, const 
     const bool in_range = (poly_raw & 1) != 0;
     int k_first = lane;
     if (poly_ok) {
-        const float kappa_fit = ecc_kappa_fit(kappa_max), dkappa = uniformf(rec->K1[6]);
+        const float kappa_fit = ecc_kappa_fit(kappa_max), dkappa = uniformf(rec->K1[6]);  // (no weight in the loops: lane 0 applies it)
         poly_loop_dispatch(p.wide_offsets != 0, pitch4, poly_ok, in_range, [&](auto P4, auto DEG, auto NOCL) {
-            k_first = moment_loop_poly<DERIV, NC, decltype(P4)::value, decltype(DEG)::value, decltype(NOCL)::value>(
-                lane, p.k_limit, rec, dkappa, kappa_fit, sv0, sv1, chan, n_alpha_f, n_t_f, pitch4_f, acc);
+            k_first = form_loop_poly<DERIV, decltype(P4)::value, decltype(DEG)::value, decltype(NOCL)::value>(
+                form, lane, p.k_limit, rec, dkappa, kappa_fit, 0.f, sv0, sv1, n_alpha_f, n_t_f, pitch4_f);
         });
         if (!(kappa_fit < kappa_max)) return;  // wave-uniform: the polynomials covered the whole range (the normal case)
         asm volatile("" : "+s"(rec));  // what follows is read from the record afterwards (as in pair_accumulate)
@@ -183,9 +140,8 @@ __device__ __forceinline__ void moment_accumulate(const EccPairParams& p, const 
     }
     const float dist_scale = n_t_f / p.range_t, dist_bias = fmaf(0.5f, n_t_f, 0.5f);
     exact_loop_dispatch(p, reduce, pitch4, sv0, sv1, iD0, iD1, [&](auto REDUCE, auto P4, const SlabView v0, const SlabView v1) {
-        const long long chan_here = decltype(P4)::value == ECC_QUAD_LAYOUT ? g.quad_channel_bytes : chan;
-        moment_loop_exact<DERIV, NC, decltype(REDUCE)::value, decltype(P4)::value>(k_first, p.k_limit, K0, K1, v0, v1, chan_here, n_alpha_f,
-                                                                                 n_t_f, dist_scale, dist_bias, pitch4_f, acc);
+        form_loop_exact<DERIV, decltype(REDUCE)::value, decltype(P4)::value>(form, k_first, p.k_limit, K0, K1, v0, v1, n_alpha_f, n_t_f,
+                                                                           dist_scale, dist_bias, pitch4_f);
     });
 }
 
@@ -222,7 +178,7 @@ __global__ __launch_bounds__(PK_MAIN_THREADS) void pairs_moments_kernel(EccPairP
 }
 
 // ---- ECC_SAMPLING_REFERENCE -------------------------------------------------------------------------
-// coeff_reference_loop (view_coeff_kernel.hip) with the moment products on the signed samples.
+// reference_loop<false> (ecc_pairs_device.h) for NC channels: the moment products on the signed samples.
 template <int NC>
 __device__ __forceinline__ void moment_reference_loop(const EccPairParams& p, const float (&K0)[8], const float (&K1)[8],
                                                       const GlobalFloats (&d0)[NC], const GlobalFloats (&d1)[NC], int first_k, int stride,
@@ -252,7 +208,7 @@ __device__ __forceinline__ void moment_reference_loop(const EccPairParams& p, co
     }
 }
 
-// pairs_coeff_reference_kernel (view_coeff_kernel.hip) with the moment products: SPLIT = 1 one wave per pair, SPLIT = 4 the
+// pairs_reference_kernel<false, SPLIT> for NC channels with the moment products: SPLIT = 1 one wave per pair, SPLIT = 4 the
 // workgroup's four waves on one pair with the wave sums added in wave order (the grouping the metric's mode fixes).
 template <int NC, int SPLIT>
 __global__ __launch_bounds__(PK_THREADS) void pairs_moments_reference_kernel(EccPairParams p, EccViewMomentParams g)
@@ -309,17 +265,8 @@ __global__ __launch_bounds__(PK_THREADS) void pairs_moments_reference_kernel(Ecc
 template <int NC>
 hipError_t launch_moments_nc(const EccPairParams& p, const EccViewMomentParams& g, hipStream_t stream)
 {
-    if (p.reference_arithmetic) {
-        if (p.reference_split > 1)
-            hipLaunchKernelGGL((pairs_moments_reference_kernel<NC, 4>), dim3((unsigned)p.count), dim3(PK_THREADS), 0, stream, p, g);
-        else
-            hipLaunchKernelGGL((pairs_moments_reference_kernel<NC, 1>), dim3((unsigned)((p.count + 3) / 4)), dim3(PK_THREADS), 0, stream, p, g);
-        return hipGetLastError();
-    }
-    const dim3 grid = main_pairs_grid(p.count), block(PK_MAIN_THREADS);
-    if (p.is_derivative) hipLaunchKernelGGL((pairs_moments_kernel<true, NC>), grid, block, 0, stream, p, g);
-    else hipLaunchKernelGGL((pairs_moments_kernel<false, NC>), grid, block, 0, stream, p, g);
-    return hipGetLastError();
+    return launch_pair_form(p, g, stream, pairs_moments_reference_kernel<NC, 4>, pairs_moments_reference_kernel<NC, 1>,
+                            pairs_moments_kernel<true, NC>, pairs_moments_kernel<false, NC>);
 }
 
 // H from the columns.  Workgroup (view v, entry e) of n_views x (K (K + 1) / 2 + K^2):
