@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <limits>
 #include <memory>
 #include <new>
@@ -454,17 +455,42 @@ int stage_pose_grid(ecc_metric* m, const double* base, int K, const int32_t* off
                     int result_words, volatile uint64_t** out, double** out_dev);
 hipError_t launch_pose_list(ecc_metric* m, int K, int Q, int result_words);
 void arm_pose_results(volatile uint64_t* out, int K);
-int wait_pose_results(ecc_ctx* ctx, volatile uint64_t* out, int K, double* sums);
+int wait_pose_results(ecc_ctx* ctx, volatile uint64_t* out, int K, double* sums, const char* batch_noun = "pose");
+// ecc_poses.hip: the poses `rest` of a pose-delta call the sequential way -- the pose's full matrices, evaluate_pose(k), the
+// matrices back -- then the base again
+int pose_deltas_sequential(ecc_metric* m, const std::vector<int>& rest, const int32_t* off, const int32_t* views, const double* moved_Ps,
+                           const std::function<int(int)>& evaluate_pose);
 // ecc_transforms.hip, for the batches of ecc_weighted_transforms.hip as well: the object radius the sequential calls would take for a
-// transform; the host half of a batch's grid (pinned block, device arrays) and the launch of transform_list_kernel over it
+// transform; the host half of a batch's grid (pinned block, device arrays) and the launch of transform_list_kernel over it; the
+// two drivers of a call -- the transforms one at a time over the cross list, then the base again; whole transforms in batches of at
+// most max_per_batch within ECC_POSE_BATCH_MAX_ENTRIES grid entries, run_batch(first transform, how many) each
 float radius_of_transform(const ecc_metric* m, const double* base, const double* T);
 int stage_transform_grid(ecc_metric* m, const double* base, int n_source, int K, const double* Ts, int result_words,
                          volatile uint64_t** out, double** out_dev);
 hipError_t launch_transform_list(ecc_metric* m, int n_source, int K, long long seg, int result_words);
+int transforms_sequential(ecc_metric* m, const std::vector<double>& base, int n_source, int n_transforms, const double* Ts,
+                          const std::function<int(int, const int32_t*, int)>& evaluate_list);
+int transforms_batched(ecc_metric* m, int64_t count, int n_transforms, int64_t max_per_batch, const std::function<int(int64_t, int)>& run_batch);
+// ecc_gram.hip: what the channel forms (Gram, view coefficients, view Hessian) need of n_channels and of the metric, with the call's
+// own texts for the range of n_channels and for the correlation cost
+int channel_form_check(const ecc_metric* m, int n_channels, const char* range_text, const char* corr_text);
 // ecc_weighted.hip: the argument checks of the weighted calls; {c, u} of all pairs at the current matrices into gram_values_d
-// (p, g: the launch as it was made)
+// (c, g: the launches as they were made); value and coverage from the two totals
+struct ColumnCall;  // (ecc_column_call.h)
 int weighted_check(const ecc_metric* m);
-int weighted_base_columns(ecc_metric* m, EccPairParams* p, EccWeightedParams* g);
+int weighted_base_columns(ecc_metric* m, ColumnCall* c, EccWeightedParams* g);
+void finish_weighted(double sum_c, double sum_u, int64_t count, double* value, double* coverage);
+
+// The distance of two channels' row-paired and row-quad copies, for the pair forms that read more than one copy per view (g: any
+// of their parameter structs).
+template <class Params>
+inline void set_channel_strides(const ecc_metric* m, Params* g)
+{
+    const int64_t n = m->n_views;
+    const int64_t paired_bytes = (int64_t)(m->n_alpha + 1) * m->pitch * 2 * (int64_t)sizeof(float);
+    g->paired_channel_bytes = n * paired_bytes;
+    g->quad_channel_bytes = n * m->quad_floats * (int64_t)sizeof(float);
+}
 
 // launch(stream) on the context's stream between its timing events (ecc_ctx_enable_timing).
 template <class Launch>

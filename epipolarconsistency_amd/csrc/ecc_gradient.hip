@@ -64,12 +64,7 @@ int gradient_one_launch(ecc_metric* m, int view, int Q, const double* moved_Ps, 
     p.PinvTs = m->PinvTs_d.ptr;
     p.Cs = m->Cs_d.ptr;
     p.pair_values = m->pose_values_d.ptr;
-    if (ctx->timing) HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
-    HIP_TRY(ecc_launch_small_poses(&p, &x, &y, ctx->stream));
-    if (ctx->timing) {
-        HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
-        ctx->ev_valid[0] = true;
-    }
+    HIP_TRY(launch_timed(ctx, [&](hipStream_t s) { return ecc_launch_small_poses(&p, &x, &y, s); }));
     std::vector<double> sums((size_t)K);
     rc = sum_poses(m, base_vals_d, K, Q, reinterpret_cast<volatile uint64_t*>(m->pose_h.host), reinterpret_cast<double*>(m->pose_h.dev),
                    sums.data());

@@ -20,15 +20,13 @@
 // A pair value depends on its two matrices, its two Radon intermediates and the parameters only, the sampling mode is the one
 // an evaluation of n (n - 1) / 2 pairs resolves to, and the sum's order is reproduced: every mean has the bits of
 // ecc_metric_set_projections + ecc_metric_evaluate_all for that pose (tests/test_gpu_pose_batch.py).
+// Which poses go into which batch: ecc_pose_batches.h; what the batch does not take: pose_deltas_sequential below.
 #include "ecc_capi_internal.h"
+#include "ecc_pose_batches.h"
 #include "ecc_pose_diff.h"
 #include "ecc_sum_order.h"
 
 using namespace ecc_internal;
-
-#ifndef ECC_POSE_BATCH_MAX_MOVED
-#define ECC_POSE_BATCH_MAX_MOVED 32  // moved views per pose the batch takes; a pose with more is evaluated the sequential way
-#endif
 
 namespace {
 
@@ -209,7 +207,8 @@ void arm_pose_results(volatile uint64_t* out, int K)
 }
 
 // The K result words a launch on the stream stores into pinned memory (armed by arm_pose_results before the launch) -> sums.
-int wait_pose_results(ecc_ctx* ctx, volatile uint64_t* out, int K, double* sums)
+// batch_noun: what kind of batch it was, for the error text.
+int wait_pose_results(ecc_ctx* ctx, volatile uint64_t* out, int K, double* sums, const char* batch_noun)
 {
     // the results arrive in pinned memory a few microseconds before the stream is reported idle: poll the last one, then the rest
     double t0 = 0.0;
@@ -223,7 +222,7 @@ int wait_pose_results(ecc_ctx* ctx, volatile uint64_t* out, int K, double* sums)
             else if (t - t0 > 2.0) {
                 HIP_TRY(hipStreamSynchronize(ctx->stream));
                 for (k = 0; k < K; ++k)
-                    if (out[k] == POSE_PENDING) return fail(ECC_ERR_HIP, "the pose batch ran and stored no result");
+                    if (out[k] == POSE_PENDING) return fail(ECC_ERR_HIP, std::string("the ") + batch_noun + " batch ran and stored no result");
                 break;
             }
         }
@@ -435,42 +434,20 @@ int evaluate_deltas(ecc_metric* m, int n_poses, const int32_t* off, const int32_
     float* base_vals_d = nullptr;
     int rc = evaluate_cached(m, 0, n_pairs, /*sum_d=*/nullptr, &base_vals_d);  // (the values only: the segmented sum adds them per pose)
     if (rc) return rc;
-    std::vector<int32_t> b_off, b_views;
-    std::vector<double> b_Ps, sums;
-    std::vector<int> b_pose;
+    std::vector<double> sums;
     const int64_t max_cols = std::max<int64_t>(ECC_POSE_BATCH_MAX_ENTRIES / n, ECC_POSE_BATCH_MAX_MOVED);
-    auto flush = [&]() -> int {
-        if (b_pose.empty()) return ECC_OK;
-        sums.resize(b_pose.size());
-        const int e = run_batch(m, base.data(), base_vals_d, (int)b_pose.size(), b_off.data(), b_views.data(), b_Ps.data(), sums.data());
-        if (e) return e;
-        for (size_t q = 0; q < b_pose.size(); ++q) means[b_pose[q]] = sums[q] / (double)n_pairs;  // ref: ...RadonIntermediate.cpp:224
-        m->last_batched_poses += (int64_t)b_pose.size();
-        b_pose.clear();
-        b_off.assign(1, 0);
-        b_views.clear();
-        b_Ps.clear();
-        return ECC_OK;
-    };
-    b_off.assign(1, 0);
-    for (int k = 0; k < n_poses; ++k) {
-        const int c = off[k + 1] - off[k];
-        const int32_t* vk = views + off[k];
-        const double* Pk = moved_Ps + 12 * (size_t)off[k];
-        if (c > ECC_POSE_BATCH_MAX_MOVED || !pose_keeps_radius(m, base_radius, c, vk, Pk)) {
-            not_batched->push_back(k);
-            continue;
-        }
-        if ((int64_t)b_views.size() + c > max_cols || b_pose.size() >= POSE_BATCH_MAX_POSES) {
-            rc = flush();
-            if (rc) return rc;
-        }
-        b_pose.push_back(k);
-        b_views.insert(b_views.end(), vk, vk + c);
-        b_Ps.insert(b_Ps.end(), Pk, Pk + 12 * (size_t)c);
-        b_off.push_back((int32_t)b_views.size());
-    }
-    rc = flush();
+    rc = ecc_pose_batches::pack(
+        n_poses, off, views, moved_Ps, max_cols, POSE_BATCH_MAX_POSES,
+        [&](int c, const int32_t* vk, const double* Pk) { return pose_keeps_radius(m, base_radius, c, vk, Pk); },
+        [&](const ecc_pose_batches::Batch& b) -> int {
+            sums.resize(b.pose.size());
+            const int e = run_batch(m, base.data(), base_vals_d, (int)b.pose.size(), b.off.data(), b.views.data(), b.Ps.data(), sums.data());
+            if (e) return e;
+            for (size_t q = 0; q < b.pose.size(); ++q) means[b.pose[q]] = sums[q] / (double)n_pairs;  // ref: ...RadonIntermediate.cpp:224
+            m->last_batched_poses += (int64_t)b.pose.size();
+            return ECC_OK;
+        },
+        not_batched);
     if (rc) return rc;
     HIP_TRY(wait_stream_spin(ctx->stream));  // (the results were seen before the stream's own completion; the scratch is reused)
     m->quiet = true;
@@ -491,6 +468,29 @@ int check_lists(const ecc_metric* m, int n_poses, const int32_t* off, const int3
         }
     }
     return ECC_OK;
+}
+
+// What the batch does not take (more moved views than it handles, a changed automatic radius, batching off): the pose's full
+// matrices the sequential way, then the base again.
+int pose_deltas_sequential(ecc_metric* m, const std::vector<int>& rest, const int32_t* off, const int32_t* views, const double* moved_Ps,
+                           const std::function<int(int)>& evaluate_pose)
+{
+    if (rest.empty()) return ECC_OK;
+    const int64_t n = m->n_views;
+    const double* Pcur = m->Ps_h[m->set_generation & 1].host;
+    const std::vector<double> base(Pcur, Pcur + 12 * n);
+    std::vector<double> full(base);
+    int rc = ECC_OK;
+    for (int k : rest) {
+        for (int q = off[k]; q < off[k + 1]; ++q) std::memcpy(full.data() + 12 * (size_t)views[q], moved_Ps + 12 * (size_t)q, sizeof(double) * 12);
+        rc = ecc_metric_set_projections(m, full.data(), (int)n);
+        if (!rc) rc = evaluate_pose(k);
+        if (rc) break;
+        for (int q = off[k]; q < off[k + 1]; ++q)
+            std::memcpy(full.data() + 12 * (size_t)views[q], base.data() + 12 * (size_t)views[q], sizeof(double) * 12);
+    }
+    const int rb = ecc_metric_set_projections(m, base.data(), (int)n);
+    return rc ? rc : rb;
 }
 }  // namespace ecc_internal
 
@@ -521,7 +521,6 @@ ECC_EXPORT int ecc_metric_evaluate_pose_deltas(ecc_metric* m, int n_poses, const
     rc = check_lists(m, n_poses, moved_offsets, moved_views);
     if (rc) return rc;
     m->last_batched_poses = 0;
-    const int64_t n = m->n_views;
     std::vector<int> rest;
     if (m->pose_batching) {
         rc = evaluate_deltas(m, n_poses, moved_offsets, moved_views, moved_Ps, means, &rest);
@@ -529,23 +528,8 @@ ECC_EXPORT int ecc_metric_evaluate_pose_deltas(ecc_metric* m, int n_poses, const
     } else {
         for (int k = 0; k < n_poses; ++k) rest.push_back(k);
     }
-    if (rest.empty()) return ECC_OK;
-    // what the batch does not take (more moved views than it handles, a changed automatic radius, batching off): the pose's
-    // full matrices the sequential way, then the base again
-    const double* Pcur = m->Ps_h[m->set_generation & 1].host;
-    const std::vector<double> base(Pcur, Pcur + 12 * n);
-    std::vector<double> full(base);
-    for (int k : rest) {
-        for (int q = moved_offsets[k]; q < moved_offsets[k + 1]; ++q)
-            std::memcpy(full.data() + 12 * (size_t)moved_views[q], moved_Ps + 12 * (size_t)q, sizeof(double) * 12);
-        rc = ecc_metric_set_projections(m, full.data(), (int)n);
-        if (!rc) rc = ecc_metric_evaluate_all(m, nullptr, &means[k]);
-        if (rc) break;
-        for (int q = moved_offsets[k]; q < moved_offsets[k + 1]; ++q)
-            std::memcpy(full.data() + 12 * (size_t)moved_views[q], base.data() + 12 * (size_t)moved_views[q], sizeof(double) * 12);
-    }
-    const int rb = ecc_metric_set_projections(m, base.data(), (int)n);
-    return rc ? rc : rb;
+    return pose_deltas_sequential(m, rest, moved_offsets, moved_views, moved_Ps,
+                                  [&](int k) { return ecc_metric_evaluate_all(m, nullptr, &means[k]); });
 }
 
 // ref for the pattern: Gui/Visualization.h:78-98 plotCostFunction, BASELINE config 5; a finite-difference gradient.

@@ -6,13 +6,12 @@
 // kernel with its per-sample factor computed from the residual instead of gathered.
 //
 // The launches: E1 (if the device geometry is behind the matrices), k01_kernel over all pairs or the list into the Gram call's
-// records (scratch of the Gram-family calls alone), pairs_robust_kernel, sum_gram_kernel over the columns c and u, the copies.  The
-// metric's kept records, kept values and pose-batch values are not touched (the list form stages its tuples in the pose batch's
-// index scratch, as ecc_metric_evaluate_weighted_pairs does).
+// records (scratch of the Gram-family calls alone; column_call_begin, ecc_column_call.h), pairs_robust_kernel, sum_gram_kernel over
+// the columns c and u, the copies (column_call_finish).  The metric's kept records, kept values and pose-batch values are not
+// touched (the list form stages its tuples in the pose batch's index scratch, as ecc_metric_evaluate_weighted_pairs does).
 // Not here: pose-delta, transform, range, group and RCCL forms; the loss combined with line weights on a 2 n metric; the loss under
 // use_corr; Tukey's biweight (not d^2 near zero: no bit link to ecc_metric_evaluate_all).
-#include "ecc_capi_internal.h"
-#include "ecc_sum_order.h"
+#include "ecc_column_call.h"
 
 using namespace ecc_internal;
 
@@ -20,8 +19,6 @@ static_assert(ECC_LOSS_HUBER == ECC_ROBUST_HUBER && ECC_LOSS_TRUNCATED == ECC_RO
                   ECC_LOSS_GEMAN_MCCLURE == ECC_ROBUST_GEMAN_MCCLURE,
               "the kernels' loss codes are the header's");
 
-extern "C" hipError_t ecc_launch_sum_gram(const float* values_d, long long col_stride, long long count, int n_columns, int n_slices,
-                                          double* partial_d, hipStream_t stream);
 extern "C" hipError_t ecc_launch_pairs_robust(const EccPairParams* p, const EccRobustParams* g, hipStream_t stream);
 
 namespace {
@@ -43,61 +40,23 @@ int robust_check(const ecc_metric* m, const double* value, int loss, float delta
 // Everything behind the checks: `count` pairs -- all pairs (idx4 null) or the list -- under the sampling mode of that many values.
 int robust_run(ecc_metric* m, const int32_t* idx4, int64_t count, int loss, float delta, double* value, double* inlier_mass, float* pair_terms)
 {
-    ecc_ctx* ctx = m->ctx;
-    int rc = set_device(ctx);
+    ColumnCall c;
+    int rc = column_call_begin(m, idx4, count, T, 2, &c);
     if (rc) return rc;
-    const int64_t col_stride = (count + 3) & ~(int64_t)3;
-    // (as the first large all-pairs evaluation does: whether this scan's pairs would read row-quad copies; the same bits either way)
-    if (!idx4 && !m->quads_decided && count >= 32768) decide_quad_copies(m);
-    EccPairParams p;
-    rc = fill_pair_params(m, &p, count, /*need_e1=*/false);
-    if (rc) return rc;
-    rc = m->gram_records_d.ensure(count, ctx->stream);
-    if (!rc) rc = m->gram_values_d.ensure((int64_t)T * col_stride, ctx->stream);
-    if (!rc) rc = m->gram_partial_d.ensure((int64_t)2 * ecc_sum::SLICES, ctx->stream);
-    if (!rc && idx4) rc = m->pose_idx_d.ensure(4 * count, ctx->stream);
-    if (rc) return rc;
-    ecc_mark_busy(m);
-    rc = ensure_e1(m);  // (see ecc_metric_evaluate_gram)
-    if (rc) return rc;
-    if (idx4) {
-        HIP_TRY(hipMemcpyAsync(m->pose_idx_d.ptr, idx4, sizeof(int32_t) * 4 * (size_t)count, hipMemcpyHostToDevice, ctx->stream));
-        p.indices = m->pose_idx_d.ptr;
-    }
-    p.first = 0;
-    p.count = count;
-    p.records = m->gram_records_d.ptr;
-    HIP_TRY(ecc_launch_k01(&p, ctx->stream));
     EccRobustParams g;
     g.values = m->gram_values_d.ptr;
-    g.col_stride = col_stride;
+    g.col_stride = c.col_stride;
     g.loss = loss;
     g.delta = delta;
     g.inv_delta = (float)(1.0 / (double)delta);
-    HIP_TRY(launch_timed(ctx, [&](hipStream_t s) { return ecc_launch_pairs_robust(&p, &g, s); }));  // (robust_kernel.hip)
-    // c and u in the order an evaluation of `count` values is added in (ecc_sum_order.h); r is not summed
-    const int n_slices = ecc_sum::slices(count, m->sum_scratch_d.ptr != nullptr);
-    HIP_TRY(ecc_launch_sum_gram(m->gram_values_d.ptr, col_stride, count, 2, n_slices, m->gram_partial_d.ptr, ctx->stream));
-    std::vector<double> partial((size_t)2 * ecc_sum::SLICES);
-    HIP_TRY(hipMemcpyAsync(partial.data(), m->gram_partial_d.ptr, sizeof(double) * partial.size(), hipMemcpyDeviceToHost, ctx->stream));
-    std::vector<float> cols;
-    if (pair_terms) {
-        cols.resize((size_t)T * (size_t)col_stride);
-        HIP_TRY(hipMemcpyAsync(cols.data(), m->gram_values_d.ptr, sizeof(float) * cols.size(), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(wait_stream_spin(ctx->stream));
-    m->done_generation = m->set_generation;
-    m->quiet = true;  // the copies are the last thing this call queued, and they have landed
-    double sum_c = 0.0, sum_u = 0.0;
-    for (int s = 0; s < n_slices; ++s) sum_c += partial[(size_t)s];
-    for (int s = 0; s < n_slices; ++s) sum_u += partial[(size_t)ecc_sum::SLICES + s];
+    HIP_TRY(launch_timed(m->ctx, [&](hipStream_t s) { return ecc_launch_pairs_robust(&c.p, &g, s); }));  // (robust_kernel.hip)
+    double totals[2];  // c and u in the order an evaluation of `count` values is added in (ecc_sum_order.h); r is not summed
+    rc = column_call_finish(m, c, 2, totals, T, m->gram_values_d.ptr, pair_terms);
+    if (rc) return rc;
     // a mean over the pairs, ref: ...RadonIntermediate.cpp:224 with all weights 1 -- NOT divided by the inlier mass: that would reward
     // pushing samples into the tails
-    *value = sum_c / (double)count;
-    if (inlier_mass) *inlier_mass = sum_u / (double)count;
-    if (pair_terms)
-        for (int64_t q = 0; q < count; ++q)
-            for (int u = 0; u < T; ++u) pair_terms[(size_t)q * T + u] = cols[(size_t)u * col_stride + q];
+    *value = totals[0] / (double)count;
+    if (inlier_mass) *inlier_mass = totals[1] / (double)count;
     return ECC_OK;
 }
 

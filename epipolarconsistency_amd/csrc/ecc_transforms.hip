@@ -23,6 +23,8 @@
 // bits of ecc_metric_set_projections(composed matrices) + ecc_metric_evaluate_pairs(that list) (tests/test_gpu_transforms.py).
 // Nothing of the metric's own state is written: current matrices, device geometry, kept records and values stay; the scratch
 // is the pose batch's (pose_*), which every batch of either kind rewrites from scratch.
+// The two drivers of a call, transforms_batched and transforms_sequential below, are ecc_weighted_transforms.hip's as well
+// (DESIGN.md 4.21); the result slots are armed and awaited through ecc_poses.hip's arm_pose_results / wait_pose_results.
 #include "ecc_capi_internal.h"
 #include "ecc_sum_order.h"
 
@@ -126,9 +128,6 @@ __global__ __launch_bounds__(256) void finish_transforms_kernel(const double* __
                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-double clock_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-constexpr uint64_t TRANSFORM_PENDING = 0x7ff8ecc0dead0003ull;  // a NaN payload no sum has
-
 size_t align64(size_t x) { return (x + 63) & ~(size_t)63; }
 
 // the pinned block of a batch: base matrices | transforms | results | radii (byte offsets)
@@ -220,8 +219,7 @@ int run_batch(ecc_metric* m, const double* base, int n_source, int K, const doub
     double* out_dev = nullptr;
     int rc = stage_transform_grid(m, base, n_source, K, Ts, K, &out, &out_dev);
     if (rc) return rc;
-    for (int k = 0; k < K; ++k) out[k] = TRANSFORM_PENDING;
-    std::atomic_thread_fence(std::memory_order_seq_cst);
+    arm_pose_results(out, K);
     rc = m->pose_values_d.ensure(seg * K, ctx->stream);
     if (!rc) rc = m->pose_partial_d.ensure((int64_t)K * SUM_SLICES, ctx->stream);
     if (rc) return rc;
@@ -254,35 +252,18 @@ int run_batch(ecc_metric* m, const double* base, int n_source, int K, const doub
     if (values)  // (transform-major on the device, seg floats apart)
         HIP_TRY(hipMemcpy2DAsync(values, sizeof(float) * (size_t)count, m->pose_values_d.ptr, sizeof(float) * (size_t)seg,
                                  sizeof(float) * (size_t)count, (size_t)K, hipMemcpyDeviceToHost, ctx->stream));
-    // the results arrive in pinned memory a few microseconds before the stream is reported idle: poll the last one, then the rest
-    double t0 = 0.0;
-    for (unsigned spins = 0;; ++spins) {
-        int k = K - 1;
-        while (k >= 0 && out[k] != TRANSFORM_PENDING) --k;
-        if (k < 0) break;
-        if ((spins & 0xfff) == 0xfff) {
-            const double t = clock_now();
-            if (t0 == 0.0) t0 = t;
-            else if (t - t0 > 2.0) {
-                HIP_TRY(hipStreamSynchronize(ctx->stream));
-                for (k = 0; k < K; ++k)
-                    if (out[k] == TRANSFORM_PENDING) return fail(ECC_ERR_HIP, "the transform batch ran and stored no result");
-                break;
-            }
-        }
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    for (int k = 0; k < K; ++k) {
-        const uint64_t bits = out[k];
-        std::memcpy(&sums[k], &bits, sizeof(double));
-    }
+    rc = wait_pose_results(ctx, out, K, sums, "transform");
+    if (rc) return rc;
     if (values) HIP_TRY(wait_stream_spin(ctx->stream));  // the copy behind the sums
     return ECC_OK;
 }
 
-// The transforms one at a time, the way a caller without this entry point does it, then the base again.
-int run_sequential(ecc_metric* m, const std::vector<double>& base, int n_source, int n_transforms, const double* Ts, double* means,
-                   float* pair_values)
+}  // namespace
+namespace ecc_internal {
+// The transforms one at a time, the way a caller without these entry points does it -- the composed matrices, then
+// evaluate_list(k, the cross list, its length): pair q = j n_source + i is (i, n_source + j, i, n_source + j) -- then the base again.
+int transforms_sequential(ecc_metric* m, const std::vector<double>& base, int n_source, int n_transforms, const double* Ts,
+                          const std::function<int(int, const int32_t*, int)>& evaluate_list)
 {
     const int n = m->n_views, n_target = n - n_source;
     const int64_t count = (int64_t)n_source * n_target;
@@ -300,13 +281,30 @@ int run_sequential(ecc_metric* m, const std::vector<double>& base, int n_source,
         for (int i = 0; i < n_source; ++i)
             ecc_host::compose_transform(base.data() + 12 * (size_t)i, Ts + 16 * (size_t)k, full.data() + 12 * (size_t)i);
         rc = ecc_metric_set_projections(m, full.data(), n);
-        if (!rc) rc = ecc_metric_evaluate_pairs(m, idx.data(), (int)count, pair_values ? pair_values + (size_t)k * count : nullptr, &means[k]);
+        if (!rc) rc = evaluate_list(k, idx.data(), (int)count);
     }
     const int rb = ecc_metric_set_projections(m, base.data(), n);
     return rc ? rc : rb;
 }
 
-}  // namespace
+// n_transforms transforms of `count` pairs each as batches of whole transforms within ECC_POSE_BATCH_MAX_ENTRIES grid entries, at
+// most max_per_batch of them: run_batch(first transform, how many) each, which returns with the batch's results seen.
+int transforms_batched(ecc_metric* m, int64_t count, int n_transforms, int64_t max_per_batch, const std::function<int(int64_t, int)>& run_batch)
+{
+    const bool was_quiet = m->quiet;
+    ecc_mark_busy(m);
+    const int64_t per_batch = std::min<int64_t>(std::max<int64_t>(ECC_POSE_BATCH_MAX_ENTRIES / count, 1), max_per_batch);
+    for (int64_t k0 = 0; k0 < n_transforms; k0 += per_batch) {
+        const int K = (int)std::min<int64_t>(per_batch, n_transforms - k0);
+        const int rc = run_batch(k0, K);
+        if (rc) return rc;
+        m->last_batched_transforms += K;
+    }
+    HIP_TRY(wait_stream_spin(m->ctx->stream));  // (the results were seen before the stream's own completion; the scratch is reused)
+    m->quiet = was_quiet;  // what was known to be complete before the call still is
+    return ECC_OK;
+}
+}  // namespace ecc_internal
 
 ECC_EXPORT void ecc_host_compose_transform(const double* P12, const double* T16, double* out12)
 {
@@ -339,22 +337,16 @@ ECC_EXPORT int ecc_metric_evaluate_transforms(ecc_metric* m, int n_source, int n
     const int64_t n = m->n_views, count = (int64_t)n_source * (n - n_source);
     const double* Pcur = m->Ps_h[m->set_generation & 1].host;
     const std::vector<double> base(Pcur, Pcur + 12 * n);
-    if (!m->pose_batching || count > ECC_POSE_BATCH_MAX_ENTRIES) return run_sequential(m, base, n_source, n_transforms, Ts, means, pair_values);
-
-    const bool was_quiet = m->quiet;
-    ecc_mark_busy(m);
-    // batches of whole transforms within ECC_POSE_BATCH_MAX_ENTRIES grid entries
-    const int64_t per_batch = std::min<int64_t>(std::max<int64_t>(ECC_POSE_BATCH_MAX_ENTRIES / count, 1), TRANSFORM_BATCH_MAX);
+    if (!m->pose_batching || count > ECC_POSE_BATCH_MAX_ENTRIES)
+        return transforms_sequential(m, base, n_source, n_transforms, Ts, [&](int k, const int32_t* idx, int len) {
+            return ecc_metric_evaluate_pairs(m, idx, len, pair_values ? pair_values + (size_t)k * count : nullptr, &means[k]);
+        });
     std::vector<double> sums;
-    for (int64_t k0 = 0; k0 < n_transforms; k0 += per_batch) {
-        const int K = (int)std::min<int64_t>(per_batch, n_transforms - k0);
+    return transforms_batched(m, count, n_transforms, TRANSFORM_BATCH_MAX, [&](int64_t k0, int K) -> int {
         sums.resize((size_t)K);
-        rc = run_batch(m, base.data(), n_source, K, Ts + 16 * (size_t)k0, sums.data(), pair_values ? pair_values + (size_t)k0 * count : nullptr);
-        if (rc) return rc;
+        const int e = run_batch(m, base.data(), n_source, K, Ts + 16 * (size_t)k0, sums.data(), pair_values ? pair_values + (size_t)k0 * count : nullptr);
+        if (e) return e;
         for (int k = 0; k < K; ++k) means[k0 + k] = sums[k] / (double)count;  // ref: ...RadonIntermediate.cpp:224 (all weights are 1)
-        m->last_batched_transforms += K;
-    }
-    HIP_TRY(wait_stream_spin(m->ctx->stream));  // (the results were seen before the stream's own completion; the scratch is reused)
-    m->quiet = was_quiet;  // what was known to be complete before the call still is
-    return ECC_OK;
+        return ECC_OK;
+    });
 }

@@ -2,14 +2,15 @@
 // data: pose optimisers.  Host code; include/ecc_hip.h states the contracts.
 //
 // ecc_metric_evaluate_weighted_pairs        an index list of (P0, P1, D0, D1) tuples: k01_kernel with the list into the Gram family's
-//                                           records, the weighted pair launch, sum_gram_kernel over the two columns, the copies.
+//                                           records (column_call_begin, ecc_column_call.h), the weighted pair launch, sum_gram_kernel
+//                                           over the two columns, the copies (column_call_finish).
 // ecc_metric_evaluate_weighted_pose_deltas  K poses that each replace a few views of the current matrices (the lists of
 //                                           ecc_metric_evaluate_pose_deltas, ecc_poses.hip):
 //   base columns   {c, u} of all pairs at the current matrices (weighted_base_columns: ecc_metric_evaluate_weighted's own launches),
 //                  recomputed on every call
-//   per batch      pose_list_kernel (index grid, E1 of the extended matrices), k01_kernel over the n x Q grid into the pose batch's
-//                  records, the weighted pair launch over it (EccPairParams::n_views stays n: the weight copy of data copy iD is
-//                  n copies behind it), sum_weighted_poses_kernel: per pose both column sums over all pairs, the pose's own entries
+//   per batch      (which poses: ecc_pose_batches.h) pose_list_kernel (index grid, E1 of the extended matrices), k01_kernel over
+//                  the n x Q grid into the pose batch's records, the weighted pair launch over it (EccPairParams::n_views stays n:
+//                  the weight copy of data copy iD is n copies behind it), sum_weighted_poses_kernel: per pose both column sums over all pairs, the pose's own entries
 //                  substituted, in the order of ecc_sum_order.h -> 2 K pinned result words the host polls
 //   host           values[k] = sum c / sum u, coverages[k] = sum u / n_pairs
 // Every value and coverage has the bits of ecc_metric_set_projections + ecc_metric_evaluate_weighted for that pose
@@ -17,17 +18,11 @@
 // Not here: base columns kept between calls (a stale column is a silently wrong result; keeping them needs change tracking over
 // matrices, parameters, sampling mode, quad copies and ecc_metric_refresh_dtrs); the full-matrices, strided, group and RCCL forms;
 // an incremental mode for the weighted value; a one-launch small path for weighted lists.
-#include "ecc_capi_internal.h"
-#include "ecc_sum_order.h"
+#include "ecc_column_call.h"
+#include "ecc_pose_batches.h"
 
 using namespace ecc_internal;
 
-#ifndef ECC_POSE_BATCH_MAX_MOVED
-#define ECC_POSE_BATCH_MAX_MOVED 32  // (ecc_poses.hip)
-#endif
-
-extern "C" hipError_t ecc_launch_sum_gram(const float* values_d, long long col_stride, long long count, int n_columns, int n_slices,
-                                          double* partial_d, hipStream_t stream);
 extern "C" hipError_t ecc_launch_sum_weighted_poses(const float* base_cols, long long base_stride, long long count, int n, int Q,
                                                     const int32_t* lists_d, int K, const float* val_cols, long long vals_stride, int slices,
                                                     double* partial_d, double* out_host_dev, hipStream_t stream);
@@ -76,14 +71,6 @@ int run_weighted_batch(ecc_metric* m, const double* base, const EccPairParams& b
     return wait_pose_results(ctx, out, 2 * K, sums);
 }
 
-void finish_weighted(double sum_c, double sum_u, int64_t n_pairs, double* value, double* coverage)
-{
-    // ref: ...RadonIntermediate.cpp:224 (sum value w / sum w), as ecc_metric_evaluate_weighted forms it
-    const bool none = sum_u == 0.0;
-    *value = none ? 0.0 : sum_c / sum_u;
-    if (coverage) *coverage = none ? 0.0 : sum_u / (double)n_pairs;
-}
-
 // The batched poses of a call; what the batch does not take goes into not_batched.
 int weighted_deltas(ecc_metric* m, int n_poses, const int32_t* off, const int32_t* views, const double* moved_Ps, double* values,
                     double* coverages, std::vector<int>* not_batched)
@@ -95,47 +82,25 @@ int weighted_deltas(ecc_metric* m, int n_poses, const int32_t* off, const int32_
     const std::vector<double> base(Pcur, Pcur + 12 * n);
     double base_radius = 0.0;
     ecc_metric_get_object_radius(m, &base_radius);
-    EccPairParams base_p;
+    ColumnCall base_c;
     EccWeightedParams base_g;
-    int rc = weighted_base_columns(m, &base_p, &base_g);  // once per call
+    int rc = weighted_base_columns(m, &base_c, &base_g);  // once per call
     if (rc) return rc;
-    std::vector<int32_t> b_off, b_views;
-    std::vector<double> b_Ps, sums;
-    std::vector<int> b_pose;
+    std::vector<double> sums;
     const int64_t max_cols = std::max<int64_t>(ECC_POSE_BATCH_MAX_ENTRIES / n, ECC_POSE_BATCH_MAX_MOVED);
-    auto flush = [&]() -> int {
-        if (b_pose.empty()) return ECC_OK;
-        sums.resize(2 * b_pose.size());
-        const int e = run_weighted_batch(m, base.data(), base_p, base_g, (int)b_pose.size(), b_off.data(), b_views.data(), b_Ps.data(), sums.data());
-        if (e) return e;
-        for (size_t q = 0; q < b_pose.size(); ++q)
-            finish_weighted(sums[2 * q], sums[2 * q + 1], n_pairs, &values[b_pose[q]], coverages ? &coverages[b_pose[q]] : nullptr);
-        m->last_batched_poses += (int64_t)b_pose.size();
-        b_pose.clear();
-        b_off.assign(1, 0);
-        b_views.clear();
-        b_Ps.clear();
-        return ECC_OK;
-    };
-    b_off.assign(1, 0);
-    for (int k = 0; k < n_poses; ++k) {
-        const int c = off[k + 1] - off[k];
-        const int32_t* vk = views + off[k];
-        const double* Pk = moved_Ps + 12 * (size_t)off[k];
-        if (c > ECC_POSE_BATCH_MAX_MOVED || !pose_keeps_radius(m, base_radius, c, vk, Pk)) {
-            not_batched->push_back(k);
-            continue;
-        }
-        if ((int64_t)b_views.size() + c > max_cols || b_pose.size() >= WEIGHTED_BATCH_MAX_POSES) {
-            rc = flush();
-            if (rc) return rc;
-        }
-        b_pose.push_back(k);
-        b_views.insert(b_views.end(), vk, vk + c);
-        b_Ps.insert(b_Ps.end(), Pk, Pk + 12 * (size_t)c);
-        b_off.push_back((int32_t)b_views.size());
-    }
-    rc = flush();
+    rc = ecc_pose_batches::pack(
+        n_poses, off, views, moved_Ps, max_cols, WEIGHTED_BATCH_MAX_POSES,
+        [&](int c, const int32_t* vk, const double* Pk) { return pose_keeps_radius(m, base_radius, c, vk, Pk); },
+        [&](const ecc_pose_batches::Batch& b) -> int {
+            sums.resize(2 * b.pose.size());
+            const int e = run_weighted_batch(m, base.data(), base_c.p, base_g, (int)b.pose.size(), b.off.data(), b.views.data(), b.Ps.data(), sums.data());
+            if (e) return e;
+            for (size_t q = 0; q < b.pose.size(); ++q)
+                finish_weighted(sums[2 * q], sums[2 * q + 1], n_pairs, &values[b.pose[q]], coverages ? &coverages[b.pose[q]] : nullptr);
+            m->last_batched_poses += (int64_t)b.pose.size();
+            return ECC_OK;
+        },
+        not_batched);
     if (rc) return rc;
     HIP_TRY(wait_stream_spin(ctx->stream));  // (the results were seen before the stream's own completion; the scratch is reused)
     m->done_generation = m->set_generation;
@@ -161,56 +126,18 @@ ECC_EXPORT int ecc_metric_evaluate_weighted_pairs(ecc_metric* m, const int32_t* 
         if (t[0] < 0 || t[0] >= nP || t[1] < 0 || t[1] >= nP || t[2] < 0 || t[2] >= nP || t[3] < 0 || t[3] >= nP)
             return fail(ECC_ERR_INVALID_ARGUMENT, "index array contains invalid indices (matrices and data intermediates lie in [0, n_views))");
     }
-    ecc_ctx* ctx = m->ctx;
-    rc = set_device(ctx);
+    ColumnCall c;
+    rc = column_call_begin(m, idx4, n_pairs, 2, 2, &c);  // columns: c, u; the sampling mode of a list of n_pairs tuples, as ecc_metric_evaluate_pairs
     if (rc) return rc;
-    const int T = 2;  // columns: c, u
-    const int64_t count = n_pairs, col_stride = (count + 3) & ~(int64_t)3;
-    EccPairParams p;
-    rc = fill_pair_params(m, &p, count, /*need_e1=*/false);  // the sampling mode of a list of n_pairs tuples, as ecc_metric_evaluate_pairs
-    if (rc) return rc;
-    rc = m->gram_records_d.ensure(count, ctx->stream);
-    if (!rc) rc = m->gram_values_d.ensure((int64_t)T * col_stride, ctx->stream);
-    if (!rc) rc = m->gram_partial_d.ensure((int64_t)T * ecc_sum::SLICES, ctx->stream);
-    if (!rc) rc = m->pose_idx_d.ensure(4 * count, ctx->stream);
-    if (rc) return rc;
-    ecc_mark_busy(m);
-    rc = ensure_e1(m);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(m->pose_idx_d.ptr, idx4, sizeof(int32_t) * 4 * (size_t)count, hipMemcpyHostToDevice, ctx->stream));
-    p.indices = m->pose_idx_d.ptr;
-    p.first = 0;
-    p.count = count;
-    p.records = m->gram_records_d.ptr;
-    HIP_TRY(ecc_launch_k01(&p, ctx->stream));
-    const int64_t n = m->n_views;
-    const int64_t paired_bytes = (int64_t)(m->n_alpha + 1) * m->pitch * 2 * (int64_t)sizeof(float);
     EccWeightedParams g;
-    g.paired_channel_bytes = n * paired_bytes;
-    g.quad_channel_bytes = n * m->quad_floats * (int64_t)sizeof(float);
+    set_channel_strides(m, &g);
     g.values = m->gram_values_d.ptr;
-    g.col_stride = col_stride;
-    HIP_TRY(launch_weighted_timed(ctx, &p, &g));
-    // both columns in the order a list of n_pairs values is added in (ecc_sum_order.h)
-    const int n_slices = ecc_sum::slices(count, m->sum_scratch_d.ptr != nullptr);
-    HIP_TRY(ecc_launch_sum_gram(m->gram_values_d.ptr, col_stride, count, T, n_slices, m->gram_partial_d.ptr, ctx->stream));
-    std::vector<double> partial((size_t)T * ecc_sum::SLICES);
-    HIP_TRY(hipMemcpyAsync(partial.data(), m->gram_partial_d.ptr, sizeof(double) * partial.size(), hipMemcpyDeviceToHost, ctx->stream));
-    std::vector<float> cols;
-    if (pair_terms) {
-        cols.resize((size_t)T * (size_t)col_stride);
-        HIP_TRY(hipMemcpyAsync(cols.data(), m->gram_values_d.ptr, sizeof(float) * cols.size(), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(wait_stream_spin(ctx->stream));
-    m->done_generation = m->set_generation;
-    m->quiet = true;  // the copies are the last thing this call queued, and they have landed
-    double sum_c = 0.0, sum_u = 0.0;
-    for (int s = 0; s < n_slices; ++s) sum_c += partial[(size_t)s];
-    for (int s = 0; s < n_slices; ++s) sum_u += partial[(size_t)ecc_sum::SLICES + s];
-    finish_weighted(sum_c, sum_u, count, value, coverage);
-    if (pair_terms)
-        for (int64_t q = 0; q < count; ++q)
-            for (int u = 0; u < T; ++u) pair_terms[(size_t)q * T + u] = cols[(size_t)u * col_stride + q];
+    g.col_stride = c.col_stride;
+    HIP_TRY(launch_weighted_timed(m->ctx, &c.p, &g));
+    double totals[2];  // both columns in the order a list of n_pairs values is added in (ecc_sum_order.h)
+    rc = column_call_finish(m, c, 2, totals, 2, m->gram_values_d.ptr, pair_terms);
+    if (rc) return rc;
+    finish_weighted(totals[0], totals[1], n_pairs, value, coverage);
     return ECC_OK;
 }
 
@@ -227,7 +154,6 @@ ECC_EXPORT int ecc_metric_evaluate_weighted_pose_deltas(ecc_metric* m, int n_pos
     rc = set_device(m->ctx);
     if (rc) return rc;
     m->last_batched_poses = 0;
-    const int64_t n = m->n_views;
     std::vector<int> rest;
     if (m->pose_batching) {
         rc = weighted_deltas(m, n_poses, moved_offsets, moved_views, moved_Ps, values, coverages, &rest);
@@ -235,21 +161,7 @@ ECC_EXPORT int ecc_metric_evaluate_weighted_pose_deltas(ecc_metric* m, int n_pos
     } else {
         for (int k = 0; k < n_poses; ++k) rest.push_back(k);
     }
-    if (rest.empty()) return ECC_OK;
-    // what the batch does not take (more moved views than it handles, a changed automatic radius, batching off): the pose's
-    // full matrices the sequential way, then the base again
-    const double* Pcur = m->Ps_h[m->set_generation & 1].host;
-    const std::vector<double> base(Pcur, Pcur + 12 * n);
-    std::vector<double> full(base);
-    for (int k : rest) {
-        for (int q = moved_offsets[k]; q < moved_offsets[k + 1]; ++q)
-            std::memcpy(full.data() + 12 * (size_t)moved_views[q], moved_Ps + 12 * (size_t)q, sizeof(double) * 12);
-        rc = ecc_metric_set_projections(m, full.data(), (int)n);
-        if (!rc) rc = ecc_metric_evaluate_weighted(m, &values[k], coverages ? &coverages[k] : nullptr, nullptr);
-        if (rc) break;
-        for (int q = moved_offsets[k]; q < moved_offsets[k + 1]; ++q)
-            std::memcpy(full.data() + 12 * (size_t)moved_views[q], base.data() + 12 * (size_t)moved_views[q], sizeof(double) * 12);
-    }
-    const int rb = ecc_metric_set_projections(m, base.data(), (int)n);
-    return rc ? rc : rb;
+    return pose_deltas_sequential(m, rest, moved_offsets, moved_views, moved_Ps, [&](int k) {
+        return ecc_metric_evaluate_weighted(m, &values[k], coverages ? &coverages[k] : nullptr, nullptr);
+    });
 }

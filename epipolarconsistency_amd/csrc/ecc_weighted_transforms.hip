@@ -33,14 +33,6 @@ namespace {
 constexpr int64_t WEIGHTED_TRANSFORM_BATCH_MAX = 32768;
 static_assert(WEIGHTED_TRANSFORM_BATCH_MAX < 65536, "transforms are the y dimension of sum_weighted_transforms_kernel's grid");
 
-void finish_weighted(double sum_c, double sum_u, int64_t count, double* value, double* coverage)
-{
-    // ref: ...RadonIntermediate.cpp:224 (sum value w / sum w), as ecc_metric_evaluate_weighted_pairs forms it
-    const bool none = sum_u == 0.0;
-    *value = none ? 0.0 : sum_c / sum_u;
-    if (coverage) *coverage = none ? 0.0 : sum_u / (double)count;
-}
-
 // One batch: K transforms Ts (16 doubles each) of the base matrices (n x 12).  sums[2 k], sums[2 k + 1]: sum c and sum u of
 // transform k over its cross list; pair_terms (nullable, host): K x count rows {c, u}.
 int run_batch(ecc_metric* m, const double* base, int n_source, int K, const double* Ts, double* sums, float* pair_terms)
@@ -66,10 +58,8 @@ int run_batch(ecc_metric* m, const double* base, int n_source, int K, const doub
     p.count = entries;
     if (m->object_radius_mm > 0) HIP_TRY(ecc_launch_k01(&p, ctx->stream));
     else HIP_TRY(ecc_launch_k01_radii(&p, m->transform_radii_d.ptr, K, ctx->stream));  // every transform the radius of its composed view 0
-    const int64_t paired_bytes = (int64_t)(m->n_alpha + 1) * m->pitch * 2 * (int64_t)sizeof(float);
     EccWeightedParams g;  // (p.n_views stays n: the weight copy of data copy D is n copies behind it)
-    g.paired_channel_bytes = n * paired_bytes;
-    g.quad_channel_bytes = n * m->quad_floats * (int64_t)sizeof(float);
+    set_channel_strides(m, &g);
     g.values = m->pose_values_d.ptr;
     g.col_stride = vals_stride;
     HIP_TRY(launch_weighted_timed(ctx, &p, &g));
@@ -89,34 +79,6 @@ int run_batch(ecc_metric* m, const double* base, int n_source, int K, const doub
             for (int u = 0; u < 2; ++u)
                 pair_terms[2 * ((size_t)k * count + q) + u] = ecc_transform_grid::value(cols.data() + (size_t)u * vals_stride, q, k, K);
     return ECC_OK;
-}
-
-// The transforms one at a time, the way a caller without this entry point does it, then the base again.
-int run_sequential(ecc_metric* m, const std::vector<double>& base, int n_source, int n_transforms, const double* Ts, double* values,
-                   double* coverages, float* pair_terms)
-{
-    const int n = m->n_views, n_target = n - n_source;
-    const int64_t count = (int64_t)n_source * n_target;
-    if (count > std::numeric_limits<int>::max()) return fail(ECC_ERR_INVALID_ARGUMENT, "the index list of one transform is too long");
-    std::vector<int32_t> idx(4 * (size_t)count);
-    for (int j = 0; j < n_target; ++j)
-        for (int i = 0; i < n_source; ++i) {
-            int32_t* t = idx.data() + 4 * ((size_t)j * n_source + i);
-            t[0] = t[2] = i;
-            t[1] = t[3] = n_source + j;
-        }
-    std::vector<double> full(base);
-    int rc = ECC_OK;
-    for (int k = 0; k < n_transforms && !rc; ++k) {
-        for (int i = 0; i < n_source; ++i)
-            ecc_host::compose_transform(base.data() + 12 * (size_t)i, Ts + 16 * (size_t)k, full.data() + 12 * (size_t)i);
-        rc = ecc_metric_set_projections(m, full.data(), n);
-        if (!rc)
-            rc = ecc_metric_evaluate_weighted_pairs(m, idx.data(), (int)count, &values[k], coverages ? &coverages[k] : nullptr,
-                                                    pair_terms ? pair_terms + 2 * (size_t)k * count : nullptr);
-    }
-    const int rb = ecc_metric_set_projections(m, base.data(), n);
-    return rc ? rc : rb;
 }
 
 }  // namespace
@@ -139,22 +101,16 @@ ECC_EXPORT int ecc_metric_evaluate_weighted_transforms(ecc_metric* m, int n_sour
     const double* Pcur = m->Ps_h[m->set_generation & 1].host;
     const std::vector<double> base(Pcur, Pcur + 12 * n);
     if (!m->pose_batching || count > ECC_POSE_BATCH_MAX_ENTRIES)
-        return run_sequential(m, base, n_source, n_transforms, Ts, values, coverages, pair_terms);
-
-    const bool was_quiet = m->quiet;
-    ecc_mark_busy(m);
-    // batches of whole transforms within ECC_POSE_BATCH_MAX_ENTRIES grid entries
-    const int64_t per_batch = std::min<int64_t>(std::max<int64_t>(ECC_POSE_BATCH_MAX_ENTRIES / count, 1), WEIGHTED_TRANSFORM_BATCH_MAX);
+        return transforms_sequential(m, base, n_source, n_transforms, Ts, [&](int k, const int32_t* idx, int len) {
+            return ecc_metric_evaluate_weighted_pairs(m, idx, len, &values[k], coverages ? &coverages[k] : nullptr,
+                                                      pair_terms ? pair_terms + 2 * (size_t)k * count : nullptr);
+        });
     std::vector<double> sums;
-    for (int64_t k0 = 0; k0 < n_transforms; k0 += per_batch) {
-        const int K = (int)std::min<int64_t>(per_batch, n_transforms - k0);
+    return transforms_batched(m, count, n_transforms, WEIGHTED_TRANSFORM_BATCH_MAX, [&](int64_t k0, int K) -> int {
         sums.resize(2 * (size_t)K);
-        rc = run_batch(m, base.data(), n_source, K, Ts + 16 * (size_t)k0, sums.data(), pair_terms ? pair_terms + 2 * (size_t)k0 * count : nullptr);
-        if (rc) return rc;
+        const int e = run_batch(m, base.data(), n_source, K, Ts + 16 * (size_t)k0, sums.data(), pair_terms ? pair_terms + 2 * (size_t)k0 * count : nullptr);
+        if (e) return e;
         for (int k = 0; k < K; ++k) finish_weighted(sums[2 * k], sums[2 * k + 1], count, &values[k0 + k], coverages ? &coverages[k0 + k] : nullptr);
-        m->last_batched_transforms += K;
-    }
-    HIP_TRY(wait_stream_spin(m->ctx->stream));  // (the results were seen before the stream's own completion; the scratch is reused)
-    m->quiet = was_quiet;  // what was known to be complete before the call still is
-    return ECC_OK;
+        return ECC_OK;
+    });
 }

@@ -142,6 +142,20 @@ def test_pose_diff_finds_the_moved_views_whatever_the_thread_count(tmp_path):
     assert r.returncode == 0 and "ok" in r.stdout, r.stdout + r.stderr
 
 
+def test_pose_batches_packs_the_poses_as_the_loop_it_replaces(tmp_path):
+    """csrc/ecc_pose_batches.h (host only): which poses of a pose-delta call go into which batch (ecc_metric_evaluate_pose_deltas,
+    ecc_metric_evaluate_weighted_pose_deltas) -- 2, 3, 5 and 40 views; poses with 0, 1, ECC_POSE_BATCH_MAX_MOVED and one more moved
+    views; poses that move view 0 and change the automatic radius; column totals on, one below and one above max_cols; small pose
+    bounds; an empty call; calls in which nothing is batched; a failing batch: the batches (offsets, views, matrices, pose indices),
+    the not_batched list, the flush points and the order of the loop ecc_poses.hip had before (a verbatim copy in the driver)."""
+    import subprocess
+    exe = os.path.join(str(tmp_path), "pose_batches")
+    subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", os.path.join(ROOT, "tests", "c", "pose_batches.cpp"), "-o", exe],
+                   check=True)
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.startswith("ok: "), r.stdout + r.stderr
+
+
 def test_view_changes_lists_the_pairs_of_the_changed_views(tmp_path):
     """csrc/ecc_view_changes.h (host only): the change scan and the pair list of the record-reuse, pose-delta and one-launch
     paths -- n from 2 to 600 views (past the 512-view skip mask), full, empty and shard ranges (the ones sharding.pair_range
