@@ -401,7 +401,8 @@ class MetricRadonIntermediate:
         self._incremental = False
         self._record_reuse = None  # library default (on unless ECC_RECORD_REUSE=0)
         self._small_eval = None    # library default (on)
-        self._debug = {}           # ecc_debug_* settings of this object (experiments), re-applied to a new handle
+        self._host_join = None     # library default (on)
+        self._debug = {}         # ecc_debug_* settings of this object (experiments), re-applied to a new handle
         # the optimiser loop's two calls, setProjectionMatrices + evaluate(): data pointers of the caller's (n, 12) arrays by
         # array object (ndarray.ctypes costs 1.2 us per call; the arrays are kept alive here, at most 1024 of them), and the
         # result cell of evaluate()
@@ -427,6 +428,8 @@ class MetricRadonIntermediate:
             check(_lib.lib().ecc_metric_set_record_reuse(self._h, int(self._record_reuse)))
         if self._small_eval is not None:
             check(_lib.lib().ecc_metric_set_small_eval(self._h, int(self._small_eval)))
+        if self._host_join is not None:
+            check(_lib.lib().ecc_metric_set_host_join(self._h, int(self._host_join)))
         self._apply_debug()
         if self._Ps is not None:
             self.setProjectionMatrices(self._Ps)
@@ -565,8 +568,17 @@ class MetricRadonIntermediate:
             check(_lib.lib().ecc_metric_set_small_eval(self._h, self._small_eval))
         return self
 
+    def setHostJoin(self, on=True):
+        """ecc_metric_set_host_join (default on): evaluate() and evaluate_range() of the two-stream record-reuse form wait on the
+        host for the moved views' launches and then queue the sum, instead of ordering it with an event on the device; the same
+        launches and bit-identical results either way.  Kept across setRadonIntermediates like the other settings."""
+        self._host_join = 1 if on else 0
+        if self._h:
+            check(_lib.lib().ecc_metric_set_host_join(self._h, self._host_join))
+        return self
+
     def device_bytes(self):
-        """ecc_metric_device_bytes -> {"paired_copies", "quad_copies", "other"}: device memory this metric owns right now (the
+        """ecc_metric_device_bytes ->{"paired_copies", "quad_copies", "other"}: device memory this metric owns right now (the
         Radon intermediates themselves belong to their RadonIntermediate objects)."""
         a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
         check(_lib.lib().ecc_metric_device_bytes(self._h, C.byref(a), C.byref(b), C.byref(c)))

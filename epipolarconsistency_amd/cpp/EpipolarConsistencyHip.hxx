@@ -616,6 +616,7 @@ class MetricRadonIntermediate : public Metric {
     bool incremental;
     int record_reuse = -1;    // -1: the library's default
     int small_eval = -1;      // -1: the library's default (on)
+    int host_join = -1;       // -1: the library's default (on; a group's metrics: off)
     ecc_metric* m_h;          // single-device metric, or the group's rank-0 metric (borrowed) when m_gh is set
     ecc_group_metric* m_gh;   // sharded over a group of devices (ecc_group_*), else null
     ecc_ctx* m_ctx;
@@ -643,6 +644,7 @@ class MetricRadonIntermediate : public Metric {
             detail::check(ecc_metric_set_incremental(m_h, incremental ? 1 : 0));
             if (record_reuse >= 0) detail::check(ecc_metric_set_record_reuse(m_h, record_reuse));
             if (small_eval >= 0) detail::check(ecc_metric_set_small_eval(m_h, small_eval));
+            if (host_join >= 0) detail::check(ecc_metric_set_host_join(m_h, host_join));
         }
     }
     void push_projections()
@@ -704,6 +706,10 @@ public:
     /// Not in the reference: ecc_metric_set_small_eval (library default: on) -- evaluations of a few pairs (index lists,
     /// evaluate() of a handful of views: the FluoroTracking pattern) go out as ONE kernel launch; bit-identical results.
     MetricRadonIntermediate& setSmallEval(bool on = true) { small_eval = on ? 1 : 0; push_params(); return *this; }
+    /// Not in the reference: ecc_metric_set_host_join (library default: on) -- evaluate() of the two-stream record-reuse form waits
+    /// on the host for the moved views' launches and then queues the sum, instead of ordering it with an event on the device; the
+    /// same launches, bit-identical results.  Single-device metrics only: a group's metrics keep the device-side order.
+    MetricRadonIntermediate& setHostJoin(bool on = true) { host_join = on ? 1 : 0; push_params(); return *this; }
     /// Not in the reference: ecc_metric_evaluate_poses -- independent all-pairs evaluations of several sets of projection
     /// matrices (a sweep as in Gui/Visualization.h:78-98 plotCostFunction, the probes of a finite-difference gradient),
     /// each value bit-identical to setProjectionMatrices(poses[k]) + evaluate().  Poses that differ from the current matrices

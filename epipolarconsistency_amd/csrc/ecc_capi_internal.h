@@ -353,6 +353,9 @@ struct ecc_metric {
     // (which skips them) already runs on the context's stream
     hipStream_t side_stream = nullptr;
     hipEvent_t fork_ev = nullptr, join_ev = nullptr;
+    // ecc_metric_set_host_join: the synchronous all-pairs / range evaluations see join_ev complete on the host and then queue the
+    // sum, instead of making the context's stream wait for it in front of the sum (ecc_evaluate.hip, wait_side_stream)
+    int host_join = 1;
     // Everything this metric has queued on the context's stream or its side stream is KNOWN to have completed: set by the
     // synchronous evaluations once they have seen their result (the last thing they queued), cleared by whatever queues work for
     // the metric.  The two-stream refit then needs no fork event: what the side stream reads -- records, device geometry, the
@@ -441,7 +444,7 @@ int ensure_e1(ecc_metric* m);  // E1 on the device for the staged matrices, if t
 // ecc_evaluate.hip: the parameters of a launch; the stream-ordered launches over a pair range; the pose-delta path
 int fill_pair_params(ecc_metric* m, EccPairParams* p, int64_t mode_count, bool need_e1 = true);
 int launch_range(ecc_metric* m, int64_t first, int64_t count, float* pair_values_d, float* cost_d, float* K01_d, double* sum_d,
-                 bool synchronous = false);
+                 bool synchronous = false, bool host_join = false);
 int evaluate_cached(ecc_metric* m, int64_t first, int64_t count, double* sum_d, float** vals_out);
 
 // ecc_poses.hip: the segmented sum behind a batch's pair launch and the wait for its results; whether a pose keeps the base's

@@ -303,6 +303,26 @@ bool ensure_side_stream(ecc_metric* m)
     return true;
 }
 
+// The host-side join of the two-stream form: returns once join_ev -- recorded behind the moved views' list launch on the side
+// stream -- has completed.  That launch is through some 200 us before the all-pairs launch beside it ends, so a synchronous
+// caller, which has nothing else to do, sees it here and then queues the sum on the context's stream with no cross-stream wait
+// in front of it: the barrier packet of hipStreamWaitEvent is processed only when the all-pairs launch has ended, and the sum
+// started 5.8 us behind that launch instead of the 3.0 us of a plain kernel boundary.  A bounded poll like wait_result's (the
+// blocking wait sleeps), then the blocking wait.
+hipError_t wait_side_stream(ecc_metric* m)
+{
+    double t0 = 0.0;
+    for (unsigned spins = 0;; ++spins) {
+        const hipError_t e = hipEventQuery(m->join_ev);
+        if (e != hipErrorNotReady) return e;
+        if ((spins & 0xff) == 0xff) {
+            const double t = pose_now();
+            if (t0 == 0.0) t0 = t;
+            else if (t - t0 > 2.0) return hipEventSynchronize(m->join_ev);
+        }
+    }
+}
+
 // The all-pairs launch of the reuse path on the context's stream, skipping the pairs of the changed views.
 int launch_skipping(ecc_metric* m, const EccPairParams& p, const std::vector<int>& changed, bool* pairs_launched)
 {
@@ -320,7 +340,11 @@ int launch_skipping(ecc_metric* m, const EccPairParams& p, const std::vector<int
 // whose device geometry is behind (host_e1), so e1_kernel is not launched.  With two streams the all-pairs launch skips those
 // pairs and their own launch runs beside it.  *reused = false (too many views changed, or the device geometry is not known):
 // nothing was launched.  *pairs_launched: the all-pairs launch is in the context's stream.
-int launch_reused(ecc_metric* m, const EccPairParams& p, bool synchronous, bool was_quiet, bool* reused, bool* pairs_launched)
+// host_join (a synchronous caller that queues a sum behind this): the context's stream is NOT made to wait for the side stream;
+// *join_pending = true says that join_ev has been recorded there, and the caller sees it complete (wait_side_stream) before it
+// queues anything that reads the values.
+int launch_reused(ecc_metric* m, const EccPairParams& p, bool synchronous, bool host_join, bool was_quiet, bool* reused,
+                  bool* pairs_launched, bool* join_pending)
 {
     ecc_ctx* ctx = m->ctx;
     const int64_t n = m->n_views;
@@ -419,7 +443,8 @@ int launch_reused(ecc_metric* m, const EccPairParams& p, bool synchronous, bool 
                 q.beside_another_launch = p.count >= ECC_BESIDE_ONE_WAVE_MIN_PAIRS ? 2 : 1;
                 HIP_TRY(ecc_launch_pairs(&q, m->side_stream));
                 HIP_TRY(hipEventRecord(m->join_ev, m->side_stream));
-                HIP_TRY(hipStreamWaitEvent(ctx->stream, m->join_ev, 0));
+                if (host_join) *join_pending = true;
+                else HIP_TRY(hipStreamWaitEvent(ctx->stream, m->join_ev, 0));
             }
             return ECC_OK;
         };
@@ -460,7 +485,7 @@ int launch_reused(ecc_metric* m, const EccPairParams& p, bool synchronous, bool 
 }  // namespace
 namespace ecc_internal {
 int launch_range(ecc_metric* m, int64_t first, int64_t count, float* pair_values_d, float* cost_d, float* K01_d,
-                 double* sum_d, bool synchronous)
+                 double* sum_d, bool synchronous, bool host_join)
 {
     ecc_ctx* ctx = m->ctx;
     const bool was_quiet = m->quiet;  // nothing of this metric's is pending on either stream (ecc_capi_internal.h)
@@ -506,11 +531,12 @@ int launch_range(ecc_metric* m, int64_t first, int64_t count, float* pair_values
     const bool keep = m->record_reuse && !K01_d && count > 0;  // this evaluation's records are kept for the next one
     const bool rec_match = keep && size_ok && m->rec.matches(first, count, (int)n, key);
     m->rec.valid = false;  // until everything below is enqueued
-    bool reused = false, pairs_launched = false;
+    bool reused = false, pairs_launched = false, join_pending = false;
     ecc_stamp(m, 3);
     m->stamps[4] = m->stamps[5] = 0.0;
     if (rec_match) {
-        rc = launch_reused(m, p, synchronous, was_quiet, &reused, &pairs_launched);
+        rc = launch_reused(m, p, synchronous, host_join && m->host_join && synchronous && sum_d && count > 0, was_quiet, &reused,
+                           &pairs_launched, &join_pending);
         if (rc) return rc;
     }
     if (!reused) {
@@ -526,7 +552,18 @@ int launch_range(ecc_metric* m, int64_t first, int64_t count, float* pair_values
     ecc_stamp(m, 5);
     if (!pairs_launched) HIP_TRY(launch_pairs_timed(ctx, &p));
     if (m->stamps[4] == 0.0) ecc_stamp(m, 4);
-    if (sum_d) {
+    ecc_stamp(m, 8);  // step queued: everything but the sum
+    if (join_pending) {
+        // The moved views' values are in their slots once join_ev has completed, visible to any kernel launched after that;
+        // the sum still runs behind the all-pairs launch by stream order.  An error must not leave side-stream work
+        // un-joined (launch_reused): the side stream is drained first.
+        hipError_t e = wait_side_stream(m);
+        if (e == hipSuccess) e = ecc_launch_sum_pairs(pair_values_d, count, sum_d, m->sum_scratch_d.ptr, ctx->stream);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(m->side_stream);
+            HIP_TRY(e);
+        }
+    } else if (sum_d) {
         if (count > 0) HIP_TRY(ecc_launch_sum_pairs(pair_values_d, count, sum_d, m->sum_scratch_d.ptr, ctx->stream));
         else if (sum_d == m->sum_h.dev) std::memset(m->sum_h.host, 0, sizeof(double));  // empty shard: nothing is launched
         else HIP_TRY(hipMemsetAsync(sum_d, 0, sizeof(double), ctx->stream));
@@ -697,7 +734,7 @@ ECC_EXPORT int ecc_metric_evaluate_range(ecc_metric* m, int64_t first, int64_t c
     float* vals_d = m->pair_values_d.ptr;
     if (m->incremental) rc = evaluate_cached(m, first, count, m->sum_h.dev, &vals_d);
     else {
-        rc = launch_range(m, first, count, m->pair_values_d.ptr, nullptr, nullptr, m->sum_h.dev, /*synchronous=*/true);
+        rc = launch_range(m, first, count, m->pair_values_d.ptr, nullptr, nullptr, m->sum_h.dev, /*synchronous=*/true, /*host_join=*/true);
         m->last_evaluated_pairs = count;
     }
     if (rc) return rc;
@@ -739,7 +776,7 @@ ECC_EXPORT int ecc_metric_evaluate_all(ecc_metric* m, float* cost_nxn, double* m
         float* vals_d = nullptr;
         rc = evaluate_cached(m, 0, n_pairs, m->sum_h.dev, &vals_d);
     } else {
-        rc = launch_range(m, 0, n_pairs, m->pair_values_d.ptr, cost_d, nullptr, m->sum_h.dev, /*synchronous=*/true);  // the sum lands in pinned host memory
+        rc = launch_range(m, 0, n_pairs, m->pair_values_d.ptr, cost_d, nullptr, m->sum_h.dev, /*synchronous=*/true, /*host_join=*/true);  // the sum lands in pinned host memory
         m->last_evaluated_pairs = n_pairs;
     }
     if (rc) return rc;

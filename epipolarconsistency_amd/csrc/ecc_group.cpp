@@ -302,6 +302,8 @@ ECC_EXPORT int ecc_group_metric_create(ecc_group* g, int n_dtrs, ecc_dtr* const*
             if (e != ECC_OK) return e;
         }
         const int e = ecc_metric_create(g->ctxs[r], n_dtrs, raw->dtrs[r].data(), &raw->metrics[r]);  // synchronises the stream
+        // (a rank's shard is a short launch the moved view's list launch is not hidden behind: the sum stays ordered on the device)
+        if (e == ECC_OK) (void)ecc_metric_set_host_join(raw->metrics[r], 0);
         if (e != ECC_OK || all_local) return e;
         // The replica must BE the stack: three probes (first, middle, last Radon intermediate, 1 KB from the middle of
         // each) read back from the copy and from its source.  A peer copy that silently did something else (first contact

@@ -209,6 +209,13 @@ ECC_EXPORT int ecc_metric_set_record_reuse(ecc_metric* m, int on)
     return ECC_OK;
 }
 
+ECC_EXPORT int ecc_metric_set_host_join(ecc_metric* m, int on)
+{
+    if (!m) return fail(ECC_ERR_INVALID_ARGUMENT, "metric is null");
+    m->host_join = on ? 1 : 0;  // (read when an evaluation queues its sum: nothing pending depends on it)
+    return ECC_OK;
+}
+
 ECC_EXPORT int ecc_metric_set_small_eval(ecc_metric* m, int on)
 {
     if (!m) return fail(ECC_ERR_INVALID_ARGUMENT, "metric is null");

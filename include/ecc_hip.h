@@ -324,7 +324,10 @@ int ecc_metric_last_evaluated_pairs(const ecc_metric* m, int64_t* pairs);
  * queued on the context's stream -- it reads nothing anybody else writes: records, device geometry, the row-paired copies
  * (ecc_metric_refresh_dtrs), pinned lists -- and is left out when the previous call was a synchronous evaluation, which
  * returns only after it has seen its result; the final sum is ordered after both streams (up to 512 views, no cost image;
- * otherwise one stream). */
+ * otherwise one stream).  The synchronous calls (ecc_metric_evaluate_all, ecc_metric_evaluate_range) order it on the host: they
+ * wait for the side stream's event -- its launches end long before the all-pairs launch does -- and then queue the sum behind the
+ * all-pairs launch, so no cross-stream wait stands between the two kernels; the asynchronous, RCCL and group forms order it with
+ * an event on the device.  The same launches with the same arguments either way. */
 #define ECC_RECORD_REUSE_MIN_PAIRS 4096
 #ifndef ECC_RECORD_REUSE_SPLIT_PAIRS
 #define ECC_RECORD_REUSE_SPLIT_PAIRS 8192
@@ -334,6 +337,12 @@ int ecc_metric_last_evaluated_pairs(const ecc_metric* m, int64_t* pairs);
  * cannot hide the refit's launches: measured 2016 pairs, 61 us per step with two streams, 40 us refitting everything; a
  * 10 873-pair shard 63 us with, 77 us without); 2 = the two-stream form for every size (tests). */
 int ecc_metric_set_record_reuse(ecc_metric* m, int on);
+/* The host-side join of the two-stream form described above (default on; 0: every call orders the sum with an event on the
+ * device, as the asynchronous forms do).  With it ecc_metric_evaluate_all / ecc_metric_evaluate_range poll the side stream's event
+ * while the all-pairs launch runs -- the calling thread would poll for the result anyway -- and the sum kernel starts about 3 us
+ * behind the all-pairs launch instead of about 6 (MI355X, 79 800 pairs).  The metrics of an ecc_group are created with it off.
+ * Results are bit-identical either way. */
+int ecc_metric_set_host_join(ecc_metric* m, int on);
 
 /* One launch per small evaluation (default on).  An evaluation of at most 192 pairs -- ecc_metric_evaluate_all of up to 20
  * views, small ecc_metric_evaluate_range shards, short ecc_metric_evaluate_pairs index lists; not with use_corr, not the
@@ -1072,9 +1081,12 @@ int ecc_debug_small_stamps(unsigned long long* out, int n_blocks);
 /* Host clock (seconds, std::chrono::steady_clock) at fixed points of the metric's last ecc_metric_set_projections and last
  * synchronous all-pairs / range evaluation -- where the host's share of a step goes (scripts/step_fixed_cost.py):
  * [0] set_projections entered, [1] returned; [2] evaluate entered, [3] change detection done (first launch next),
- * [4] first pair-kernel launch returned, [5] refit / list launches queued, [6] sum launch returned, [7] result seen. */
-#define ECC_STEP_STAMPS 8
-int ecc_debug_step_stamps(const ecc_metric* m, double* out8);
+ * [4] first pair-kernel launch returned, [5] refit / list launches queued, [6] sum launch returned, [7] result seen,
+ * [8] step queued: every launch of the evaluation but the sum is in its stream ([6] - [8] is then the host-side join of the
+ * two-stream form -- ecc_metric_evaluate_all and ecc_metric_evaluate_range wait for the moved views' list launch on the host and
+ * queue the sum behind the all-pairs launch with no cross-stream wait -- plus the sum's launch call).  out: ECC_STEP_STAMPS doubles. */
+#define ECC_STEP_STAMPS 9
+int ecc_debug_step_stamps(const ecc_metric* m, double* out);
 
 #ifdef __cplusplus
 }

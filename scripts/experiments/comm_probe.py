@@ -31,7 +31,7 @@ def run(tag, f):
     torch.cuda.synchronize(); t0 = time.perf_counter()
     for k in range(600): m.setProjectionMatrices(P2 if k & 1 else P); f()
     torch.cuda.synchronize(); dt = 1e6 * (time.perf_counter() - t0) / 600
-    st = np.zeros(8); _lib.lib().ecc_debug_step_stamps(m._h, C.c_void_p(st.ctypes.data))
+    st = np.zeros(9); _lib.lib().ecc_debug_step_stamps(m._h, C.c_void_p(st.ctypes.data))
     print(tag, "step %.1f us, kernel %.1f us, stamps(us) %s" % (dt, 1e3 * np.median(ks), np.round(1e6 * (st[1:] - st[0]), 1)))
 if mode == "commfirst":
     comm = sharding.RcclComm(ctx, 0, 1, sharding.torch_broadcast_bytes(dev))

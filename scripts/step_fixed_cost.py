@@ -3,7 +3,7 @@
 One view moves per step (ref: Gui/SingleImageMotion.h:84-90), like bench.py.  world = 1: all 79 800 pairs (the step bench.py
 times); world = G: the middle rank's cost-balanced shard of a G-rank job (scripts/shard_step.py's step, but WITH the moved
 view).  Reports the step time, the pair kernel's time (HIP events, separate pass), and the host's stamps inside the two
-calls (ecc_debug_step_stamps): set_projections, change detection, first launch, refit launches, sum launch, result."""
+calls (ecc_debug_step_stamps): set_projections, change detection, first launch, refit launches, step queued, sum launch, result."""
 import ctypes as C
 import os
 import sys
@@ -46,14 +46,14 @@ def step(k):
     return metric.evaluate() if world == 1 else metric.evaluate_range(first, count)
 
 
-stamps = np.zeros(8)
+stamps = np.zeros(9)
 for reuse in (True, False):
     metric.setRecordReuse(reuse)
     for k in range(40):
         step(k)
     ctx.enable_timing(False)
     torch.cuda.synchronize()
-    acc = np.zeros(8)
+    acc = np.zeros(9)
     t0 = time.perf_counter()
     for k in range(steps):
         step(k)
@@ -69,5 +69,6 @@ for reuse in (True, False):
     a = acc / steps * 1e6
     print("world %d (%d pairs), record reuse %s: step %.1f us, pair kernel %.1f us, non-pair %.1f us" % (world, count, reuse, el * 1e6, pk, el * 1e6 - pk))
     print("   host stamps (us after set_projections entered): set returned %.1f | evaluate entered %.1f | change detection done %.1f | "
-          "first pair launch returned %.1f | refit launches queued %.1f | sum launch returned %.1f | result seen %.1f | "
-          "(next set_projections %.1f later)" % (a[1], a[2], a[3], a[4], a[5], a[6], a[7], el * 1e6 - a[7]))
+          "first pair launch returned %.1f | refit launches queued %.1f | step queued %.1f | sum launch returned %.1f (behind the "
+          "host-side join, where the call takes it) | result seen %.1f | (next set_projections %.1f later)"
+          % (a[1], a[2], a[3], a[4], a[5], a[8], a[6], a[7], el * 1e6 - a[7]))
