@@ -690,6 +690,24 @@ class MetricRadonIntermediate:
                                                                   C.c_void_p(values.ctypes.data), C.c_void_p(coverages.ctypes.data)))
         return values, coverages
 
+    def evaluate_robust_pose_deltas(self, moved_views, moved_Ps, loss, delta):
+        """ecc_metric_evaluate_robust_pose_deltas: evaluate_pose_deltas under the per-sample robust loss of evaluate_robust (loss,
+        delta as there).  The same lists; returns (values, inlier_masses), every entry bit-identical to setProjectionMatrices +
+        evaluate_robust(loss, delta) of that pose; the current matrices stay."""
+        return self.evaluate_robust_pose_deltas_packed(*_pack_pose_lists(moved_views, moved_Ps), loss, delta)
+
+    def evaluate_robust_pose_deltas_packed(self, moved_offsets, moved_views, moved_Ps, loss, delta):
+        """The C signature itself, with the arguments of evaluate_pose_deltas_packed, then loss and delta; returns (values,
+        inlier_masses)."""
+        off, views, flat = _check_pose_lists(moved_offsets, moved_views, moved_Ps)
+        values, masses = np.zeros(len(off) - 1, np.float64), np.zeros(len(off) - 1, np.float64)
+        check(_lib.lib().ecc_metric_evaluate_robust_pose_deltas(self._h, len(values), C.c_void_p(off.ctypes.data),
+                                                                C.c_void_p(views.ctypes.data) if len(views) else None,
+                                                                C.c_void_p(flat.ctypes.data) if len(views) else None,
+                                                                int(loss), float(delta),
+                                                                C.c_void_p(values.ctypes.data), C.c_void_p(masses.ctypes.data)))
+        return values, masses
+
     def evaluate_weighted_pairs(self, idx4, want_pairs=False):
         """ecc_metric_evaluate_weighted_pairs: evaluate_weighted over an index list of (P0, P1, D0, D1) tuples -- matrices P*, data
         intermediates D* in [0, n_views); the weights of a sample come from intermediate n_views + D*.  Returns (value, coverage) =
@@ -913,9 +931,32 @@ class MetricRadonIntermediate:
                                                                  C.c_void_p(pairs.ctypes.data) if (want_pairs and pairs.size) else None))
         return (values, coverages, pairs) if want_pairs else (values, coverages)
 
+    def evaluate_robust_transforms(self, n_source, Ts, loss, delta, want_pairs=False):
+        """ecc_metric_evaluate_robust_transforms: evaluate_transforms under the per-sample robust loss of evaluate_robust (loss, delta
+        as there; one intermediate per view).  n_source and Ts as for evaluate_transforms.  Returns (values, inlier_masses) = per
+        transform (sum c, sum u) / (n_source n_target) over the cross pairs -- with want_pairs (values, inlier_masses, pairs), pairs
+        (K, n_target, n_source, 3) float32 rows {c, u, r}: every number bit-identical to setProjectionMatrices(composed) +
+        evaluate_robust_pairs(the cross list, loss, delta) per transform; the current matrices stay."""
+        T = np.asarray(Ts, dtype=np.float64)
+        if T.ndim == 2 and T.shape == (4, 4):
+            T = T[None]
+        if T.ndim != 3 or T.shape[1:] != (4, 4):
+            raise ValueError("Ts must be (K, 4, 4)")
+        flat = np.ascontiguousarray(T.transpose(0, 2, 1)).reshape(-1, 16)  # column-major per transform
+        n_source = int(n_source)
+        K, n = len(flat), self.getNumberOfProjetions()
+        values, masses = np.zeros(K, np.float64), np.zeros(K, np.float64)
+        pairs = np.zeros((K, max(n - n_source, 0), max(n_source, 0), 3), np.float32) if want_pairs else None
+        check(_lib.lib().ecc_metric_evaluate_robust_transforms(self._h, n_source, K, C.c_void_p(flat.ctypes.data if K else 0),
+                                                               int(loss), float(delta),
+                                                               C.c_void_p(values.ctypes.data if K else 0),
+                                                               C.c_void_p(masses.ctypes.data if K else 0),
+                                                               C.c_void_p(pairs.ctypes.data) if (want_pairs and pairs.size) else None))
+        return (values, masses, pairs) if want_pairs else (values, masses)
+
     def last_batched_transforms(self):
-        """Transforms of the last evaluate_transforms / evaluate_weighted_transforms call that went through the batch (0: the
-        sequential way)."""
+        """Transforms of the last evaluate_transforms / evaluate_weighted_transforms / evaluate_robust_transforms call that went
+        through the batch (0: the sequential way)."""
         v = C.c_int64(0)
         check(_lib.lib().ecc_metric_last_batched_transforms(self._h, C.byref(v)))
         return v.value

@@ -999,6 +999,53 @@ public:
                                                               coverages ? coverages->data() : 0x0, pair_terms));
     }
 
+    /// Not in the reference: ecc_metric_evaluate_robust_pose_deltas -- evaluatePoseDeltas under the per-sample robust loss of
+    /// evaluateRobust (loss, delta as there).  values[k] and inlier_masses[k] (inlier_masses nullable) are bit-identical to replacing
+    /// the views moved_views[k] by moved_Ps[k], setProjectionMatrices and evaluateRobust(loss, delta); the current matrices stay.
+    /// Single device only.
+    void evaluateRobustPoseDeltas(const std::vector<std::vector<int> >& moved_views,
+                                  const std::vector<std::vector<Geometry::ProjectionMatrix> >& moved_Ps, int loss, float delta,
+                                  std::vector<double>& values, std::vector<double>* inlier_masses = 0x0)
+    {
+        if (m_gh) throw std::runtime_error("evaluateRobustPoseDeltas: not available on a device group");
+        if (moved_views.size() != moved_Ps.size()) throw std::runtime_error("evaluateRobustPoseDeltas: one matrix list per pose");
+        values.assign(moved_views.size(), 0.0);
+        if (inlier_masses) inlier_masses->assign(moved_views.size(), 0.0);
+        if (moved_views.empty()) return;
+        std::vector<int32_t> off(1, 0), views;
+        std::vector<double> flat;
+        for (size_t k = 0; k < moved_views.size(); ++k) {
+            if (moved_views[k].size() != moved_Ps[k].size()) throw std::runtime_error("evaluateRobustPoseDeltas: one matrix per moved view");
+            for (size_t q = 0; q < moved_views[k].size(); ++q) {
+                views.push_back(moved_views[k][q]);
+                flat.insert(flat.end(), moved_Ps[k][q].data(), moved_Ps[k][q].data() + 12);
+            }
+            off.push_back((int32_t)views.size());
+        }
+        detail::check(ecc_metric_evaluate_robust_pose_deltas(m_h, (int)moved_views.size(), off.data(), views.empty() ? 0x0 : views.data(),
+                                                             flat.empty() ? 0x0 : flat.data(), loss, delta, values.data(),
+                                                             inlier_masses ? inlier_masses->data() : 0x0));
+    }
+
+    /// Not in the reference: ecc_metric_evaluate_robust_transforms -- evaluateTransforms under the per-sample robust loss of
+    /// evaluateRobust (n_source and Ts as for evaluateTransforms).  values[k] = sum c / (n_source n_target) over the cross pairs under
+    /// Ts[k]; inlier_masses (nullable): sum u / (n_source n_target) per transform; pair_terms (nullable): Ts.size() x n_target x
+    /// n_source x 3 floats, per transform its rows {c, u, r} with the source index fast.  Every number is bit-identical to Ps[i] * Ts[k]
+    /// by ecc_host_compose_transform, setProjectionMatrices and evaluateRobustPairs of the cross list per transform; the current
+    /// matrices stay (ecc_hip.h).  Single device only.
+    void evaluateRobustTransforms(int n_source, const std::vector<Geometry::RP3Homography>& Ts, int loss, float delta,
+                                  std::vector<double>& values, std::vector<double>* inlier_masses = 0x0, float* pair_terms = 0x0)
+    {
+        if (m_gh) throw std::runtime_error("evaluateRobustTransforms: not available on a device group");
+        values.assign(Ts.size(), 0.0);
+        if (inlier_masses) inlier_masses->assign(Ts.size(), 0.0);
+        std::vector<double> flat(16 * Ts.size());
+        for (size_t k = 0; k < Ts.size(); ++k)
+            for (int q = 0; q < 16; ++q) flat[16 * k + q] = Ts[k].data()[q];
+        detail::check(ecc_metric_evaluate_robust_transforms(m_h, n_source, (int)Ts.size(), flat.data(), loss, delta, values.data(),
+                                                            inlier_masses ? inlier_masses->data() : 0x0, pair_terms));
+    }
+
     /// Not in the reference: ecc_metric_evaluate_view_hessian -- the quadratic form of the per-view channel coefficients as a matrix:
     /// metric(a) = a^T H a, gradient 2 H a, with the index c * n_views + i of evaluateViewCoefficients' coeffs.  Intermediates as for
     /// evaluateGram.  H: (n_views n_channels)^2, symmetric bit for bit; pair_blocks (nullable): n_pairs x (K (K + 1) + K^2) doubles,

@@ -59,6 +59,14 @@ extern "C" hipError_t ecc_launch_sum_pairs_to_host(const float* vals, long long 
 extern "C" hipError_t ecc_launch_publish_scalar(const double* value_d, double* host_slot_dev, hipStream_t stream);
 extern "C" size_t ecc_sum_scratch_bytes();
 extern "C" hipError_t ecc_launch_pairs_weighted(const EccPairParams* p, const EccWeightedParams* g, hipStream_t stream);
+extern "C" hipError_t ecc_launch_pairs_robust(const EccPairParams* p, const EccRobustParams* g, hipStream_t stream);
+// the segmented sums of columns 0 and 1 of a column-form buffer: per pose over all pairs with the pose's own entries substituted
+// (weighted_poses_kernel.hip), per transform over its cross list (weighted_transforms_kernel.hip)
+extern "C" hipError_t ecc_launch_sum_weighted_poses(const float* base_cols, long long base_stride, long long count, int n, int Q,
+                                                    const int32_t* lists_d, int K, const float* val_cols, long long vals_stride, int slices,
+                                                    double* partial_d, double* out_host_dev, hipStream_t stream);
+extern "C" hipError_t ecc_launch_sum_weighted_transforms(const float* val_cols, long long col_stride, long long count, int K, int slices,
+                                                         double* partial_d, double* out_host_dev, hipStream_t stream);
 extern "C" hipError_t ecc_launch_dilate_max(const float* src, float* dst, int64_t stride, int n_img, int n_u, int n_v, int radius,
                                             hipStream_t stream);
 extern "C" hipError_t ecc_launch_clip_min(const float* lengths, int64_t lengths_stride, float* dst, int64_t dst_stride, int n_img,
@@ -483,6 +491,11 @@ struct ColumnCall;  // (ecc_column_call.h)
 int weighted_check(const ecc_metric* m);
 int weighted_base_columns(ecc_metric* m, ColumnCall* c, EccWeightedParams* g);
 void finish_weighted(double sum_c, double sum_u, int64_t count, double* value, double* coverage);
+// ecc_robust.hip: the argument checks of the robust calls (value: the required result pointer); the launch's loss; {c, u, r} of all
+// pairs at the current matrices into gram_values_d (c, g: the launches as they were made)
+int robust_check(const ecc_metric* m, const double* value, int loss, float delta);
+void fill_robust_params(EccRobustParams* g, float* values, int64_t col_stride, int loss, float delta);
+int robust_base_columns(ecc_metric* m, int loss, float delta, ColumnCall* c, EccRobustParams* g);
 
 // The distance of two channels' row-paired and row-quad copies, for the pair forms that read more than one copy per view (g: any
 // of their parameter structs).
@@ -520,6 +533,12 @@ inline hipError_t launch_pairs_timed(ecc_ctx* ctx, const EccPairParams* p, const
 inline hipError_t launch_weighted_timed(ecc_ctx* ctx, const EccPairParams* p, const EccWeightedParams* g)
 {
     return launch_timed(ctx, [&](hipStream_t s) { return ecc_launch_pairs_weighted(p, g, s); });
+}
+
+// The robust pair launch (robust_kernel.hip) between the same events.
+inline hipError_t launch_robust_timed(ecc_ctx* ctx, const EccPairParams* p, const EccRobustParams* g)
+{
+    return launch_timed(ctx, [&](hipStream_t s) { return ecc_launch_pairs_robust(p, g, s); });
 }
 
 }  // namespace ecc_internal

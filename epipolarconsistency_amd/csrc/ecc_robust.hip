@@ -9,8 +9,10 @@
 // records (scratch of the Gram-family calls alone; column_call_begin, ecc_column_call.h), pairs_robust_kernel, sum_gram_kernel over
 // the columns c and u, the copies (column_call_finish).  The metric's kept records, kept values and pose-batch values are not
 // touched (the list form stages its tuples in the pose batch's index scratch, as ecc_metric_evaluate_weighted_pairs does).
-// Not here: pose-delta, transform, range, group and RCCL forms; the loss combined with line weights on a 2 n metric; the loss under
-// use_corr; Tukey's biweight (not d^2 near zero: no bit link to ecc_metric_evaluate_all).
+// The pose-delta and transform forms are in ecc_robust_batches.hip; they take the checks, the launch parameters and the base's columns
+// from robust_check, fill_robust_params and robust_base_columns below.
+// Not here: range, group and RCCL forms; the loss combined with line weights on a 2 n metric; the loss under use_corr; Tukey's
+// biweight (not d^2 near zero: no bit link to ecc_metric_evaluate_all).
 #include "ecc_column_call.h"
 
 using namespace ecc_internal;
@@ -19,13 +21,12 @@ static_assert(ECC_LOSS_HUBER == ECC_ROBUST_HUBER && ECC_LOSS_TRUNCATED == ECC_RO
                   ECC_LOSS_GEMAN_MCCLURE == ECC_ROBUST_GEMAN_MCCLURE,
               "the kernels' loss codes are the header's");
 
-extern "C" hipError_t ecc_launch_pairs_robust(const EccPairParams* p, const EccRobustParams* g, hipStream_t stream);
-
 namespace {
-
 constexpr int T = 3;  // columns: c, u, r
+}  // namespace
 
-// What both calls need of their arguments and of the metric (after the null check of m), before the device is touched.
+namespace ecc_internal {
+// What every robust call needs of its arguments and of the metric (after the null check of m), before the device is touched.
 int robust_check(const ecc_metric* m, const double* value, int loss, float delta)
 {
     if (!value) return fail(ECC_ERR_INVALID_ARGUMENT, "value is null");
@@ -37,6 +38,32 @@ int robust_check(const ecc_metric* m, const double* value, int loss, float delta
     return ECC_OK;
 }
 
+// The launch's loss: three columns in `values`, col_stride apart; 1 / delta is formed here, on the host, in float64.
+void fill_robust_params(EccRobustParams* g, float* values, int64_t col_stride, int loss, float delta)
+{
+    g->values = values;
+    g->col_stride = col_stride;
+    g->loss = loss;
+    g->delta = delta;
+    g->inv_delta = (float)(1.0 / (double)delta);
+}
+
+// {c, u, r} of all pairs at the current matrices: everything of ecc_metric_evaluate_robust up to and including its pair launch.
+// The three columns are in m->gram_values_d, g->col_stride apart, once the stream gets there; c->p and *g are the launches as they
+// were made (ecc_robust_batches.hip launches the grids of its poses with the same parameters).
+int robust_base_columns(ecc_metric* m, int loss, float delta, ColumnCall* c, EccRobustParams* g)
+{
+    const int64_t n = m->n_views;
+    const int rc = column_call_begin(m, nullptr, n * (n - 1) / 2, T, 2, c);  // the sampling mode of an all-pairs evaluation
+    if (rc) return rc;
+    fill_robust_params(g, m->gram_values_d.ptr, c->col_stride, loss, delta);
+    HIP_TRY(launch_robust_timed(m->ctx, &c->p, g));
+    return ECC_OK;
+}
+}  // namespace ecc_internal
+
+namespace {
+
 // Everything behind the checks: `count` pairs -- all pairs (idx4 null) or the list -- under the sampling mode of that many values.
 int robust_run(ecc_metric* m, const int32_t* idx4, int64_t count, int loss, float delta, double* value, double* inlier_mass, float* pair_terms)
 {
@@ -44,12 +71,8 @@ int robust_run(ecc_metric* m, const int32_t* idx4, int64_t count, int loss, floa
     int rc = column_call_begin(m, idx4, count, T, 2, &c);
     if (rc) return rc;
     EccRobustParams g;
-    g.values = m->gram_values_d.ptr;
-    g.col_stride = c.col_stride;
-    g.loss = loss;
-    g.delta = delta;
-    g.inv_delta = (float)(1.0 / (double)delta);
-    HIP_TRY(launch_timed(m->ctx, [&](hipStream_t s) { return ecc_launch_pairs_robust(&c.p, &g, s); }));  // (robust_kernel.hip)
+    fill_robust_params(&g, m->gram_values_d.ptr, c.col_stride, loss, delta);
+    HIP_TRY(launch_robust_timed(m->ctx, &c.p, &g));  // (robust_kernel.hip)
     double totals[2];  // c and u in the order an evaluation of `count` values is added in (ecc_sum_order.h); r is not summed
     rc = column_call_finish(m, c, 2, totals, T, m->gram_values_d.ptr, pair_terms);
     if (rc) return rc;

@@ -23,10 +23,6 @@
 
 using namespace ecc_internal;
 
-extern "C" hipError_t ecc_launch_sum_weighted_poses(const float* base_cols, long long base_stride, long long count, int n, int Q,
-                                                    const int32_t* lists_d, int K, const float* val_cols, long long vals_stride, int slices,
-                                                    double* partial_d, double* out_host_dev, hipStream_t stream);
-
 namespace {
 
 // poses per batch: the sum's grid is slices x poses x 2 columns, half a million workgroups at most

@@ -24,9 +24,6 @@
 
 using namespace ecc_internal;
 
-extern "C" hipError_t ecc_launch_sum_weighted_transforms(const float* val_cols, long long col_stride, long long count, int K, int slices,
-                                                         double* partial_d, double* out_host_dev, hipStream_t stream);
-
 namespace {
 
 // transforms per batch: they are the y dimension of the sum's grid

@@ -25,8 +25,9 @@
 // kernel arguments and the loss a uniform select (a scalar branch around one division), not a template parameter: three times the
 // instantiations of every loop for the same registers.  Plain vector loads and stores only: no atomics, no inline
 // assembly.
-// Not here (include/ecc_hip.h): pose-delta, transform, range, group and RCCL forms; the loss combined with line weights; the loss
-// under the correlation cost; Tukey's biweight.
+// The pose-delta and transform forms (ecc_robust_batches.hip) launch these kernels over their grids as they stand.
+// Not here (include/ecc_hip.h): range, group and RCCL forms; the loss combined with line weights; the loss under the correlation
+// cost; Tukey's biweight.
 #include <hip/hip_runtime.h>
 #include <float.h>
 

@@ -1,6 +1,8 @@
 // weighted_poses_kernel.hip -- the segmented float64 sums of ecc_metric_evaluate_weighted_pose_deltas (gfx950): per pose the sums of
 // BOTH columns {c, u} over all n (n - 1) / 2 pairs -- the base's column with the pose's own entries substituted -- in the order of
 // ecc_sum_order.h, so that sum c / sum u of a pose has the bits of ecc_metric_set_projections + ecc_metric_evaluate_weighted.
+// Nothing here knows about line weights: the kernel sums columns 0 and 1 of any column-form buffer, and
+// ecc_metric_evaluate_robust_pose_deltas (ecc_robust_batches.hip) uses it for {c, u} of its three columns {c, u, r}.
 //
 // sum_weighted_poses_kernel<SLICES> is sum_poses_kernel (ecc_poses.hip) for column `col` of the base (base + col * base_stride) and
 // column `col` of the grid's values (vals + col * vals_stride): workgroup (slice, pose, column); the slice is staged through LDS in

@@ -1,6 +1,8 @@
 // weighted_transforms_kernel.hip -- the segmented float64 sums of ecc_metric_evaluate_weighted_transforms (gfx950): per transform the
 // sums of BOTH columns {c, u} over its `count` = n_source n_target cross pairs in the order of ecc_sum_order.h, so that
 // sum c / sum u of a transform has the bits of ecc_metric_set_projections(composed matrices) + ecc_metric_evaluate_weighted_pairs.
+// Nothing here knows about line weights: the kernel sums columns 0 and 1 of any column-form buffer, and
+// ecc_metric_evaluate_robust_transforms (ecc_robust_batches.hip) uses it for {c, u} of its three columns {c, u, r}.
 //
 // sum_weighted_transforms_kernel<SLICES>: workgroup (slice, transform, column).  The weighted pair launch has no value slots: it
 // leaves column `col` of grid entry e at val_cols[col * col_stride + e], and the grid is pair-major (ecc_transform_grid.h), so the

@@ -626,7 +626,8 @@ int ecc_metric_evaluate_view_hessian(ecc_metric* m, int n_channels, double* hess
  * The registration of two scans: ecc_metric_evaluate_weighted_transforms below.
  * Out of scope: full-matrices pose batches, range, group and RCCL forms; weights under use_corr; a
  * 1 / (sigma0^2 + sigma1^2) variance form.  A per-sample robust loss, for callers who do not know where the bad lines are:
- * ecc_metric_evaluate_robust below (on a metric of n_views intermediates; not combined with line weights). */
+ * ecc_metric_evaluate_robust and its pose-delta and transform forms below (on a metric of n_views intermediates; not combined with
+ * line weights). */
 int ecc_metric_evaluate_weighted(ecc_metric* m, double* value, double* coverage, float* pair_terms);
 
 /* The weighted metric for pose optimisers (csrc/ecc_weighted_poses.hip): a tracker that scores one frame against
@@ -792,13 +793,62 @@ int ecc_metric_evaluate_weighted_transforms(ecc_metric* m, int n_source, int n_t
  *     call: fewer intermediates than views); a bad tuple.  ECC_ERR_UNSUPPORTED under use_corr.
  * Launches: the record kernel over all pairs or the list, pairs_robust_kernel -- one wave per pair, the position arithmetic of a
  * kappa step once, 4 gathers --, one launch for the sums of c and u (r is not summed), the copies.
- * Not built: pose-delta, transform, range, group and RCCL forms; the loss combined with line weights on a 2 n metric; the loss under
- * use_corr; Tukey's biweight (not d^2 near zero, so no bit link to ecc_metric_evaluate_all). */
+ * Pose deltas and transforms per call: ecc_metric_evaluate_robust_pose_deltas, ecc_metric_evaluate_robust_transforms below.
+ * Not built: range, group and RCCL forms; the loss combined with line weights on a 2 n metric; the loss under use_corr; Tukey's
+ * biweight (not d^2 near zero, so no bit link to ecc_metric_evaluate_all). */
 enum { ECC_LOSS_HUBER = 0, ECC_LOSS_TRUNCATED = 1, ECC_LOSS_GEMAN_MCCLURE = 2 };
 int ecc_metric_evaluate_robust(ecc_metric* m, int loss, float delta, double* value, double* inlier_mass, float* pair_terms);
 int ecc_metric_evaluate_robust_pairs(ecc_metric* m, const int32_t* idx4, int n_pairs, int loss, float delta, double* value,
                                      double* inlier_mass, float* pair_terms);
 double ecc_host_robust_scale(const float* pair_terms, int64_t n_pairs, double k);
+
+/* The robust loss for optimisers (csrc/ecc_robust_batches.hip): a population of poses or of source-to-target
+ * transforms per call, as ecc_metric_evaluate_pose_deltas / ecc_metric_evaluate_transforms take them for the plain metric and the
+ * weighted siblings for line weights.  The losses, delta, the three float32 columns {c, u, r} per pair and the value convention are
+ * exactly those of ecc_metric_evaluate_robust: a value is the mean of c over the pairs, never divided by the inlier mass.
+ *
+ * ecc_metric_evaluate_robust_pose_deltas: the lists of ecc_metric_evaluate_pose_deltas -- pose k = the CURRENT matrices with the
+ * views moved_views[moved_offsets[k] .. moved_offsets[k + 1]) (strictly ascending) replaced by moved_Ps[12 q ..]; n_poses < 1:
+ * ECC_OK.  values[k] and inlier_masses[k] (inlier_masses nullable) have THE BITS of ecc_metric_set_projections(pose k) +
+ * ecc_metric_evaluate_robust(loss, delta) (tests/test_gpu_robust_poses.py).  The call runs in four steps:
+ *   1. once per call, the base columns {c, u} (and r) of all pairs at the current matrices: the launches of
+ *      ecc_metric_evaluate_robust, recomputed on every call -- kept base columns are not built;
+ *   2. per batch, ONE launch that lists the pairs and does E1 of the extended matrices, and ONE record launch over the n x Q grid;
+ *   3. per batch, ONE robust pair launch over that grid under the sampling mode (and wave split) of an all-pairs evaluation;
+ *   4. per batch, ONE segmented float64 sum per pose of columns c and u, the base's values with the pose's own entries substituted,
+ *      in the order of csrc/ecc_sum_order.h.
+ * A pose with more than ECC_POSE_BATCH_MAX_MOVED (32) moved views, one that moves view 0 under the automatic object radius and changes
+ * it, and every pose after ecc_metric_set_pose_batching(m, 0) is evaluated the sequential way inside the call (same bits);
+ * ecc_metric_last_batched_poses reports how many went through the batch.  Calls of more than 2^20 grid entries are cut into batches
+ * over the same base columns.
+ *
+ * ecc_metric_evaluate_robust_transforms: views, transforms, the cross list (entry q = j * n_source + i is the tuple
+ * (i, n_source + j, i, n_source + j)) and the batching are those of ecc_metric_evaluate_transforms; count = n_source * n_target.
+ *   values[k] (required): sum c / count over the list of transform k;  inlier_masses[k] (nullable): sum u / count.
+ *   pair_terms (host, nullable): n_transforms x n_target x n_source x 3 float32, per transform its count rows {c, u, r} in list order.
+ * All three have THE BITS of ecc_metric_set_projections(the composed matrices) + ecc_metric_evaluate_robust_pairs(that list, loss,
+ * delta) (tests/test_gpu_robust_transforms.py).  So the sampling mode resolves from a list of count tuples, and under the automatic
+ * object radius every transform takes the radius of its composed view 0.  Per batch: ecc_metric_evaluate_transforms' list launch and
+ * record launch, ONE robust pair launch over the pair-major grid, ONE segmented sum of columns c and u.  A transform whose list
+ * alone exceeds a batch, and every transform after ecc_metric_set_pose_batching(m, 0), is evaluated the sequential way inside the call
+ * (same bits); ecc_metric_last_batched_transforms counts the batched ones.  Needs at least one Radon intermediate per view and
+ * 1 <= n_source < n_views.  n_transforms == 0 (after the checks): ECC_OK, nothing written.
+ *
+ * Both: with delta = +infinity (or FLT_MAX) values has the bits of ecc_metric_evaluate_pose_deltas / ecc_metric_evaluate_transforms
+ * on the same metric, and every inlier mass is 1.0.  The calls leave the metric as they found it: current matrices, kept records,
+ * the kept values of the pose-delta mode and of the pose batch.  (They rewrite the pose batch's per-batch scratch and
+ * ecc_metric_evaluate_gram's scratch, as their weighted siblings do.)
+ * Errors are returned before anything is launched or written, checked in this order: (1) m == NULL: ECC_ERR_INVALID_ARGUMENT;
+ * (2) null or negative arguments as in the weighted siblings (moved_offsets / values; Ts / values with n_transforms > 0;
+ * n_transforms < 0; the list arrays when moved_offsets[n_poses] > 0); (3) loss outside 0..2, delta NaN or <= 0, no matrices set or
+ * fewer than two views, fewer intermediates than views: ECC_ERR_INVALID_ARGUMENT -- use_corr: ECC_ERR_UNSUPPORTED; (4) a bad list,
+ * n_source outside [1, n_views).
+ * Not built: kept base columns; the full-matrices and strided pose forms; range, group and RCCL forms; the loss combined with line
+ * weights; the loss under use_corr. */
+int ecc_metric_evaluate_robust_pose_deltas(ecc_metric* m, int n_poses, const int32_t* moved_offsets, const int32_t* moved_views,
+                                           const double* moved_Ps, int loss, float delta, double* values, double* inlier_masses);
+int ecc_metric_evaluate_robust_transforms(ecc_metric* m, int n_source, int n_transforms, const double* Ts, int loss, float delta,
+                                          double* values, double* inlier_masses, float* pair_terms);
 
 /* Multi-GPU building block: evaluate only pairs ij in [first, first+count) of the get_ij order
  * (ref: EpipolarConsistencyCommon.hxx:52-79); returns the partial sum (float64) -- the caller
