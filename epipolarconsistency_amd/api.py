@@ -885,6 +885,40 @@ class MetricRadonIntermediate:
                                                           C.c_void_p(pairs.ctypes.data) if (want_pairs and pairs.size) else None))
         return (value.value, mass.value, pairs) if want_pairs else (value.value, mass.value)
 
+    def evaluate_weighted_robust(self, loss, delta, want_pairs=False):
+        """ecc_metric_evaluate_weighted_robust: line weights and the robust loss together, for scans that have both kinds of bad
+        data -- lines somebody flagged (line_weights) and an instrument nobody did.  The metric holds 2 * n_views Radon
+        intermediates as for evaluate_weighted; loss and delta as for evaluate_robust.  Per sample f = mu * w(d): mu the product of
+        the two line weights, w the IRLS weight of the raw residual d.  Returns (value, coverage, inlier_mass): value = sum c /
+        sum u (normalised by the coverage, never by the mass the loss keeps), coverage = sum u / n_pairs, inlier_mass = sum k / sum u
+        -- with want_pairs (value, coverage, inlier_mass, pairs), pairs (n_pairs, 4) float32 in the pair order of evaluate(cost):
+        per pair c, its value, u, its coverage, k, the weight mass the loss keeps, and r, the weighted mean squared raw residual
+        (weighted_robust_scale takes delta from r / u).  delta = inf: the bits of evaluate_weighted; all weights 1: the bits of
+        evaluate_robust.  The current matrices and everything the metric keeps stay."""
+        n = 0 if self._Ps is None else len(self._Ps)  # (no matrices: the library reports it)
+        value, coverage, mass = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
+        pairs = np.zeros((n * (n - 1) // 2, 4), np.float32) if want_pairs else None
+        check(_lib.lib().ecc_metric_evaluate_weighted_robust(self._h, int(loss), float(delta), C.byref(value), C.byref(coverage), C.byref(mass),
+                                                             C.c_void_p(pairs.ctypes.data) if (want_pairs and pairs.size) else None))
+        return (value.value, coverage.value, mass.value, pairs) if want_pairs else (value.value, coverage.value, mass.value)
+
+    def evaluate_weighted_robust_pairs(self, idx4, loss, delta, want_pairs=False):
+        """ecc_metric_evaluate_weighted_robust_pairs: evaluate_weighted_robust over an index list of (P0, P1, D0, D1) tuples as
+        evaluate_weighted_pairs takes them: D0, D1 index the data intermediates, in [0, n_views), and the weight follows the data
+        index.  Returns (value, coverage, inlier_mass) over the list -- with want_pairs also pairs (n_pairs, 4) float32 rows
+        {c, u, k, r} in list order.  The sampling mode resolves from the list's length; an empty list writes nothing
+        (0.0, 0.0, 0.0)."""
+        idx = np.ascontiguousarray(idx4, np.int32)
+        if idx.size % 4 or (idx.ndim == 2 and idx.shape[1] != 4) or idx.ndim > 2:
+            raise ValueError("idx4 must hold (P0, P1, D0, D1) tuples")
+        idx = idx.reshape(-1, 4)
+        value, coverage, mass = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
+        pairs = np.zeros((len(idx), 4), np.float32) if want_pairs else None
+        check(_lib.lib().ecc_metric_evaluate_weighted_robust_pairs(self._h, C.c_void_p(idx.ctypes.data) if len(idx) else None, len(idx),
+                                                                   int(loss), float(delta), C.byref(value), C.byref(coverage), C.byref(mass),
+                                                                   C.c_void_p(pairs.ctypes.data) if (want_pairs and pairs.size) else None))
+        return (value.value, coverage.value, mass.value, pairs) if want_pairs else (value.value, coverage.value, mass.value)
+
     def evaluate_transforms(self, n_source, Ts, want_pairs=False):
         """ecc_metric_evaluate_transforms: the registration of two scans (ref: tools/Registration/Registration3D3D.hxx).  The
         current matrices are the base, views [0, n_source) the source scan, the rest the target scan; Ts: anything np.asarray
@@ -1549,6 +1583,16 @@ def robust_scale(pair_terms, k=1.0):
     if rows.ndim != 2 or rows.shape[1] != 3:
         raise ValueError("pair_terms must be (n_pairs, 3) rows {c, u, r}")
     return float(_lib.lib().ecc_host_robust_scale(C.c_void_p(rows.ctypes.data) if len(rows) else None, len(rows), float(k)))
+
+
+def weighted_robust_scale(pair_terms, k=1.0):
+    """ecc_host_weighted_robust_scale: a scale delta for evaluate_weighted_robust from the pair rows {c, u, k, r} of an earlier call
+    (normally the one with delta = inf) -- k x the median over the pairs with r > 0 and u > 0 of sqrt(r / u), the pair's rms residual
+    over the lines its weights trust; 0.0 without such a pair.  With every u == 1 it is robust_scale of the rows {c, k, r}."""
+    rows = np.ascontiguousarray(pair_terms, np.float32)
+    if rows.ndim != 2 or rows.shape[1] != 4:
+        raise ValueError("pair_terms must be (n_pairs, 4) rows {c, u, k, r}")
+    return float(_lib.lib().ecc_host_weighted_robust_scale(C.c_void_p(rows.ctypes.data) if len(rows) else None, len(rows), float(k)))
 
 
 def _line_weights_config(zero_at_px, guard_bins, dilate_px):

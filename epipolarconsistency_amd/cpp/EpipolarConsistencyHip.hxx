@@ -953,6 +953,63 @@ public:
         return ecc_host_robust_scale(pair_terms.empty() ? 0x0 : pair_terms.data(), (int64_t)(pair_terms.size() / 3), k);
     }
 
+    /// Not in the reference: ecc_metric_evaluate_weighted_robust -- line weights and the robust loss together, for scans with lines
+    /// somebody flagged and an instrument nobody did.  Intermediates as for evaluateWeighted (2 * n_views: data, then line weights),
+    /// loss and delta as for evaluateRobust; per sample the factor is mu * w(d), w of the raw residual.  Returns sum c / sum u
+    /// (normalised by the coverage, never by the mass the loss keeps); coverage (nullable): sum u / n_pairs; inlier_mass (nullable):
+    /// sum k / sum u; pair_terms (nullable): n_pairs x 4 floats, pair-major, per pair i < j {c, u, k, r} (ecc_hip.h;
+    /// weightedRobustScale takes delta from r / u).  Single device only.
+    double evaluateWeightedRobust(int loss, float delta, double* coverage = 0x0, double* inlier_mass = 0x0,
+                                  std::vector<float>* pair_terms = 0x0)
+    {
+        if (m_gh) throw std::runtime_error("evaluateWeightedRobust: not available on a device group");
+        const size_t n = Ps.size();
+        if (pair_terms) pair_terms->assign(4 * (n * (n > 0 ? n - 1 : 0) / 2), 0.f);
+        double value = 0.0;
+        detail::check(ecc_metric_evaluate_weighted_robust(m_h, loss, delta, &value, coverage, inlier_mass,
+                                                          (pair_terms && !pair_terms->empty()) ? pair_terms->data() : 0x0));
+        return value;
+    }
+
+    /// Not in the reference: ecc_metric_evaluate_weighted_robust_pairs -- evaluateWeightedRobust over an index list of
+    /// (P0, P1, D0, D1) tuples as evaluateWeightedPairs takes them (4 ints per tuple; D0, D1 in [0, n_views), the weight follows the
+    /// data index).  Returns sum c / sum u over the list; coverage, inlier_mass (nullable) as there; pair_terms (nullable): n_pairs x 4
+    /// floats {c, u, k, r} in list order.  The sampling mode resolves from the list's length (ecc_hip.h).  Single device only.
+    double evaluateWeightedRobustPairs(const std::vector<int>& indices, int loss, float delta, double* coverage = 0x0,
+                                       double* inlier_mass = 0x0, std::vector<float>* pair_terms = 0x0)
+    {
+        if (m_gh) throw std::runtime_error("evaluateWeightedRobustPairs: not available on a device group");
+        if (indices.size() % 4) throw std::runtime_error("evaluateWeightedRobustPairs: four indices per tuple");
+        const std::vector<int32_t> idx(indices.begin(), indices.end());
+        if (pair_terms) pair_terms->assign(idx.size(), 0.f);
+        double value = 0.0;
+        if (coverage) *coverage = 0.0;
+        if (inlier_mass) *inlier_mass = 0.0;
+        detail::check(ecc_metric_evaluate_weighted_robust_pairs(m_h, idx.empty() ? 0x0 : idx.data(), (int)(idx.size() / 4), loss, delta,
+                                                                &value, coverage, inlier_mass,
+                                                                (pair_terms && !pair_terms->empty()) ? pair_terms->data() : 0x0));
+        return value;
+    }
+#ifdef ECC_ADAPTER_HAVE_EIGEN
+    double evaluateWeightedRobustPairs(const std::vector<Eigen::Vector4i>& indices, int loss, float delta, double* coverage = 0x0,
+                                       double* inlier_mass = 0x0, std::vector<float>* pair_terms = 0x0)
+    {
+        std::vector<int> idx(4 * indices.size());
+        for (size_t i = 0; i < indices.size(); ++i)
+            for (int k = 0; k < 4; ++k) idx[4 * i + k] = indices[i][k];
+        return evaluateWeightedRobustPairs(idx, loss, delta, coverage, inlier_mass, pair_terms);
+    }
+#endif
+
+    /// ecc_host_weighted_robust_scale: a scale delta for evaluateWeightedRobust from the rows {c, u, k, r} of an earlier call
+    /// (normally the one with delta = infinity): k x the median over the pairs with r > 0 and u > 0 of sqrt(r / u); 0.0 without such
+    /// a pair.  Touches no device.
+    static double weightedRobustScale(const std::vector<float>& pair_terms, double k = 1.0)
+    {
+        if (pair_terms.size() % 4) throw std::runtime_error("weightedRobustScale: four floats per pair");
+        return ecc_host_weighted_robust_scale(pair_terms.empty() ? 0x0 : pair_terms.data(), (int64_t)(pair_terms.size() / 4), k);
+    }
+
     /// Not in the reference: ecc_metric_evaluate_weighted_pose_deltas -- evaluatePoseDeltas for the metric with per-line weights
     /// (intermediates as for evaluateWeighted).  values[k] and coverages[k] (coverages nullable) are bit-identical to replacing the
     /// views moved_views[k] by moved_Ps[k], setProjectionMatrices and evaluateWeighted(); the current matrices stay.  Single device only.

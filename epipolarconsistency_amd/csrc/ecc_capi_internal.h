@@ -60,6 +60,7 @@ extern "C" hipError_t ecc_launch_publish_scalar(const double* value_d, double* h
 extern "C" size_t ecc_sum_scratch_bytes();
 extern "C" hipError_t ecc_launch_pairs_weighted(const EccPairParams* p, const EccWeightedParams* g, hipStream_t stream);
 extern "C" hipError_t ecc_launch_pairs_robust(const EccPairParams* p, const EccRobustParams* g, hipStream_t stream);
+extern "C" hipError_t ecc_launch_pairs_weighted_robust(const EccPairParams* p, const EccWeightedRobustParams* g, hipStream_t stream);
 // the segmented sums of columns 0 and 1 of a column-form buffer: per pose over all pairs with the pose's own entries substituted
 // (weighted_poses_kernel.hip), per transform over its cross list (weighted_transforms_kernel.hip)
 extern "C" hipError_t ecc_launch_sum_weighted_poses(const float* base_cols, long long base_stride, long long count, int n, int Q,
@@ -539,6 +540,12 @@ inline hipError_t launch_weighted_timed(ecc_ctx* ctx, const EccPairParams* p, co
 inline hipError_t launch_robust_timed(ecc_ctx* ctx, const EccPairParams* p, const EccRobustParams* g)
 {
     return launch_timed(ctx, [&](hipStream_t s) { return ecc_launch_pairs_robust(p, g, s); });
+}
+
+// The weighted robust pair launch (weighted_robust_kernel.hip) between the same events.
+inline hipError_t launch_weighted_robust_timed(ecc_ctx* ctx, const EccPairParams* p, const EccWeightedRobustParams* g)
+{
+    return launch_timed(ctx, [&](hipStream_t s) { return ecc_launch_pairs_weighted_robust(p, g, s); });
 }
 
 }  // namespace ecc_internal

@@ -286,6 +286,20 @@ struct EccRobustParams {
     float inv_delta;               // (float)(1.0 / (double)delta), formed on the host
 };
 
+// ---- line weights and the robust loss together (weighted_robust_kernel.hip) -------------------------------
+// 2 n_views channel-major intermediates and copies as for EccWeightedParams.  Four float32 entries per pair -- the value c, the
+// coverage u, the weight mass the loss keeps k and the weighted mean squared raw residual r -- stored COLUMN-major with the Gram
+// form's col_stride rule.
+struct EccWeightedRobustParams {
+    int64_t paired_channel_bytes;  // as in EccGramParams
+    int64_t quad_channel_bytes;
+    float* values;                 // 4 columns of col_stride floats
+    int64_t col_stride;
+    int loss;                      // ECC_ROBUST_*, launch-uniform
+    float delta;                   // the scale, > 0; +infinity: no sample is down-weighted
+    float inv_delta;               // (float)(1.0 / (double)delta), formed on the host
+};
+
 // ---- projection pre-processing ------------------------------------------------
 #define ECC_PRE_MAX_CHUNKS 32  // workgroups per image of the maximum search in front of PreProccess::process (normalize)
 struct EccPreprocessParams {

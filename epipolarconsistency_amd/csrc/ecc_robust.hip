@@ -11,8 +11,9 @@
 // touched (the list form stages its tuples in the pose batch's index scratch, as ecc_metric_evaluate_weighted_pairs does).
 // The pose-delta and transform forms are in ecc_robust_batches.hip; they take the checks, the launch parameters and the base's columns
 // from robust_check, fill_robust_params and robust_base_columns below.
-// Not here: range, group and RCCL forms; the loss combined with line weights on a 2 n metric; the loss under use_corr; Tukey's
-// biweight (not d^2 near zero: no bit link to ecc_metric_evaluate_all).
+// The loss combined with line weights on a 2 n metric is ecc_weighted_robust.hip; it takes robust_check from here.
+// Not here: range, group and RCCL forms; the loss under use_corr; Tukey's biweight (not d^2 near zero: no bit link to
+// ecc_metric_evaluate_all).
 #include "ecc_column_call.h"
 
 using namespace ecc_internal;

@@ -21,8 +21,8 @@
 //   host           values[k] = sum c / count, inlier_masses[k] = sum u / count
 // Every result has the bits of the sequential calls (tests/test_gpu_robust_poses.py, tests/test_gpu_robust_transforms.py); what a
 // batch does not take is evaluated that way inside the call.
-// Not here: base columns kept between calls; the full-matrices and strided pose forms; range, group and RCCL forms; the loss
-// combined with line weights; the loss under use_corr.
+// Not here: base columns kept between calls; the full-matrices and strided pose forms; range, group and RCCL forms; these batches
+// for the loss combined with line weights (ecc_weighted_robust.hip has its all-pairs and list forms); the loss under use_corr.
 #include "ecc_column_call.h"
 #include "ecc_pose_batches.h"
 #include "ecc_transform_grid.h"

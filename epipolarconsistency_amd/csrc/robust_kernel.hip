@@ -26,36 +26,22 @@
 // instantiations of every loop for the same registers.  Plain vector loads and stores only: no atomics, no inline
 // assembly.
 // The pose-delta and transform forms (ecc_robust_batches.hip) launch these kernels over their grids as they stand.
-// Not here (include/ecc_hip.h): range, group and RCCL forms; the loss combined with line weights; the loss under the correlation
-// cost; Tukey's biweight.
+// The loss combined with line weights on a 2 n metric is weighted_robust_kernel.hip.
+// Not here (include/ecc_hip.h): range, group and RCCL forms; the loss under the correlation cost; Tukey's biweight.
 #include <hip/hip_runtime.h>
 #include <float.h>
 
 #include "ecc_layout.h"
 #include "ecc_pair_forms.h"
+#include "ecc_robust_weight.h"
 
 namespace {
 
 // the four per-lane sums: the value, the weight mass, the raw squares, the sample count
 enum { VALUE, MASS, RAW, COUNT, ROBUST_SUMS };
 
-// the launch-uniform part of the loss
-struct RobustLoss {
-    int loss;
-    float delta, inv_delta;
-};
-
-// w(d): the IRLS weight of a residual (see the head of this file; `loss` is wave-uniform, the branch a scalar one)
-__device__ __forceinline__ float robust_weight(const RobustLoss& L, float d)
-{
-    const float a = fabsf(d);
-    if (L.loss == ECC_ROBUST_GEMAN_MCCLURE) {
-        const float s = a * L.inv_delta;
-        return 1.0f / fmaf(s, s, 1.0f);
-    }
-    const float t = fminf(1.0f, L.delta / a);
-    return L.loss == ECC_ROBUST_HUBER ? t * (2.0f - t) : t * t;
-}
+// (RobustLoss, the launch-uniform part of the loss, and robust_weight, w(d), are in ecc_robust_weight.h: weighted_robust_kernel.hip
+// takes the same ones)
 
 // the trips of the three loop kinds (ecc_pair_forms.h): 4 gathers, the residuals of the + and the - sample, their weights, the sums
 struct RobustForm : PairFormDefaults {

@@ -22,7 +22,8 @@
 // stores only: no atomics, no inline assembly.
 // Index lists and pose deltas launch these kernels over their own records (ecc_weighted_poses.hip).
 // Not here (include/ecc_hip.h): full-matrices pose batches, transform, range, group and RCCL forms; weights under the correlation
-// cost; a 1 / (sigma0^2 + sigma1^2) variance form.  A per-sample robust loss is robust_kernel.hip (not combined with these weights).
+// cost; a 1 / (sigma0^2 + sigma1^2) variance form.  A per-sample robust loss is robust_kernel.hip; the loss combined with these weights is
+// weighted_robust_kernel.hip.
 #include <hip/hip_runtime.h>
 #include <float.h>
 

@@ -626,8 +626,8 @@ int ecc_metric_evaluate_view_hessian(ecc_metric* m, int n_channels, double* hess
  * The registration of two scans: ecc_metric_evaluate_weighted_transforms below.
  * Out of scope: full-matrices pose batches, range, group and RCCL forms; weights under use_corr; a
  * 1 / (sigma0^2 + sigma1^2) variance form.  A per-sample robust loss, for callers who do not know where the bad lines are:
- * ecc_metric_evaluate_robust and its pose-delta and transform forms below (on a metric of n_views intermediates; not combined with
- * line weights). */
+ * ecc_metric_evaluate_robust and its pose-delta and transform forms below (on a metric of n_views intermediates); the loss combined
+ * with these weights: ecc_metric_evaluate_weighted_robust below. */
 int ecc_metric_evaluate_weighted(ecc_metric* m, double* value, double* coverage, float* pair_terms);
 
 /* The weighted metric for pose optimisers (csrc/ecc_weighted_poses.hip): a tracker that scores one frame against
@@ -794,8 +794,9 @@ int ecc_metric_evaluate_weighted_transforms(ecc_metric* m, int n_source, int n_t
  * Launches: the record kernel over all pairs or the list, pairs_robust_kernel -- one wave per pair, the position arithmetic of a
  * kappa step once, 4 gathers --, one launch for the sums of c and u (r is not summed), the copies.
  * Pose deltas and transforms per call: ecc_metric_evaluate_robust_pose_deltas, ecc_metric_evaluate_robust_transforms below.
- * Not built: range, group and RCCL forms; the loss combined with line weights on a 2 n metric; the loss under use_corr; Tukey's
- * biweight (not d^2 near zero, so no bit link to ecc_metric_evaluate_all). */
+ * The loss combined with line weights on a 2 n metric: ecc_metric_evaluate_weighted_robust below.
+ * Not built: range, group and RCCL forms; the loss under use_corr; Tukey's biweight (not d^2 near zero, so no bit link to
+ * ecc_metric_evaluate_all). */
 enum { ECC_LOSS_HUBER = 0, ECC_LOSS_TRUNCATED = 1, ECC_LOSS_GEMAN_MCCLURE = 2 };
 int ecc_metric_evaluate_robust(ecc_metric* m, int loss, float delta, double* value, double* inlier_mass, float* pair_terms);
 int ecc_metric_evaluate_robust_pairs(ecc_metric* m, const int32_t* idx4, int n_pairs, int loss, float delta, double* value,
@@ -843,12 +844,84 @@ double ecc_host_robust_scale(const float* pair_terms, int64_t n_pairs, double k)
  * n_transforms < 0; the list arrays when moved_offsets[n_poses] > 0); (3) loss outside 0..2, delta NaN or <= 0, no matrices set or
  * fewer than two views, fewer intermediates than views: ECC_ERR_INVALID_ARGUMENT -- use_corr: ECC_ERR_UNSUPPORTED; (4) a bad list,
  * n_source outside [1, n_views).
- * Not built: kept base columns; the full-matrices and strided pose forms; range, group and RCCL forms; the loss combined with line
- * weights; the loss under use_corr. */
+ * Not built: kept base columns; the full-matrices and strided pose forms; range, group and RCCL forms; pose-delta and transform
+ * batches of the loss combined with line weights (ecc_metric_evaluate_weighted_robust below has the all-pairs and list forms); the
+ * loss under use_corr. */
 int ecc_metric_evaluate_robust_pose_deltas(ecc_metric* m, int n_poses, const int32_t* moved_offsets, const int32_t* moved_views,
                                            const double* moved_Ps, int loss, float delta, double* values, double* inlier_masses);
 int ecc_metric_evaluate_robust_transforms(ecc_metric* m, int n_source, int n_transforms, const double* Ts, int loss, float delta,
                                           double* values, double* inlier_masses, float* pair_terms);
+
+/* LINE WEIGHTS AND THE ROBUST LOSS TOGETHER (csrc/ecc_weighted_robust.hip, csrc/weighted_robust_kernel.hip): real
+ * scans have both kinds of bad data at once -- a fluoroscopy sequence has collimator blades, known and flagged once per view
+ * (ecc_radon_line_weights), and a catheter nobody flagged.  ecc_metric_evaluate_weighted alone leaves the instrument in;
+ * ecc_metric_evaluate_robust alone spends its scale on lines whose badness was known in advance, reports an inlier mass that mixes
+ * the two causes, and on a 2 n metric would take the weights for data.
+ *
+ * The metric is ecc_metric_evaluate_weighted's: n_dtrs == 2 * n_views, the data of every view, then its line weights.  For a pair a
+ * +-kappa sample has the positions, kappa range and sampling mode of ecc_metric_evaluate_all; d is that evaluation's difference of the
+ * two signed data samples.  loss, delta and inv_delta are ecc_metric_evaluate_robust's.  Per sample, every operation one float32
+ * operation:
+ *     mu = W_i(sample) * W_j(sample)      as in ecc_metric_evaluate_weighted: unsigned taps of the weight intermediates
+ *     w  = the IRLS weight of ecc_metric_evaluate_robust's table, of the RAW residual d -- a line weight says how far a line is
+ *          trusted, it does not rescale its residual
+ *     f  = mu * w
+ * Per kappa step the value term is the weighted call's expression with f in place of mu --
+ *     polynomial loops             fmaf(f_p * dp, dp, (f_m * dm) * dm) * w06_dkappa
+ *     exact and reference loops    (((f_p * dp) * dp + (f_m * dm) * dm) * K0[6]) * dkappa
+ * -- accumulated in float64 per lane in the same trip order and reduced by the same wave tree.  Beside it each lane adds
+ * (double)(mu_p + mu_m), the weight mass, (double)(f_p + f_m), the mass the loss keeps, (double)(mu_p * (dp * dp)) +
+ * (double)(mu_m * (dm * dm)), the weighted raw squares (products in float32), and 2.0, the sample count.  Per pair q, four float32
+ * columns:
+ *     c_q = the value,
+ *     u_q = (float)(mass / count), the COVERAGE of ecc_metric_evaluate_weighted,
+ *     k_q = (float)(kept / count), the weight mass the loss keeps; k_q <= u_q for weights >= 0,
+ *     r_q = (float)(raw / count), the weighted mean squared raw residual, independent of loss and delta;
+ *     a pair without samples, or a list tuple with P0 == P1, has {0, 1, 1, 0}.
+ *   value (required): sum c_q / sum u_q, the sums in the order of csrc/ecc_sum_order.h.  Normalised by the line-weight coverage, as
+ *     the weighted call does and for its reason; NEVER divided by the mass the loss keeps, as the robust call refuses to and for its
+ *     reason.
+ *   coverage (nullable): sum u_q / n_pairs.
+ *   inlier_mass (nullable): sum k_q / sum u_q, the mean IRLS weight among the lines that are trusted at all.
+ *   sum u_q == 0: all three are 0.0 and ECC_OK.
+ *   pair_terms (host, nullable): n_pairs x 4 float32, pair-major, rows {c_q, u_q, k_q, r_q}; get_ij order (all pairs), list order
+ *     (list).
+ * ecc_metric_evaluate_weighted_robust: all pairs over the current matrices; the sampling mode resolves from n (n - 1) / 2.
+ * ecc_metric_evaluate_weighted_robust_pairs: (P0, P1, D0, D1) tuples exactly as ecc_metric_evaluate_weighted_pairs takes them: D*
+ * must lie in [0, n_views), the weight follows the data index, the mode resolves from the list's length; n_pairs == 0: ECC_OK,
+ * nothing written.
+ *
+ * ecc_host_weighted_robust_scale: k x the median of sqrt((double)r_q / (double)u_q) over the rows with r_q > 0 and u_q > 0 (even
+ * count: the mean of the two middle values); no such row: 0.0.  Touches no device.  The intended use: one call with delta = INFINITY
+ * -- which is also ecc_metric_evaluate_weighted's value --, then delta = ecc_host_weighted_robust_scale(terms, n_pairs, k).  With
+ * every u_q == 1.0f it is ecc_host_robust_scale of the rows {c, k, r}, to the bit.
+ *
+ * The contract (tests/test_gpu_weighted_robust.py), three bit links that hold by construction:
+ *   1. delta = +infinity or FLT_MAX (every w == 1.0f, f == mu): {c, u}, value and coverage have the bits of
+ *      ecc_metric_evaluate_weighted, k_q has the bits of u_q, inlier_mass == 1.0.
+ *   2. Every weight 1.0f (f == w): {c, k, r}, value and inlier_mass have the bits of ecc_metric_evaluate_robust's {c, u, r}, value
+ *      and inlier_mass on the n_views metric over the same data; u_q == 1.0 and coverage == 1.0.
+ *   3. Both: the bits of ecc_metric_evaluate_all.
+ *   4. {c, u, k, r} agree with a float64 oracle (tests/weighted_robust_terms.py) to the project's bars.
+ *   5. With W_v = 0 for one view the pairs with v are {0, 0, 0, 0}; data that differ only on lines of weight 0 give the same bits
+ *      (f = 0 * w with w finite for all three losses; the differing data must keep d * d finite for r).
+ *   - The calls change nothing a later call can see: current matrices, kept records, the kept values of the pose-delta mode and of
+ *     the pose batch.  (They share ecc_metric_evaluate_gram's scratch; the list form stages its tuples in the pose batch's index
+ *     scratch.)
+ *   - Errors before anything is launched or written, checked in this order: (1) m == NULL: ECC_ERR_INVALID_ARGUMENT; (2) the list
+ *     form: n_pairs < 0, idx4 == NULL with n_pairs > 0: ECC_ERR_INVALID_ARGUMENT; (3) ecc_metric_evaluate_robust's conditions in its
+ *     order -- value == NULL, loss outside 0..2, delta NaN or <= 0 (+infinity is allowed), no matrices set, fewer than two views:
+ *     ECC_ERR_INVALID_ARGUMENT, then use_corr: ECC_ERR_UNSUPPORTED; (4) n_dtrs != 2 * n_views: ECC_ERR_INVALID_ARGUMENT; (5) the list
+ *     form: a tuple with an index outside [0, n_views): ECC_ERR_INVALID_ARGUMENT.  After them n_pairs == 0 is ECC_OK.
+ * Launches: the record kernel over all pairs or the list, pairs_weighted_robust_kernel -- one wave per pair, the position arithmetic
+ * of a kappa step once, 8 gathers --, one launch for the sums of c, u and k (r is not summed), the copies.
+ * Not built: the pose-delta and transform batches of this form (they need no kernel beyond this one); range, group and RCCL forms;
+ * use_corr; Tukey's biweight; a 1 / (sigma0^2 + sigma1^2) variance form. */
+int ecc_metric_evaluate_weighted_robust(ecc_metric* m, int loss, float delta, double* value, double* coverage,
+                                        double* inlier_mass, float* pair_terms);
+int ecc_metric_evaluate_weighted_robust_pairs(ecc_metric* m, const int32_t* idx4, int n_pairs, int loss, float delta,
+                                              double* value, double* coverage, double* inlier_mass, float* pair_terms);
+double ecc_host_weighted_robust_scale(const float* pair_terms, int64_t n_pairs, double k);
 
 /* Multi-GPU building block: evaluate only pairs ij in [first, first+count) of the get_ij order
  * (ref: EpipolarConsistencyCommon.hxx:52-79); returns the partial sum (float64) -- the caller
