@@ -387,6 +387,41 @@ def _check_pose_lists(moved_offsets, moved_views, moved_Ps):
     return off, views, flat
 
 
+def _ptr(a):
+    """The address of an optional array for a C call: None for no array and for an empty one."""
+    return C.c_void_p(a.ctypes.data) if (a is not None and a.size) else None
+
+
+def _idx4_list(idx4):
+    idx = np.ascontiguousarray(idx4, np.int32)
+    if idx.size % 4 or (idx.ndim == 2 and idx.shape[1] != 4) or idx.ndim > 2:
+        raise ValueError("idx4 must hold (P0, P1, D0, D1) tuples")
+    return idx.reshape(-1, 4)
+
+
+def _transforms_colmajor(Ts):
+    """Anything np.asarray turns into (K, 4, 4) or (4, 4) -> (K, 16) float64, column-major per transform."""
+    T = np.asarray(Ts, dtype=np.float64)
+    if T.ndim == 2 and T.shape == (4, 4):
+        T = T[None]
+    if T.ndim != 3 or T.shape[1:] != (4, 4):
+        raise ValueError("Ts must be (K, 4, 4)")
+    return np.ascontiguousarray(T.transpose(0, 2, 1)).reshape(-1, 16)
+
+
+def _with_pairs(results, pairs, want_pairs):
+    return results + (pairs,) if want_pairs else results
+
+
+def _pose_lists_call(fn, handle, moved_offsets, moved_views, moved_Ps, extra, n_results):
+    """fn(handle, K, offsets, views, matrices, *extra, results...) over checked pose lists -> the n_results float64 arrays of K."""
+    off, views, flat = _check_pose_lists(moved_offsets, moved_views, moved_Ps)
+    results = tuple(np.zeros(len(off) - 1, np.float64) for _ in range(n_results))
+    check(fn(handle, len(off) - 1, C.c_void_p(off.ctypes.data), _ptr(views), _ptr(flat), *extra,
+             *[C.c_void_p(r.ctypes.data) for r in results]))
+    return results
+
+
 class MetricRadonIntermediate:
     """ref: class MetricRadonIntermediate : public Metric."""
 
@@ -666,13 +701,7 @@ class MetricRadonIntermediate:
     def evaluate_pose_deltas_packed(self, moved_offsets, moved_views, moved_Ps):
         """The C signature itself: moved_offsets (K + 1 int32, [0] = 0), moved_views (Q int32, ascending within a pose), moved_Ps
         ((Q, 12) float64, column-major per matrix).  No per-pose Python work."""
-        off, views, flat = _check_pose_lists(moved_offsets, moved_views, moved_Ps)
-        means = np.zeros(len(off) - 1, np.float64)
-        check(_lib.lib().ecc_metric_evaluate_pose_deltas(self._h, len(means), C.c_void_p(off.ctypes.data),
-                                                         C.c_void_p(views.ctypes.data) if len(views) else None,
-                                                         C.c_void_p(flat.ctypes.data) if len(views) else None,
-                                                         C.c_void_p(means.ctypes.data)))
-        return means
+        return _pose_lists_call(_lib.lib().ecc_metric_evaluate_pose_deltas, self._h, moved_offsets, moved_views, moved_Ps, (), 1)[0]
 
     def evaluate_weighted_pose_deltas(self, moved_views, moved_Ps):
         """ecc_metric_evaluate_weighted_pose_deltas: evaluate_pose_deltas for the metric with per-line weights (evaluate_weighted: the
@@ -682,13 +711,7 @@ class MetricRadonIntermediate:
 
     def evaluate_weighted_pose_deltas_packed(self, moved_offsets, moved_views, moved_Ps):
         """The C signature itself, with the arguments of evaluate_pose_deltas_packed; returns (values, coverages)."""
-        off, views, flat = _check_pose_lists(moved_offsets, moved_views, moved_Ps)
-        values, coverages = np.zeros(len(off) - 1, np.float64), np.zeros(len(off) - 1, np.float64)
-        check(_lib.lib().ecc_metric_evaluate_weighted_pose_deltas(self._h, len(values), C.c_void_p(off.ctypes.data),
-                                                                  C.c_void_p(views.ctypes.data) if len(views) else None,
-                                                                  C.c_void_p(flat.ctypes.data) if len(views) else None,
-                                                                  C.c_void_p(values.ctypes.data), C.c_void_p(coverages.ctypes.data)))
-        return values, coverages
+        return _pose_lists_call(_lib.lib().ecc_metric_evaluate_weighted_pose_deltas, self._h, moved_offsets, moved_views, moved_Ps, (), 2)
 
     def evaluate_robust_pose_deltas(self, moved_views, moved_Ps, loss, delta):
         """ecc_metric_evaluate_robust_pose_deltas: evaluate_pose_deltas under the per-sample robust loss of evaluate_robust (loss,
@@ -699,30 +722,21 @@ class MetricRadonIntermediate:
     def evaluate_robust_pose_deltas_packed(self, moved_offsets, moved_views, moved_Ps, loss, delta):
         """The C signature itself, with the arguments of evaluate_pose_deltas_packed, then loss and delta; returns (values,
         inlier_masses)."""
-        off, views, flat = _check_pose_lists(moved_offsets, moved_views, moved_Ps)
-        values, masses = np.zeros(len(off) - 1, np.float64), np.zeros(len(off) - 1, np.float64)
-        check(_lib.lib().ecc_metric_evaluate_robust_pose_deltas(self._h, len(values), C.c_void_p(off.ctypes.data),
-                                                                C.c_void_p(views.ctypes.data) if len(views) else None,
-                                                                C.c_void_p(flat.ctypes.data) if len(views) else None,
-                                                                int(loss), float(delta),
-                                                                C.c_void_p(values.ctypes.data), C.c_void_p(masses.ctypes.data)))
-        return values, masses
+        return _pose_lists_call(_lib.lib().ecc_metric_evaluate_robust_pose_deltas, self._h, moved_offsets, moved_views, moved_Ps,
+                                (int(loss), float(delta)), 2)
 
     def evaluate_weighted_pairs(self, idx4, want_pairs=False):
         """ecc_metric_evaluate_weighted_pairs: evaluate_weighted over an index list of (P0, P1, D0, D1) tuples -- matrices P*, data
         intermediates D* in [0, n_views); the weights of a sample come from intermediate n_views + D*.  Returns (value, coverage) =
         (sum c / sum u, sum u / n_pairs) over the list -- with want_pairs (value, coverage, pairs), pairs (n_pairs, 2) float32 rows
         {c, u} in list order.  The sampling mode resolves from the list's length, as evaluate(indices) resolves it."""
-        idx = np.ascontiguousarray(idx4, np.int32)
-        if idx.size % 4 or (idx.ndim == 2 and idx.shape[1] != 4) or idx.ndim > 2:
-            raise ValueError("idx4 must hold (P0, P1, D0, D1) tuples")
-        idx = idx.reshape(-1, 4)
+        idx = _idx4_list(idx4)
         value, coverage = C.c_double(0.0), C.c_double(0.0)
         pairs = np.zeros((len(idx), 2), np.float32) if want_pairs else None
-        check(_lib.lib().ecc_metric_evaluate_weighted_pairs(self._h, C.c_void_p(idx.ctypes.data) if len(idx) else None, len(idx),
+        check(_lib.lib().ecc_metric_evaluate_weighted_pairs(self._h, _ptr(idx), len(idx),
                                                             C.byref(value), C.byref(coverage),
-                                                            C.c_void_p(pairs.ctypes.data) if (want_pairs and pairs.size) else None))
-        return (value.value, coverage.value, pairs) if want_pairs else (value.value, coverage.value)
+                                                            _ptr(pairs)))
+        return _with_pairs((value.value, coverage.value), pairs, want_pairs)
 
     def setPoseBatching(self, on=True):
         """ecc_metric_set_pose_batching: off = evaluate_poses runs every pose as its own stream-ordered evaluation."""
@@ -791,7 +805,7 @@ class MetricRadonIntermediate:
         n = 0 if self._Ps is None else len(self._Ps)  # (no matrices: the library reports it)
         G = np.zeros((max(K, 0), max(K, 0)), np.float64)
         pairs = np.zeros((n * (n - 1) // 2, max(K, 0) * (max(K, 0) + 1) // 2), np.float32) if want_pairs else None
-        check(_lib.lib().ecc_metric_evaluate_gram(self._h, K, C.c_void_p(pairs.ctypes.data) if (want_pairs and pairs.size) else None,
+        check(_lib.lib().ecc_metric_evaluate_gram(self._h, K, _ptr(pairs),
                                                   C.c_void_p(G.ctypes.data) if G.size else None))
         return (G, pairs) if want_pairs else G
 
@@ -814,7 +828,7 @@ class MetricRadonIntermediate:
         pairs = np.zeros((n * (n - 1) // 2, 1 + 2 * K), np.float32) if want_pairs else None
         check(_lib.lib().ecc_metric_evaluate_view_coefficients(self._h, K, C.c_void_p(a.ctypes.data) if a.size else None, C.byref(value),
                                                                C.c_void_p(grad.ctypes.data) if grad.size else None,
-                                                               C.c_void_p(pairs.ctypes.data) if (want_pairs and pairs.size) else None))
+                                                               _ptr(pairs)))
         return (value.value, grad, pairs) if want_pairs else (value.value, grad)
 
     def evaluate_view_hessian(self, n_channels, want_pairs=False, want_matrix=True):
@@ -852,8 +866,8 @@ class MetricRadonIntermediate:
         value, coverage = C.c_double(0.0), C.c_double(0.0)
         pairs = np.zeros((n * (n - 1) // 2, 2), np.float32) if want_pairs else None
         check(_lib.lib().ecc_metric_evaluate_weighted(self._h, C.byref(value), C.byref(coverage),
-                                                      C.c_void_p(pairs.ctypes.data) if (want_pairs and pairs.size) else None))
-        return (value.value, coverage.value, pairs) if want_pairs else (value.value, coverage.value)
+                                                      _ptr(pairs)))
+        return _with_pairs((value.value, coverage.value), pairs, want_pairs)
 
     def evaluate_robust(self, loss, delta, want_pairs=False):
         """ecc_metric_evaluate_robust: the metric under a per-sample robust loss rho(d) = w(d) d^2 -- loss one of LOSS_HUBER,
@@ -866,24 +880,21 @@ class MetricRadonIntermediate:
         value, mass = C.c_double(0.0), C.c_double(0.0)
         pairs = np.zeros((n * (n - 1) // 2, 3), np.float32) if want_pairs else None
         check(_lib.lib().ecc_metric_evaluate_robust(self._h, int(loss), float(delta), C.byref(value), C.byref(mass),
-                                                    C.c_void_p(pairs.ctypes.data) if (want_pairs and pairs.size) else None))
-        return (value.value, mass.value, pairs) if want_pairs else (value.value, mass.value)
+                                                    _ptr(pairs)))
+        return _with_pairs((value.value, mass.value), pairs, want_pairs)
 
     def evaluate_robust_pairs(self, idx4, loss, delta, want_pairs=False):
         """ecc_metric_evaluate_robust_pairs: evaluate_robust over an index list of (P0, P1, D0, D1) tuples, as evaluate(indices)
         takes them.  Returns (value, inlier_mass) over the list -- with want_pairs (value, inlier_mass, pairs), pairs (n_pairs, 3)
         float32 rows {c, u, r} in list order.  The sampling mode resolves from the list's length; an empty list writes nothing
         (0.0, 0.0)."""
-        idx = np.ascontiguousarray(idx4, np.int32)
-        if idx.size % 4 or (idx.ndim == 2 and idx.shape[1] != 4) or idx.ndim > 2:
-            raise ValueError("idx4 must hold (P0, P1, D0, D1) tuples")
-        idx = idx.reshape(-1, 4)
+        idx = _idx4_list(idx4)
         value, mass = C.c_double(0.0), C.c_double(0.0)
         pairs = np.zeros((len(idx), 3), np.float32) if want_pairs else None
-        check(_lib.lib().ecc_metric_evaluate_robust_pairs(self._h, C.c_void_p(idx.ctypes.data) if len(idx) else None, len(idx),
+        check(_lib.lib().ecc_metric_evaluate_robust_pairs(self._h, _ptr(idx), len(idx),
                                                           int(loss), float(delta), C.byref(value), C.byref(mass),
-                                                          C.c_void_p(pairs.ctypes.data) if (want_pairs and pairs.size) else None))
-        return (value.value, mass.value, pairs) if want_pairs else (value.value, mass.value)
+                                                          _ptr(pairs)))
+        return _with_pairs((value.value, mass.value), pairs, want_pairs)
 
     def evaluate_weighted_robust(self, loss, delta, want_pairs=False):
         """ecc_metric_evaluate_weighted_robust: line weights and the robust loss together, for scans that have both kinds of bad
@@ -899,8 +910,8 @@ class MetricRadonIntermediate:
         value, coverage, mass = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
         pairs = np.zeros((n * (n - 1) // 2, 4), np.float32) if want_pairs else None
         check(_lib.lib().ecc_metric_evaluate_weighted_robust(self._h, int(loss), float(delta), C.byref(value), C.byref(coverage), C.byref(mass),
-                                                             C.c_void_p(pairs.ctypes.data) if (want_pairs and pairs.size) else None))
-        return (value.value, coverage.value, mass.value, pairs) if want_pairs else (value.value, coverage.value, mass.value)
+                                                             _ptr(pairs)))
+        return _with_pairs((value.value, coverage.value, mass.value), pairs, want_pairs)
 
     def evaluate_weighted_robust_pairs(self, idx4, loss, delta, want_pairs=False):
         """ecc_metric_evaluate_weighted_robust_pairs: evaluate_weighted_robust over an index list of (P0, P1, D0, D1) tuples as
@@ -908,16 +919,13 @@ class MetricRadonIntermediate:
         index.  Returns (value, coverage, inlier_mass) over the list -- with want_pairs also pairs (n_pairs, 4) float32 rows
         {c, u, k, r} in list order.  The sampling mode resolves from the list's length; an empty list writes nothing
         (0.0, 0.0, 0.0)."""
-        idx = np.ascontiguousarray(idx4, np.int32)
-        if idx.size % 4 or (idx.ndim == 2 and idx.shape[1] != 4) or idx.ndim > 2:
-            raise ValueError("idx4 must hold (P0, P1, D0, D1) tuples")
-        idx = idx.reshape(-1, 4)
+        idx = _idx4_list(idx4)
         value, coverage, mass = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
         pairs = np.zeros((len(idx), 4), np.float32) if want_pairs else None
-        check(_lib.lib().ecc_metric_evaluate_weighted_robust_pairs(self._h, C.c_void_p(idx.ctypes.data) if len(idx) else None, len(idx),
+        check(_lib.lib().ecc_metric_evaluate_weighted_robust_pairs(self._h, _ptr(idx), len(idx),
                                                                    int(loss), float(delta), C.byref(value), C.byref(coverage), C.byref(mass),
-                                                                   C.c_void_p(pairs.ctypes.data) if (want_pairs and pairs.size) else None))
-        return (value.value, coverage.value, mass.value, pairs) if want_pairs else (value.value, coverage.value, mass.value)
+                                                                   _ptr(pairs)))
+        return _with_pairs((value.value, coverage.value, mass.value), pairs, want_pairs)
 
     def evaluate_transforms(self, n_source, Ts, want_pairs=False):
         """ecc_metric_evaluate_transforms: the registration of two scans (ref: tools/Registration/Registration3D3D.hxx).  The
@@ -927,19 +935,14 @@ class MetricRadonIntermediate:
         Returns the K means (float64), with want_pairs also the pair values as (K, n_target, n_source) float32: every number
         bit-identical to setProjectionMatrices(composed) + evaluate(index list) per transform; the current matrices stay.
         Fix the object radius (setObjectRadius) for a sweep whose values are compared with each other."""
-        T = np.asarray(Ts, dtype=np.float64)
-        if T.ndim == 2 and T.shape == (4, 4):
-            T = T[None]
-        if T.ndim != 3 or T.shape[1:] != (4, 4):
-            raise ValueError("Ts must be (K, 4, 4)")
-        flat = np.ascontiguousarray(T.transpose(0, 2, 1)).reshape(-1, 16)  # column-major per transform
+        flat = _transforms_colmajor(Ts)
         n_source = int(n_source)
         K, n = len(flat), self.getNumberOfProjetions()
         means = np.zeros(K, np.float64)
         pairs = np.zeros((K, max(n - n_source, 0), max(n_source, 0)), np.float32) if want_pairs else None
         check(_lib.lib().ecc_metric_evaluate_transforms(self._h, n_source, K, C.c_void_p(flat.ctypes.data if K else 0),
                                                         C.c_void_p(means.ctypes.data if K else 0),
-                                                        C.c_void_p(pairs.ctypes.data) if (want_pairs and pairs.size) else None))
+                                                        _ptr(pairs)))
         return (means, pairs) if want_pairs else means
 
     def evaluate_weighted_transforms(self, n_source, Ts, want_pairs=False):
@@ -949,12 +952,7 @@ class MetricRadonIntermediate:
         over the cross pairs -- with want_pairs (values, coverages, pairs), pairs (K, n_target, n_source, 2) float32 rows {c, u}: every
         number bit-identical to setProjectionMatrices(composed) + evaluate_weighted_pairs(the cross list) per transform; the current
         matrices stay."""
-        T = np.asarray(Ts, dtype=np.float64)
-        if T.ndim == 2 and T.shape == (4, 4):
-            T = T[None]
-        if T.ndim != 3 or T.shape[1:] != (4, 4):
-            raise ValueError("Ts must be (K, 4, 4)")
-        flat = np.ascontiguousarray(T.transpose(0, 2, 1)).reshape(-1, 16)  # column-major per transform
+        flat = _transforms_colmajor(Ts)
         n_source = int(n_source)
         K, n = len(flat), self.getNumberOfProjetions()
         values, coverages = np.zeros(K, np.float64), np.zeros(K, np.float64)
@@ -962,8 +960,8 @@ class MetricRadonIntermediate:
         check(_lib.lib().ecc_metric_evaluate_weighted_transforms(self._h, n_source, K, C.c_void_p(flat.ctypes.data if K else 0),
                                                                  C.c_void_p(values.ctypes.data if K else 0),
                                                                  C.c_void_p(coverages.ctypes.data if K else 0),
-                                                                 C.c_void_p(pairs.ctypes.data) if (want_pairs and pairs.size) else None))
-        return (values, coverages, pairs) if want_pairs else (values, coverages)
+                                                                 _ptr(pairs)))
+        return _with_pairs((values, coverages), pairs, want_pairs)
 
     def evaluate_robust_transforms(self, n_source, Ts, loss, delta, want_pairs=False):
         """ecc_metric_evaluate_robust_transforms: evaluate_transforms under the per-sample robust loss of evaluate_robust (loss, delta
@@ -971,12 +969,7 @@ class MetricRadonIntermediate:
         transform (sum c, sum u) / (n_source n_target) over the cross pairs -- with want_pairs (values, inlier_masses, pairs), pairs
         (K, n_target, n_source, 3) float32 rows {c, u, r}: every number bit-identical to setProjectionMatrices(composed) +
         evaluate_robust_pairs(the cross list, loss, delta) per transform; the current matrices stay."""
-        T = np.asarray(Ts, dtype=np.float64)
-        if T.ndim == 2 and T.shape == (4, 4):
-            T = T[None]
-        if T.ndim != 3 or T.shape[1:] != (4, 4):
-            raise ValueError("Ts must be (K, 4, 4)")
-        flat = np.ascontiguousarray(T.transpose(0, 2, 1)).reshape(-1, 16)  # column-major per transform
+        flat = _transforms_colmajor(Ts)
         n_source = int(n_source)
         K, n = len(flat), self.getNumberOfProjetions()
         values, masses = np.zeros(K, np.float64), np.zeros(K, np.float64)
@@ -985,8 +978,8 @@ class MetricRadonIntermediate:
                                                                int(loss), float(delta),
                                                                C.c_void_p(values.ctypes.data if K else 0),
                                                                C.c_void_p(masses.ctypes.data if K else 0),
-                                                               C.c_void_p(pairs.ctypes.data) if (want_pairs and pairs.size) else None))
-        return (values, masses, pairs) if want_pairs else (values, masses)
+                                                               _ptr(pairs)))
+        return _with_pairs((values, masses), pairs, want_pairs)
 
     def last_batched_transforms(self):
         """Transforms of the last evaluate_transforms / evaluate_weighted_transforms / evaluate_robust_transforms call that went

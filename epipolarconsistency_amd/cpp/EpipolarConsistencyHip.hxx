@@ -754,18 +754,8 @@ public:
             setProjectionMatrices(keep);
             return means;
         }
-        std::vector<int32_t> off(1, 0), views;
-        std::vector<double> flat;
-        for (size_t k = 0; k < moved_views.size(); ++k) {
-            if (moved_views[k].size() != moved_Ps[k].size()) throw std::runtime_error("evaluatePoseDeltas: one matrix per moved view");
-            for (size_t q = 0; q < moved_views[k].size(); ++q) {
-                views.push_back(moved_views[k][q]);
-                flat.insert(flat.end(), moved_Ps[k][q].data(), moved_Ps[k][q].data() + 12);
-            }
-            off.push_back((int32_t)views.size());
-        }
-        detail::check(ecc_metric_evaluate_pose_deltas(m_h, (int)moved_views.size(), off.data(), views.empty() ? nullptr : views.data(),
-                                                      flat.empty() ? nullptr : flat.data(), means.data()));
+        const PackedPoseLists l("evaluatePoseDeltas", moved_views, moved_Ps);
+        detail::check(ecc_metric_evaluate_pose_deltas(m_h, (int)moved_views.size(), l.off.data(), l.views_or_null(), l.Ps_or_null(), means.data()));
         return means;
     }
 
@@ -1022,19 +1012,9 @@ public:
         values.assign(moved_views.size(), 0.0);
         if (coverages) coverages->assign(moved_views.size(), 0.0);
         if (moved_views.empty()) return;
-        std::vector<int32_t> off(1, 0), views;
-        std::vector<double> flat;
-        for (size_t k = 0; k < moved_views.size(); ++k) {
-            if (moved_views[k].size() != moved_Ps[k].size()) throw std::runtime_error("evaluateWeightedPoseDeltas: one matrix per moved view");
-            for (size_t q = 0; q < moved_views[k].size(); ++q) {
-                views.push_back(moved_views[k][q]);
-                flat.insert(flat.end(), moved_Ps[k][q].data(), moved_Ps[k][q].data() + 12);
-            }
-            off.push_back((int32_t)views.size());
-        }
-        detail::check(ecc_metric_evaluate_weighted_pose_deltas(m_h, (int)moved_views.size(), off.data(), views.empty() ? 0x0 : views.data(),
-                                                               flat.empty() ? 0x0 : flat.data(), values.data(),
-                                                               coverages ? coverages->data() : 0x0));
+        const PackedPoseLists l("evaluateWeightedPoseDeltas", moved_views, moved_Ps);
+        detail::check(ecc_metric_evaluate_weighted_pose_deltas(m_h, (int)moved_views.size(), l.off.data(), l.views_or_null(), l.Ps_or_null(),
+                                                               values.data(), coverages ? coverages->data() : 0x0));
     }
 
     /// Not in the reference: ecc_metric_evaluate_weighted_transforms -- evaluateTransforms for the metric with per-line weights
@@ -1069,19 +1049,9 @@ public:
         values.assign(moved_views.size(), 0.0);
         if (inlier_masses) inlier_masses->assign(moved_views.size(), 0.0);
         if (moved_views.empty()) return;
-        std::vector<int32_t> off(1, 0), views;
-        std::vector<double> flat;
-        for (size_t k = 0; k < moved_views.size(); ++k) {
-            if (moved_views[k].size() != moved_Ps[k].size()) throw std::runtime_error("evaluateRobustPoseDeltas: one matrix per moved view");
-            for (size_t q = 0; q < moved_views[k].size(); ++q) {
-                views.push_back(moved_views[k][q]);
-                flat.insert(flat.end(), moved_Ps[k][q].data(), moved_Ps[k][q].data() + 12);
-            }
-            off.push_back((int32_t)views.size());
-        }
-        detail::check(ecc_metric_evaluate_robust_pose_deltas(m_h, (int)moved_views.size(), off.data(), views.empty() ? 0x0 : views.data(),
-                                                             flat.empty() ? 0x0 : flat.data(), loss, delta, values.data(),
-                                                             inlier_masses ? inlier_masses->data() : 0x0));
+        const PackedPoseLists l("evaluateRobustPoseDeltas", moved_views, moved_Ps);
+        detail::check(ecc_metric_evaluate_robust_pose_deltas(m_h, (int)moved_views.size(), l.off.data(), l.views_or_null(), l.Ps_or_null(), loss,
+                                                             delta, values.data(), inlier_masses ? inlier_masses->data() : 0x0));
     }
 
     /// Not in the reference: ecc_metric_evaluate_robust_transforms -- evaluateTransforms under the per-sample robust loss of
@@ -1136,6 +1106,28 @@ private:
         double* b = !pair_blocks ? 0x0 : (pair_blocks->empty() ? &none : pair_blocks->data());
         detail::check(ecc_metric_evaluate_view_hessian(m_h, n_channels, h, b));
     }
+
+    // The pose lists of the evaluate*PoseDeltas calls as the C calls take them: off[0] = 0 ... off[K] = Q, the Q moved views, their
+    // Q x 12 matrices.  views_or_null() / Ps_or_null(): what the calls pass for them.
+    struct PackedPoseLists {
+        std::vector<int32_t> off, views;
+        std::vector<double> flat;
+        PackedPoseLists(const char* who, const std::vector<std::vector<int> >& moved_views,
+                        const std::vector<std::vector<Geometry::ProjectionMatrix> >& moved_Ps)
+            : off(1, 0)
+        {
+            for (size_t k = 0; k < moved_views.size(); ++k) {
+                if (moved_views[k].size() != moved_Ps[k].size()) throw std::runtime_error(std::string(who) + ": one matrix per moved view");
+                for (size_t q = 0; q < moved_views[k].size(); ++q) {
+                    views.push_back(moved_views[k][q]);
+                    flat.insert(flat.end(), moved_Ps[k][q].data(), moved_Ps[k][q].data() + 12);
+                }
+                off.push_back((int32_t)views.size());
+            }
+        }
+        const int32_t* views_or_null() const { return views.empty() ? 0x0 : views.data(); }
+        const double* Ps_or_null() const { return flat.empty() ? 0x0 : flat.data(); }
+    };
 
 public:
     /// The metric borrows the dtrs: "DO NOT delete or change _dtrs during lifetime" (ref: .h:45).

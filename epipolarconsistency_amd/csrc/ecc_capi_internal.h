@@ -460,7 +460,7 @@ int evaluate_cached(ecc_metric* m, int64_t first, int64_t count, double* sum_d, 
 // (automatic) object radius
 int sum_poses(ecc_metric* m, const float* base_vals_d, int K, int Q, volatile uint64_t* out, double* out_dev, double* sums);
 bool pose_keeps_radius(const ecc_metric* m, double base_radius, int c, const int32_t* views, const double* moved_Ps);
-// ecc_poses.hip, for the batches of ecc_weighted_poses.hip as well: the lists' checks; the host half of a batch's grid (pinned block,
+// ecc_poses.hip, for the batches of ecc_form_call.h as well: the lists' checks; the host half of a batch's grid (pinned block,
 // device arrays) and the launch of pose_list_kernel over it; the result slots' sentinel and the bounded wait for them
 int check_lists(const ecc_metric* m, int n_poses, const int32_t* off, const int32_t* views);
 int stage_pose_grid(ecc_metric* m, const double* base, int K, const int32_t* off, const int32_t* views, const double* moved_Ps,
@@ -472,7 +472,7 @@ int wait_pose_results(ecc_ctx* ctx, volatile uint64_t* out, int K, double* sums,
 // matrices back -- then the base again
 int pose_deltas_sequential(ecc_metric* m, const std::vector<int>& rest, const int32_t* off, const int32_t* views, const double* moved_Ps,
                            const std::function<int(int)>& evaluate_pose);
-// ecc_transforms.hip, for the batches of ecc_weighted_transforms.hip as well: the object radius the sequential calls would take for a
+// ecc_transforms.hip, for the batches of ecc_form_call.h as well: the object radius the sequential calls would take for a
 // transform; the host half of a batch's grid (pinned block, device arrays) and the launch of transform_list_kernel over it; the
 // two drivers of a call -- the transforms one at a time over the cross list, then the base again; whole transforms in batches of at
 // most max_per_batch within ECC_POSE_BATCH_MAX_ENTRIES grid entries, run_batch(first transform, how many) each
@@ -486,17 +486,10 @@ int transforms_batched(ecc_metric* m, int64_t count, int n_transforms, int64_t m
 // ecc_gram.hip: what the channel forms (Gram, view coefficients, view Hessian) need of n_channels and of the metric, with the call's
 // own texts for the range of n_channels and for the correlation cost
 int channel_form_check(const ecc_metric* m, int n_channels, const char* range_text, const char* corr_text);
-// ecc_weighted.hip: the argument checks of the weighted calls; {c, u} of all pairs at the current matrices into gram_values_d
-// (c, g: the launches as they were made); value and coverage from the two totals
-struct ColumnCall;  // (ecc_column_call.h)
+// ecc_weighted.hip: the argument checks of the weighted calls
 int weighted_check(const ecc_metric* m);
-int weighted_base_columns(ecc_metric* m, ColumnCall* c, EccWeightedParams* g);
-void finish_weighted(double sum_c, double sum_u, int64_t count, double* value, double* coverage);
-// ecc_robust.hip: the argument checks of the robust calls (value: the required result pointer); the launch's loss; {c, u, r} of all
-// pairs at the current matrices into gram_values_d (c, g: the launches as they were made)
+// ecc_robust.hip: the argument checks of the robust calls (value: the required result pointer)
 int robust_check(const ecc_metric* m, const double* value, int loss, float delta);
-void fill_robust_params(EccRobustParams* g, float* values, int64_t col_stride, int loss, float delta);
-int robust_base_columns(ecc_metric* m, int loss, float delta, ColumnCall* c, EccRobustParams* g);
 
 // The distance of two channels' row-paired and row-quad copies, for the pair forms that read more than one copy per view (g: any
 // of their parameter structs).
@@ -528,24 +521,6 @@ inline hipError_t launch_timed(ecc_ctx* ctx, Launch&& launch)
 inline hipError_t launch_pairs_timed(ecc_ctx* ctx, const EccPairParams* p, const EccSmallEval* x = nullptr)
 {
     return launch_timed(ctx, [&](hipStream_t s) { return x ? ecc_launch_small_eval(p, x, s) : ecc_launch_pairs(p, s); });
-}
-
-// The weighted pair launch (weighted_kernel.hip) between the same events.
-inline hipError_t launch_weighted_timed(ecc_ctx* ctx, const EccPairParams* p, const EccWeightedParams* g)
-{
-    return launch_timed(ctx, [&](hipStream_t s) { return ecc_launch_pairs_weighted(p, g, s); });
-}
-
-// The robust pair launch (robust_kernel.hip) between the same events.
-inline hipError_t launch_robust_timed(ecc_ctx* ctx, const EccPairParams* p, const EccRobustParams* g)
-{
-    return launch_timed(ctx, [&](hipStream_t s) { return ecc_launch_pairs_robust(p, g, s); });
-}
-
-// The weighted robust pair launch (weighted_robust_kernel.hip) between the same events.
-inline hipError_t launch_weighted_robust_timed(ecc_ctx* ctx, const EccPairParams* p, const EccWeightedRobustParams* g)
-{
-    return launch_timed(ctx, [&](hipStream_t s) { return ecc_launch_pairs_weighted_robust(p, g, s); });
 }
 
 }  // namespace ecc_internal

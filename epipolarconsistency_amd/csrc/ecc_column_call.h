@@ -1,7 +1,8 @@
 // ecc_column_call.h -- the host side of a column-form call, once.  A column-form call evaluates `count` pairs --
 // all pairs of the current matrices, or an index list -- with a pair kernel that stores T columns per pair, col_stride apart, and
 // returns the float64 totals of the leading S columns and, on request, the columns as rows.  ecc_metric_evaluate_gram,
-// _view_coefficients, _view_hessian, _weighted, _weighted_pairs and _robust[_pairs] are such calls:
+// _view_coefficients, _view_hessian, _weighted, _weighted_pairs, _robust[_pairs] and _weighted_robust[_pairs] are such calls (the
+// weighted and robust families through ecc_form_call.h, which states their four steps once):
 //   its checks                 every one returns before the device is touched
 //   column_call_begin          everything up to and including the record launch
 //   its own parameter struct and pair launch, between the timing events (launch_timed)

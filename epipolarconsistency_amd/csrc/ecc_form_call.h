@@ -1,0 +1,274 @@
+// ecc_form_call.h -- the host side of the weighted, robust and weighted-robust call families, once.  The three
+// forms are column-form calls (ecc_column_call.h) whose pair kernels differ in what they store per pair; what a call does around
+// its pair launch does not depend on the form.  A PairForm says what does: how many columns the pair launch stores, how many of
+// them are summed, how to launch the pair kernel into a column buffer, how totals become the caller's results.  weighted_form
+// (ecc_weighted.hip), robust_form (ecc_robust.hip) and weighted_robust_form (ecc_weighted_robust.hip) build one from a call's
+// arguments; the drivers below are written over it and never ask which form it is.
+//
+// form_call          all pairs of the current matrices, or an index list: E1 (if the device geometry is behind the matrices),
+//                    k01_kernel into the Gram family's records (column_call_begin), the form's pair launch (form_columns),
+//                    sum_gram_kernel over the S leading columns, the copies, the one wait (column_call_finish), the form's division.
+//                    The metric's kept records, kept values and pose-batch values are not touched (a list stages its tuples in the
+//                    pose batch's index scratch).
+// form_pose_deltas   K poses that each replace a few views of the current matrices (the lists of ecc_metric_evaluate_pose_deltas):
+//   base columns     all pairs at the current matrices (form_columns: the all-pairs call's own launches), once per call
+//   per batch        (which poses: ecc_pose_batches.h) pose_list_kernel (index grid, E1 of the extended matrices), k01_kernel over
+//                    the n x Q grid into the pose batch's records, the form's pair launch over it with the base's parameters (the
+//                    sampling mode and wave split of an all-pairs evaluation; EccPairParams::n_views stays n: the weight copy of data
+//                    copy iD is n copies behind it) into T columns of pose_values_d, sum_weighted_poses_kernel: per pose the sums of
+//                    columns 0 and 1 over all pairs, the pose's own entries substituted, in the order of ecc_sum_order.h -> 2 K
+//                    pinned result words the host polls; the form's division per pose
+//   the rest         what the batch does not take: the pose's matrices, the form's all-pairs call, the matrices back
+// form_transforms    K transforms of the source views (ecc_metric_evaluate_transforms' views and cross list), per batch:
+//                    transform_list_kernel (ecc_transforms.hip's launch, unchanged: the DATA indices of an entry stay i and
+//                    n_source + j whatever its extended matrix index is; its value slots are written and not read: these pair
+//                    launches have none), k01_kernel (k01_radii_kernel under the automatic object radius) over the pair-major,
+//                    transform-minor grid (ecc_transform_grid.h), the form's pair launch under the mode of a list of `count` tuples,
+//                    sum_weighted_transforms_kernel over columns 0 and 1 -> 2 K result words; the pair terms: one copy of the T
+//                    columns and the transposition to transform-major rows; with batching off or a list longer than a batch the
+//                    transforms one at a time through the form's list call
+// The two segmented sums read columns 0 and 1 of a column-form buffer and know nothing of what the columns mean, so a batch has two
+// sums per pose or transform whatever the form's T.
+#ifndef ECC_FORM_CALL_H
+#define ECC_FORM_CALL_H
+
+#include "ecc_column_call.h"
+#include "ecc_pose_batches.h"
+#include "ecc_transform_grid.h"
+
+namespace ecc_internal {
+
+struct PairForm {
+    int T;  // columns the pair launch stores per pair
+    int S;  // leading columns that are summed
+    // the form's pair kernel over p into T columns at `values`, col_stride apart, between the context's timing events
+    std::function<hipError_t(ecc_metric* m, const EccPairParams& p, float* values, int64_t col_stride)> launch;
+    // result k of the call from the totals of the summed columns over `count` pairs
+    std::function<void(const double* totals, int64_t count, int64_t k)> finish;
+};
+
+// ecc_weighted.hip: T = S = 2, columns {c, u}; values[k] = sum c / sum u, coverages[k] (coverages nullable) = sum u / count
+PairForm weighted_form(double* values, double* coverages);
+// ecc_robust.hip: T = 3, S = 2, columns {c, u, r}; values[k] = sum c / count, inlier_masses[k] (nullable) = sum u / count
+PairForm robust_form(int loss, float delta, double* values, double* inlier_masses);
+
+// poses per batch: the sum's grid is slices x poses x 2 columns, half a million workgroups at most
+constexpr size_t FORM_BATCH_MAX_POSES = (1 << 19) / (2 * ecc_sum::SLICES);
+static_assert(FORM_BATCH_MAX_POSES < 65536, "poses are the y dimension of sum_weighted_poses_kernel's grid");
+// transforms per batch: they are the y dimension of the sum's grid
+constexpr int64_t FORM_TRANSFORM_BATCH_MAX = 32768;
+static_assert(FORM_TRANSFORM_BATCH_MAX < 65536, "transforms are the y dimension of sum_weighted_transforms_kernel's grid");
+
+// The (P0, P1, D0, D1) tuples of an index list: P index the current matrices, in [0, nP), D the intermediates, in [0, nD).
+inline int check_index_list(const int32_t* idx4, int n_pairs, int nP, int nD, const char* message)
+{
+    for (int q = 0; q < n_pairs; ++q) {
+        const int32_t* t = idx4 + 4 * (size_t)q;
+        if (t[0] < 0 || t[0] >= nP || t[1] < 0 || t[1] >= nP || t[2] < 0 || t[2] >= nD || t[3] < 0 || t[3] >= nD)
+            return fail(ECC_ERR_INVALID_ARGUMENT, message);
+    }
+    return ECC_OK;
+}
+
+// k x the median of rms (even count: the mean of the two middle values); 0.0 with no entry.
+inline double scaled_median(std::vector<double>& rms, double k)
+{
+    if (rms.empty()) return 0.0;
+    std::sort(rms.begin(), rms.end());
+    const size_t h = rms.size() / 2;
+    return k * (rms.size() & 1 ? rms[h] : (rms[h - 1] + rms[h]) / 2.0);
+}
+
+// The form's columns of `count` pairs -- all pairs (idx4 null) or the list -- under the sampling mode of that many values: a call
+// up to and including its pair launch.  The T columns are in m->gram_values_d, c->col_stride apart, once the stream gets there;
+// c->p is the record launch as it was made (the pose batches launch their grids with the same parameters).
+inline int form_columns(ecc_metric* m, const PairForm& f, const int32_t* idx4, int64_t count, ColumnCall* c)
+{
+    const int rc = column_call_begin(m, idx4, count, f.T, f.S, c);
+    if (rc) return rc;
+    HIP_TRY(f.launch(m, c->p, m->gram_values_d.ptr, c->col_stride));
+    return ECC_OK;
+}
+
+// Everything behind the checks: result 0 of the form over `count` pairs; pair_terms (nullable, host): count x T rows.
+inline int form_call(ecc_metric* m, const PairForm& f, const int32_t* idx4, int64_t count, float* pair_terms)
+{
+    ColumnCall c;
+    int rc = form_columns(m, f, idx4, count, &c);
+    if (rc) return rc;
+    std::vector<double> totals((size_t)f.S);  // in the order an evaluation of `count` values is added in (ecc_sum_order.h)
+    rc = column_call_finish(m, c, f.S, totals.data(), f.T, m->gram_values_d.ptr, pair_terms);
+    if (rc) return rc;
+    f.finish(totals.data(), count, 0);
+    return ECC_OK;
+}
+inline int form_call_all_pairs(ecc_metric* m, const PairForm& f, float* pair_terms)
+{
+    const int64_t n = m->n_views;
+    return form_call(m, f, nullptr, n * (n - 1) / 2, pair_terms);
+}
+
+// One batch: poses with off[0] = 0 ... off[K] = Q columns over the base matrices `base`, whose columns are in m->gram_values_d
+// (base_c).  sums[2 k], sums[2 k + 1]: the sums of columns 0 and 1 of pose k over all pairs.
+inline int form_pose_batch(ecc_metric* m, const PairForm& f, const double* base, const ColumnCall& base_c, int K, const int32_t* off,
+                           const int32_t* views, const double* moved_Ps, double* sums)
+{
+    ecc_ctx* ctx = m->ctx;
+    const int64_t n = m->n_views, n_pairs = n * (n - 1) / 2;
+    const int Q = off[K];
+    const int64_t entries = n * (int64_t)Q;
+    const int64_t vals_stride = (std::max<int64_t>(entries, 1) + 3) & ~(int64_t)3;
+    volatile uint64_t* out = nullptr;
+    double* out_dev = nullptr;
+    int rc = stage_pose_grid(m, base, K, off, views, moved_Ps, 2 * K, &out, &out_dev);
+    if (!rc) rc = m->pose_values_d.ensure(f.T * vals_stride, ctx->stream);
+    if (!rc) rc = m->pose_partial_d.ensure((int64_t)2 * K * ecc_sum::SLICES, ctx->stream);
+    if (rc) return rc;
+    HIP_TRY(launch_pose_list(m, K, Q, 2 * K));
+    if (entries > 0) {
+        EccPairParams p = base_c.p;  // the sampling mode of an all-pairs evaluation; n_views stays n
+        p.PinvTs = m->pose_PinvTs_d.ptr;
+        p.Cs = m->pose_Cs_d.ptr;
+        p.indices = m->pose_idx_d.ptr;
+        p.records = m->pose_records_d.ptr;
+        p.first = 0;
+        p.count = entries;
+        HIP_TRY(ecc_launch_k01(&p, ctx->stream));
+        HIP_TRY(f.launch(m, p, m->pose_values_d.ptr, vals_stride));
+    }
+    arm_pose_results(out, 2 * K);
+    const int slices = ecc_sum::slices(n_pairs, m->sum_scratch_d.ptr != nullptr);  // the all-pairs call's choice
+    HIP_TRY(ecc_launch_sum_weighted_poses(m->gram_values_d.ptr, base_c.col_stride, n_pairs, (int)n, Q, m->pose_lists_d.ptr, K,
+                                          m->pose_values_d.ptr, vals_stride, slices, m->pose_partial_d.ptr, out_dev, ctx->stream));
+    return wait_pose_results(ctx, out, 2 * K, sums);
+}
+
+// The batched poses of a call; what the batch does not take goes into not_batched.
+inline int form_pose_deltas_batched(ecc_metric* m, const PairForm& f, int n_poses, const int32_t* off, const int32_t* views,
+                                    const double* moved_Ps, std::vector<int>* not_batched)
+{
+    ecc_ctx* ctx = m->ctx;
+    const int64_t n = m->n_views, n_pairs = n * (n - 1) / 2;
+    ecc_mark_busy(m);
+    const double* Pcur = m->Ps_h[m->set_generation & 1].host;
+    const std::vector<double> base(Pcur, Pcur + 12 * n);
+    double base_radius = 0.0;
+    ecc_metric_get_object_radius(m, &base_radius);
+    ColumnCall base_c;
+    int rc = form_columns(m, f, nullptr, n_pairs, &base_c);  // once per call
+    if (rc) return rc;
+    std::vector<double> sums;
+    const int64_t max_cols = std::max<int64_t>(ECC_POSE_BATCH_MAX_ENTRIES / n, ECC_POSE_BATCH_MAX_MOVED);
+    rc = ecc_pose_batches::pack(
+        n_poses, off, views, moved_Ps, max_cols, FORM_BATCH_MAX_POSES,
+        [&](int c, const int32_t* vk, const double* Pk) { return pose_keeps_radius(m, base_radius, c, vk, Pk); },
+        [&](const ecc_pose_batches::Batch& b) -> int {
+            sums.resize(2 * b.pose.size());
+            const int e = form_pose_batch(m, f, base.data(), base_c, (int)b.pose.size(), b.off.data(), b.views.data(), b.Ps.data(), sums.data());
+            if (e) return e;
+            for (size_t q = 0; q < b.pose.size(); ++q) f.finish(&sums[2 * q], n_pairs, b.pose[q]);
+            m->last_batched_poses += (int64_t)b.pose.size();
+            return ECC_OK;
+        },
+        not_batched);
+    if (rc) return rc;
+    HIP_TRY(wait_stream_spin(ctx->stream));  // (the results were seen before the stream's own completion; the scratch is reused)
+    m->done_generation = m->set_generation;
+    m->quiet = true;
+    return ECC_OK;
+}
+
+// Everything of a pose-delta call behind its checks.  evaluate_pose(k): the form's all-pairs call for result k, at the current
+// matrices.
+inline int form_pose_deltas(ecc_metric* m, const PairForm& f, int n_poses, const int32_t* off, const int32_t* views, const double* moved_Ps,
+                            const std::function<int(int)>& evaluate_pose)
+{
+    int rc = set_device(m->ctx);
+    if (rc) return rc;
+    m->last_batched_poses = 0;
+    std::vector<int> rest;
+    if (m->pose_batching) {
+        rc = form_pose_deltas_batched(m, f, n_poses, off, views, moved_Ps, &rest);
+        if (rc) return rc;
+    } else {
+        for (int k = 0; k < n_poses; ++k) rest.push_back(k);
+    }
+    return pose_deltas_sequential(m, rest, off, views, moved_Ps, evaluate_pose);
+}
+
+// One batch: K transforms Ts (16 doubles each) of the base matrices (n x 12).  sums[2 k], sums[2 k + 1]: the sums of columns 0 and
+// 1 of transform k over its cross list; pair_terms (nullable, host): K x count rows of T.  batch_noun: wait_pose_results' word for
+// the batch.
+inline int form_transform_batch(ecc_metric* m, const PairForm& f, const double* base, int n_source, int K, const double* Ts,
+                                const char* batch_noun, double* sums, float* pair_terms)
+{
+    ecc_ctx* ctx = m->ctx;
+    const int T = f.T;
+    const int64_t n = m->n_views, count = (int64_t)n_source * (n - n_source), entries = count * K;
+    const int64_t vals_stride = (entries + 3) & ~(int64_t)3;
+    volatile uint64_t* out = nullptr;
+    double* out_dev = nullptr;
+    int rc = stage_transform_grid(m, base, n_source, K, Ts, 2 * K, &out, &out_dev);
+    if (!rc) rc = m->pose_values_d.ensure(T * vals_stride, ctx->stream);
+    if (!rc) rc = m->pose_partial_d.ensure((int64_t)2 * K * ecc_sum::SLICES, ctx->stream);
+    if (rc) return rc;
+    EccPairParams p;
+    rc = fill_pair_params(m, &p, count, /*need_e1=*/false);  // the sampling mode of a list of `count` tuples
+    if (rc) return rc;
+    HIP_TRY(launch_transform_list(m, n_source, K, (long long)((count + 3) & ~(int64_t)3), 2 * K));
+    p.PinvTs = m->pose_PinvTs_d.ptr;
+    p.Cs = m->pose_Cs_d.ptr;
+    p.indices = m->pose_idx_d.ptr;
+    p.records = m->pose_records_d.ptr;
+    p.first = 0;
+    p.count = entries;
+    if (m->object_radius_mm > 0) HIP_TRY(ecc_launch_k01(&p, ctx->stream));
+    else HIP_TRY(ecc_launch_k01_radii(&p, m->transform_radii_d.ptr, K, ctx->stream));  // every transform the radius of its composed view 0
+    HIP_TRY(f.launch(m, p, m->pose_values_d.ptr, vals_stride));  // (p.n_views stays n: the weight copy of data copy D is n copies behind it)
+    arm_pose_results(out, 2 * K);
+    const int slices = ecc_sum::slices(count, m->sum_scratch_d.ptr != nullptr);  // the list call's choice
+    HIP_TRY(ecc_launch_sum_weighted_transforms(m->pose_values_d.ptr, vals_stride, count, K, slices, m->pose_partial_d.ptr, out_dev, ctx->stream));
+    std::vector<float> cols;
+    if (pair_terms) {
+        cols.resize(T * (size_t)vals_stride);
+        HIP_TRY(hipMemcpyAsync(cols.data(), m->pose_values_d.ptr, sizeof(float) * cols.size(), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    rc = wait_pose_results(ctx, out, 2 * K, sums, batch_noun);
+    if (rc || !pair_terms) return rc;
+    HIP_TRY(wait_stream_spin(ctx->stream));  // the copy behind the sums
+    for (int k = 0; k < K; ++k)
+        for (int64_t q = 0; q < count; ++q)
+            for (int u = 0; u < T; ++u)
+                pair_terms[T * ((size_t)k * count + q) + u] = ecc_transform_grid::value(cols.data() + (size_t)u * vals_stride, q, k, K);
+    return ECC_OK;
+}
+
+// Everything of a transforms call behind its checks.  evaluate_list(k, the cross list, its length, the rows of transform k or
+// null): the form's list call for result k, at the current matrices.
+inline int form_transforms(ecc_metric* m, const PairForm& f, int n_source, int n_transforms, const double* Ts, float* pair_terms,
+                           const char* batch_noun, const std::function<int(int, const int32_t*, int, float*)>& evaluate_list)
+{
+    m->last_batched_transforms = 0;
+    if (n_transforms == 0) return ECC_OK;
+    const int rc = set_device(m->ctx);
+    if (rc) return rc;
+    const int64_t n = m->n_views, count = (int64_t)n_source * (n - n_source);
+    const double* Pcur = m->Ps_h[m->set_generation & 1].host;
+    const std::vector<double> base(Pcur, Pcur + 12 * n);
+    auto rows_of = [&](int64_t k) -> float* { return pair_terms ? pair_terms + f.T * (size_t)k * count : nullptr; };
+    if (!m->pose_batching || count > ECC_POSE_BATCH_MAX_ENTRIES)
+        return transforms_sequential(m, base, n_source, n_transforms, Ts,
+                                     [&](int k, const int32_t* idx, int len) { return evaluate_list(k, idx, len, rows_of(k)); });
+    std::vector<double> sums;
+    return transforms_batched(m, count, n_transforms, FORM_TRANSFORM_BATCH_MAX, [&](int64_t k0, int K) -> int {
+        sums.resize(2 * (size_t)K);
+        const int e = form_transform_batch(m, f, base.data(), n_source, K, Ts + 16 * (size_t)k0, batch_noun, sums.data(), rows_of(k0));
+        if (e) return e;
+        for (int k = 0; k < K; ++k) f.finish(&sums[2 * k], count, k0 + k);
+        return ECC_OK;
+    });
+}
+
+}  // namespace ecc_internal
+
+#endif

@@ -1,5 +1,5 @@
 // ecc_pose_batches.h -- which poses of a pose-delta call go into which batch (host only, no HIP: compiled by
-// tests/c/pose_batches.cpp as well as by ecc_poses.hip, ecc_weighted_poses.hip and ecc_robust_batches.hip).
+// tests/c/pose_batches.cpp as well as by ecc_poses.hip and, through ecc_form_call.h, the weighted and robust pose-delta calls).
 //
 // A call hands over poses as lists of moved views (off, views, moved_Ps: ecc_metric_evaluate_pose_deltas).  A batch is ONE record
 // launch, ONE pair launch and ONE segmented sum over a grid of n x (its columns), a column per (pose, moved view); the packing rule

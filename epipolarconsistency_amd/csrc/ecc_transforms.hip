@@ -23,7 +23,7 @@
 // bits of ecc_metric_set_projections(composed matrices) + ecc_metric_evaluate_pairs(that list) (tests/test_gpu_transforms.py).
 // Nothing of the metric's own state is written: current matrices, device geometry, kept records and values stay; the scratch
 // is the pose batch's (pose_*), which every batch of either kind rewrites from scratch.
-// The two drivers of a call, transforms_batched and transforms_sequential below, are ecc_weighted_transforms.hip's as well
+// The two drivers of a call, transforms_batched and transforms_sequential below, are ecc_form_call.h's as well
 // (DESIGN.md 4.21); the result slots are armed and awaited through ecc_poses.hip's arm_pose_results / wait_pose_results.
 #include "ecc_capi_internal.h"
 #include "ecc_sum_order.h"

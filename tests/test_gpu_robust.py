@@ -341,8 +341,12 @@ def test_errors(gpu_ctx, oracle_mod):
         for bad in ([0, c.n, 0, 1], [-1, 1, 0, 1], [0, 1, c.n, 1], [0, 1, 0, -1]):              # a bad tuple, behind good ones
             lst = np.concatenate([idx[:3], [bad]]).astype(np.int32)
             assert L.ecc_metric_evaluate_robust_pairs(m._h, C.c_void_p(lst.ctypes.data), 4, 0, delta, *out) == 1, bad
+            assert L.ecc_last_error().endswith(b"index array contains invalid indices")        # the robust list's own, short text
+        assert L.ecc_metric_evaluate_robust_pairs(m._h, None, 0, 7, delta, *out) == 1           # an empty list: the checks come first
+        assert L.ecc_metric_evaluate_robust_pairs(m._h, None, 0, 0, -1.0, *out) == 1
         m.useCorrelation(True)
         assert both(m._h, 0, delta) == (5, 5)                                                   # ECC_ERR_UNSUPPORTED
+        assert both(m._h, 0, delta, lst=None, count=0)[1] == 5                                  # ... of an empty list as well
         with pytest.raises(E.EccError) as e:
             m.evaluate_robust(E.LOSS_HUBER, delta)
         assert e.value.code == 5, e.value
@@ -351,11 +355,21 @@ def test_errors(gpu_ctx, oracle_mod):
         none = E.MetricRadonIntermediate(gpu_ctx, None, c.data)                                 # no matrices set
         for other in (one, none):
             assert both(other._h, 0, delta, lst=pidx, count=1) == (1, 1)
+            assert both(other._h, 0, delta, lst=None, count=0)[1] == 1                          # an empty list: the checks come first
             with pytest.raises(E.EccError) as e:
                 other.evaluate_robust(E.LOSS_HUBER, delta)
             assert e.value.code == 1
             other.close()
+        few = E.MetricRadonIntermediate(gpu_ctx, c.Ps, c.data[:-1])                             # fewer intermediates than views
+        assert L.ecc_metric_evaluate_robust(few._h, 0, delta, *out) == 1 and b"fewer Radon intermediates" in L.ecc_last_error()
+        few.close()
         assert value.value == -1.0 and mass.value == -1.0 and np.all(terms == -1.0)            # nothing written by any of them
+        more = E.MetricRadonIntermediate(gpu_ctx, c.Ps, c.data + c.data[:1])                    # D* are bounded by the intermediates held
+        rows = [more.evaluate_robust_pairs(np.array([[0, 1, D0, 1]], np.int32), E.LOSS_HUBER, delta, want_pairs=True)[2] for D0 in (0, c.n)]
+        assert np.array_equal(_u32(rows[0]), _u32(rows[1])) and rows[0][0, 2] > 0
+        with pytest.raises(E.EccError):
+            more.evaluate_robust_pairs(np.array([[0, 1, c.n + 1, 1]], np.int32), E.LOSS_HUBER, delta)
+        more.close()
         again = m.evaluate_robust(E.LOSS_HUBER, delta, want_pairs=True)
         assert _u64(again[0])[()] == _u64(want[0])[()] and np.array_equal(_u32(again[2]), _u32(want[2]))
         m.close()

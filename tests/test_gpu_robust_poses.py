@@ -217,6 +217,7 @@ def test_errors(gpu_ctx):
         assert _same(m.evaluate_robust_pose_deltas([[2]], [P0[3:4]], 0, delta), want)
         values, masses = m.evaluate_robust_pose_deltas([], [], 0, delta)                           # n_poses < 1: ECC_OK
         assert len(values) == 0 and len(masses) == 0
+        assert m.last_batched_poses() == 1                                         # (the call before it; n_poses < 1 returns before the reset)
         here = m.evaluate_robust(0, delta)
         values, masses = m.evaluate_robust_pose_deltas([[]], [np.zeros((0, 12))], 0, delta)        # a pose that moves nothing: the base
         assert _u64(values[0])[()] == _u64(here[0])[()] and _u64(masses[0])[()] == _u64(here[1])[()]

@@ -309,6 +309,7 @@ def test_weights_follow_the_data_index(gpu_ctx, oracle_mod, mode):
 # ---- 7. argument errors ------------------------------------------------------------------------------------------------------------
 def test_errors(gpu_ctx):
     import epipolarconsistency_amd as E
+    from epipolarconsistency_amd import _lib
     n = 6
     s = _Scan(gpu_ctx, n)
     try:
@@ -328,8 +329,15 @@ def test_errors(gpu_ctx):
         raises(1, lambda: m.evaluate_weighted_pose_deltas([[n]], [P0[:1]]))                        # outside [0, n)
         raises(1, lambda: m.evaluate_weighted_pose_deltas([[3, 1]], [P0[:2]]))
         assert m.evaluate_weighted_pairs(np.zeros((0, 4), np.int32)) == (0.0, 0.0)                 # n_pairs == 0: ECC_OK, nothing written
+        assert m.last_batched_poses() == 1                                                         # (want_p's pose)
         values, coverages = m.evaluate_weighted_pose_deltas([], [])
         assert len(values) == 0 and len(coverages) == 0
+        assert m.last_batched_poses() == 1                                                         # n_poses < 1 returns before the count is reset
+        with pytest.raises(E.EccError) as e:
+            m.evaluate_weighted_pairs(np.array([idx[0], [0, 1, 0, n]], np.int32))
+        assert str(e.value).endswith("(matrices and data intermediates lie in [0, n_views))")    # the weighted lists' own text
+        L, empty = _lib.lib(), np.zeros((0, 4), np.int32)
+        assert L.ecc_metric_evaluate_weighted_pairs(m._h, None, -1, None, None, None) == 1 and b"value is null" in L.ecc_last_error()
         base = m.evaluate_weighted()
         values, coverages = m.evaluate_weighted_pose_deltas([[]], [np.zeros((0, 12))])             # a pose that moves nothing: the base
         assert _u64(values[0])[()] == _u64(base[0])[()] and _u64(coverages[0])[()] == _u64(base[1])[()]
@@ -338,6 +346,7 @@ def test_errors(gpu_ctx):
         m.useCorrelation(True)
         raises(5, lambda: m.evaluate_weighted_pairs(idx))                                          # ECC_ERR_UNSUPPORTED
         raises(5, lambda: m.evaluate_weighted_pose_deltas([[2]], [P0[3:4]]))
+        assert m.evaluate_weighted_pairs(empty) == (0.0, 0.0)          # n_pairs == 0 returns before the metric's state is looked at
         m.useCorrelation(False)
         again = m.evaluate_weighted_pairs(idx, want_pairs=True)
         assert again[:2] == want[:2] and np.array_equal(_u32(again[2]), _u32(want[2]))
@@ -346,14 +355,17 @@ def test_errors(gpu_ctx):
             bad = E.MetricRadonIntermediate(gpu_ctx, s.Ps, dtrs)
             raises(1, lambda: bad.evaluate_weighted_pairs(idx))
             raises(1, lambda: bad.evaluate_weighted_pose_deltas([[2]], [P0[3:4]]))
+            assert bad.evaluate_weighted_pairs(empty) == (0.0, 0.0)
             bad.close()
         one = E.MetricRadonIntermediate(gpu_ctx, s.Ps[:1], [s.data[0], s.weights[0]])              # fewer than two views
         raises(1, lambda: one.evaluate_weighted_pairs(np.array([[0, 0, 0, 0]], np.int32)))
         raises(1, lambda: one.evaluate_weighted_pose_deltas([[0]], [P0[:1]]))
+        assert one.evaluate_weighted_pairs(empty) == (0.0, 0.0)
         one.close()
         none = E.MetricRadonIntermediate(gpu_ctx, None, s.data + s.weights)                       # no matrices set
         raises(1, lambda: none.evaluate_weighted_pairs(idx))
         raises(1, lambda: none.evaluate_weighted_pose_deltas([[0]], [P0[:1]]))
+        assert none.evaluate_weighted_pairs(empty) == (0.0, 0.0)
         none.close()
     finally:
         s.close()

@@ -482,6 +482,7 @@ def test_errors_in_the_documented_order(gpu_ctx, oracle_mod):
             lst = np.concatenate([idx[:3], [bad]]).astype(np.int32)
             code, text = pairs(m._h, C.c_void_p(lst.ctypes.data), 4, 0, delta)
             assert code == 1 and b"invalid indices" in text, bad
+            assert text.endswith(b"(matrices and data intermediates lie in [0, n_views))")      # the weighted lists' own text
         # the precedence: list checks < value < loss < delta < use_corr < the number of intermediates < a bad tuple
         lst = np.array([[0, 1, 0, c.n]], np.int32)
         plst = C.c_void_p(lst.ctypes.data)
@@ -490,7 +491,9 @@ def test_errors_in_the_documented_order(gpu_ctx, oracle_mod):
         assert pairs(m._h, plst, 1, 7, -1.0, no_value)[1] == b"value is null"
         assert b"loss" in pairs(m._h, plst, 1, 7, -1.0)[1]
         assert b"delta" in pairs(m._h, plst, 1, 0, -1.0)[1]
+        assert b"loss" in pairs(m._h, None, 0, 7, delta)[1] and b"delta" in pairs(m._h, None, 0, 0, -1.0)[1]   # an empty list: the checks first
         m.useCorrelation(True)
+        assert pairs(m._h, None, 0, 0, delta)[0] == 5
         assert both(m._h, 0, delta) == (5, 5)                                                   # ECC_ERR_UNSUPPORTED
         assert pairs(m._h, plst, 1, 0, delta)[0] == 5 and b"delta" in pairs(m._h, plst, 1, 0, -1.0)[1]
         with pytest.raises(E.EccError) as e:
@@ -502,6 +505,8 @@ def test_errors_in_the_documented_order(gpu_ctx, oracle_mod):
             assert both(other._h, 0, delta) == (1, 1) and b"2 * n_views" in L.ecc_last_error(), len(dtrs)
             code, text = pairs(other._h, plst, 1, 0, delta)
             assert code == 1 and b"2 * n_views" in text, len(dtrs)                               # before the bad tuple
+            code, text = pairs(other._h, None, 0, 0, delta)
+            assert code == 1 and b"2 * n_views" in text, len(dtrs)                               # ... and before an empty list's return
             other.useCorrelation(True)
             assert both(other._h, 0, delta) == (5, 5), len(dtrs)                                # use_corr before the count
             with pytest.raises(E.EccError) as e:
