@@ -179,7 +179,13 @@ def test_dtr_save_load(gpu_ctx, small_scan, tmp_path):
 
 def test_use_correlation(gpu_ctx, oracle_mod, small_scan):
     """useCorrelation(true): 1 - cc per pair (provisional formula, parity unpinned).  1 - cc is
-    a cancellation of two numbers near 1, so it is compared absolutely."""
+    a cancellation of two numbers near 1, so it is compared absolutely.
+    What this test can see: that the switch selects the correlation form and back, that the cost image, the mean and an index
+    list (a reversed tuple included) carry it, and gross errors.  What it cannot: on the consistent small scan the two views'
+    samples agree, cc is within 0.1 of 1 for every pair (asserted on the mean), and there cc is a ratio of nearly proportional
+    sums -- almost any weighting of the samples, a dropped trip or a dropped tail of the range passes the 2e-6 bar.  The
+    weight, the samples' own fold signs, plain data and every loop class of the correlation form are held away from cc = 1 by
+    tests/test_gpu_correlation.py against the float64 statement of tests/correlation_terms.py."""
     import epipolarconsistency_amd as E
     s = small_scan
     dtrs = [E.RadonIntermediate.from_host(gpu_ctx, d, s["n_u"], s["n_v"]) for d in s["dtrs"]]
