@@ -896,6 +896,79 @@ class MetricRadonIntermediate:
                                                           _ptr(pairs)))
         return _with_pairs((value.value, mass.value), pairs, want_pairs)
 
+    def _robust_map_views(self, views):
+        """(the int32 list or None, how many planes a map call returns)"""
+        if views is None:
+            return None, len(self._dtrs)
+        v = np.ascontiguousarray(views, np.int32).reshape(-1)
+        if len(v) == 0:
+            raise ValueError("views: None for every view, or at least one index")
+        return v, len(v)
+
+    def _robust_map_planes(self, k):
+        n_alpha, n_t = (self._dtrs[0].getRadonBinNumber(0), self._dtrs[0].getRadonBinNumber(1)) if self._dtrs else (0, 0)
+        return np.zeros((k, n_t, n_alpha), np.float32), np.zeros((k, n_t, n_alpha), np.float32)
+
+    def evaluate_robust_map(self, loss, delta, views=None, want_pairs=False):
+        """ecc_metric_evaluate_robust_map: evaluate_robust(loss, delta) -- the same bits in value, inlier_mass and pairs -- and WHERE
+        the loss rejected: per mapped view a HITS plane (the bilinear footprints of every sample taken in that view) and a REJ plane
+        (the same footprints times 1 - w, the sample's distrust).  views: indices of the views to map (distinct), None: every view in
+        order.  Returns (value, inlier_mass, hits, rejected[, pairs]); hits, rejected: (len(views), n_t, n_alpha) float32.  The sums
+        are fixed point on the device: the same call gives the same bits.  REJ / HITS is the mean distrust of a line;
+        robust_map_weights turns the held map into line weights.  delta = inf: rejected is all zeros."""
+        n = 0 if self._Ps is None else len(self._Ps)  # (no matrices: the library reports it)
+        v, k = self._robust_map_views(views)
+        if views is None:
+            k = n
+        hits, rejected = self._robust_map_planes(k)
+        value, mass = C.c_double(0.0), C.c_double(0.0)
+        pairs = np.zeros((n * (n - 1) // 2, 3), np.float32) if want_pairs else None
+        check(_lib.lib().ecc_metric_evaluate_robust_map(self._h, int(loss), float(delta), _ptr(v), 0 if v is None else len(v),
+                                                        _ptr(hits), _ptr(rejected), C.byref(value), C.byref(mass), _ptr(pairs)))
+        self._robust_map_count = k
+        return _with_pairs((value.value, mass.value, hits, rejected), pairs, want_pairs)
+
+    def evaluate_robust_map_pairs(self, idx4, loss, delta, views=None, want_pairs=False):
+        """ecc_metric_evaluate_robust_map_pairs: evaluate_robust_map over an index list of (P0, P1, D0, D1) tuples; the view of a
+        sample is the tuple's data index, views (None: every intermediate of the metric) index the intermediates.  A pair listed
+        twice deposits twice; the planes do not depend on the order of the list."""
+        idx = _idx4_list(idx4)
+        v, k = self._robust_map_views(views)
+        hits, rejected = self._robust_map_planes(k)
+        value, mass = C.c_double(0.0), C.c_double(0.0)
+        pairs = np.zeros((len(idx), 3), np.float32) if want_pairs else None
+        check(_lib.lib().ecc_metric_evaluate_robust_map_pairs(self._h, _ptr(idx), len(idx), int(loss), float(delta), _ptr(v),
+                                                              0 if v is None else len(v), _ptr(hits), _ptr(rejected), C.byref(value),
+                                                              C.byref(mass), _ptr(pairs)))
+        self._robust_map_count = k
+        return _with_pairs((value.value, mass.value, hits, rejected), pairs, want_pairs)
+
+    def robust_map_weights(self, min_hits=1.0, gain=1.0):
+        """ecc_metric_robust_map_weights: the map the last evaluate_robust_map[_pairs] call left on the device as line weights, a list of
+        RadonIntermediate (FILTER_NONE, values in [0, 1]), one per mapped view in the order of `views`: the second half of a 2 n
+        metric for evaluate_weighted / evaluate_weighted_robust.  Per bin with the float32 plane values h and r: 1 where h < min_hits,
+        else float32(max(0, 1 - gain * r / h)) in float64.  Raises if no map is held (refresh_dtrs and set_params drop it)."""
+        k = getattr(self, "_robust_map_count", 0)
+        hs = (C.c_void_p * max(k, 1))()
+        check(_lib.lib().ecc_metric_robust_map_weights(self._h, float(min_hits), float(gain), hs))
+        return [RadonIntermediate(self.ctx, C.c_void_p(h)) for h in hs[:k]]
+
+    def robust_map_fixed(self):
+        """ecc_debug_robust_map_fixed: the held map's fixed-point sums (quantum 2^-32) folded to bins, (hits, rejected) of
+        (n_mapped, n_t, n_alpha) uint64 -- integers, so that maps of disjoint lists add exactly."""
+        k = getattr(self, "_robust_map_count", 0)
+        n_alpha, n_t = self._dtrs[0].getRadonBinNumber(0), self._dtrs[0].getRadonBinNumber(1)
+        pitch = slab_floats(n_alpha, n_t) // (n_alpha + 2)
+        raw = np.zeros((2 * max(k, 1), n_alpha + 2, pitch), np.uint64)
+        check(_lib.lib().ecc_debug_robust_map_fixed(self._h, _ptr(raw), raw.size))
+        q = raw[:, :, :n_t + 2].copy()
+        q[:, 1] += q[:, 0]
+        q[:, -2] += q[:, -1]
+        q[:, :, 1] += q[:, :, 0]
+        q[:, :, -2] += q[:, :, -1]
+        bins = np.ascontiguousarray(q[:2 * k, 1:-1, 1:-1].transpose(0, 2, 1))
+        return bins[:k], bins[k:]
+
     def evaluate_weighted_robust(self, loss, delta, want_pairs=False):
         """ecc_metric_evaluate_weighted_robust: line weights and the robust loss together, for scans that have both kinds of bad
         data -- lines somebody flagged (line_weights) and an instrument nobody did.  The metric holds 2 * n_views Radon

@@ -621,6 +621,16 @@ class MetricRadonIntermediate : public Metric {
     ecc_group_metric* m_gh;   // sharded over a group of devices (ecc_group_*), else null
     ecc_ctx* m_ctx;
     ecc_group* m_group;
+    size_t m_map_planes = 0;  // views the map held by the library has (robustMapWeights)
+
+    // the planes of a map call over k views, sized from the first intermediate
+    void sizeMapPlanes(size_t k, std::vector<float>* hits, std::vector<float>* rejected) const
+    {
+        const size_t bins = dtrs.empty() ? 0 : (size_t)dtrs[0]->getRadonBinNumber(0) * (size_t)dtrs[0]->getRadonBinNumber(1);
+        if (hits) hits->assign(k * bins, 0.f);
+        if (rejected) rejected->assign(k * bins, 0.f);
+    }
+    static float* dataOrNull(std::vector<float>* v) { return (v && !v->empty()) ? v->data() : 0x0; }
 
     void push_params()
     {
@@ -934,6 +944,61 @@ public:
         return evaluateRobustPairs(idx, loss, delta, inlier_mass, pair_terms);
     }
 #endif
+
+    /// Not in the reference: ecc_metric_evaluate_robust_map -- evaluateRobust (the same bits in the result, inlier_mass and pair_terms)
+    /// and WHERE the loss rejected: per mapped view a HITS plane (the bilinear footprints of the samples taken in that view) and a REJ
+    /// plane (the same footprints times 1 - w).  views: distinct view indices, empty: every view in order.  hits, rejected (nullable):
+    /// resized to views x n_t x n_alpha floats, alpha fastest.  The sums are fixed point on the device: the same call gives the same
+    /// bits (ecc_hip.h).  Single device only.
+    double evaluateRobustMap(int loss, float delta, const std::vector<int>& views, std::vector<float>* hits, std::vector<float>* rejected,
+                             double* inlier_mass = 0x0, std::vector<float>* pair_terms = 0x0)
+    {
+        if (m_gh) throw std::runtime_error("evaluateRobustMap: not available on a device group");
+        const size_t n = Ps.size();
+        if (pair_terms) pair_terms->assign(3 * (n * (n > 0 ? n - 1 : 0) / 2), 0.f);
+        const std::vector<int32_t> v(views.begin(), views.end());
+        sizeMapPlanes(v.empty() ? n : v.size(), hits, rejected);
+        double value = 0.0;
+        detail::check(ecc_metric_evaluate_robust_map(m_h, loss, delta, v.empty() ? 0x0 : v.data(), (int)v.size(), dataOrNull(hits),
+                                                     dataOrNull(rejected), &value, inlier_mass, dataOrNull(pair_terms)));
+        m_map_planes = v.empty() ? n : v.size();
+        return value;
+    }
+
+    /// Not in the reference: ecc_metric_evaluate_robust_map_pairs -- evaluateRobustMap over an index list of (P0, P1, D0, D1) tuples;
+    /// the view of a sample is the tuple's data index, `views` (empty: every intermediate) index the intermediates.  Single device only.
+    double evaluateRobustMapPairs(const std::vector<int>& indices, int loss, float delta, const std::vector<int>& views,
+                                  std::vector<float>* hits, std::vector<float>* rejected, double* inlier_mass = 0x0,
+                                  std::vector<float>* pair_terms = 0x0)
+    {
+        if (m_gh) throw std::runtime_error("evaluateRobustMapPairs: not available on a device group");
+        if (indices.size() % 4) throw std::runtime_error("evaluateRobustMapPairs: four indices per tuple");
+        const std::vector<int32_t> idx(indices.begin(), indices.end());
+        if (pair_terms) pair_terms->assign(3 * (idx.size() / 4), 0.f);
+        const std::vector<int32_t> v(views.begin(), views.end());
+        sizeMapPlanes(v.empty() ? dtrs.size() : v.size(), hits, rejected);
+        double value = 0.0;
+        if (inlier_mass) *inlier_mass = 0.0;
+        detail::check(ecc_metric_evaluate_robust_map_pairs(m_h, idx.empty() ? 0x0 : idx.data(), (int)(idx.size() / 4), loss, delta,
+                                                           v.empty() ? 0x0 : v.data(), (int)v.size(), dataOrNull(hits), dataOrNull(rejected),
+                                                           &value, inlier_mass, dataOrNull(pair_terms)));
+        m_map_planes = idx.empty() ? 0 : (v.empty() ? dtrs.size() : v.size());
+        return value;
+    }
+
+    /// Not in the reference: ecc_metric_robust_map_weights -- the map the last evaluateRobustMap[Pairs] call left on the device as line
+    /// weights, one intermediate per mapped view (Filter None, values in [0, 1]): the second half of the intermediates of
+    /// evaluateWeighted*.  Per bin with the plane values h and r: 1 where h < min_hits, else max(0, 1 - gain r / h).  The caller owns
+    /// the results.
+    std::vector<RadonIntermediate*> robustMapWeights(float min_hits = 1.0f, float gain = 1.0f)
+    {
+        if (m_gh) throw std::runtime_error("robustMapWeights: not available on a device group");
+        std::vector<ecc_dtr*> hs(m_map_planes ? m_map_planes : 1, (ecc_dtr*)0x0);
+        detail::check(ecc_metric_robust_map_weights(m_h, min_hits, gain, hs.data()));
+        std::vector<RadonIntermediate*> out;
+        for (size_t k = 0; k < m_map_planes; ++k) out.push_back(new RadonIntermediate(hs[k]));
+        return out;
+    }
 
     /// ecc_host_robust_scale: a scale delta for evaluateRobust from the rows {c, u, r} of an earlier call (normally the one with
     /// delta = infinity): k x the median over the pairs with r > 0 of sqrt(r); 0.0 without such a pair.  Touches no device.

@@ -422,6 +422,14 @@ struct ecc_metric {
     // automatic object radius, one float per transform of a batch
     DeviceArray<float> transform_radii_d;
     int64_t last_batched_transforms = 0;  // ecc_metric_last_batched_transforms
+    // ecc_metric_evaluate_robust_map (ecc_robust_map.hip): the fixed-point planes of a call (zeroed per call, grown geometrically), the
+    // per-intermediate plane table, and the float planes of the LAST map call -- HITS of every mapped view, then REJ -- which
+    // ecc_metric_robust_map_weights reads; dropped (map_valid) by ecc_metric_refresh_dtrs and ecc_metric_set_params
+    DeviceArray<unsigned long long> map_fixed_d;
+    DeviceArray<int32_t> map_slot_d;
+    DeviceArray<float> map_planes_d;
+    int map_n_mapped = 0;
+    bool map_valid = false;
     // ecc_debug_step_stamps: host clock (seconds, steady) at fixed points of the last set_projections / synchronous evaluation
     double stamps[ECC_STEP_STAMPS] = {0};
 };
@@ -444,6 +452,8 @@ int radon_check_args(ecc_ctx* ctx, const float* image, int n, int n_u, int n_v, 
                      ecc_dtr** out);
 int radon_launch_stack(ecc_ctx* ctx, const float* images_d, int n, int n_u, int n_v, int n_alpha, int n_t, int filter, int post,
                        float* slabs, int64_t slab_stride);
+// ecc_line_weights.hip: n line-weight handles (FILTER_NONE) over one slab stack, slab k at owner->ptr + k * ecc_layout_floats
+int make_weight_handles(ecc_ctx* ctx, const std::shared_ptr<Slab>& owner, int n, int n_alpha, int n_t, int n_u, int n_v, ecc_dtr** out);
 void arm_result(ecc_metric* m);
 hipError_t wait_result(ecc_metric* m, hipStream_t stream, double* value);
 int set_device(const ecc_ctx* ctx);

@@ -87,8 +87,11 @@ int launch_stack(ecc_ctx* ctx, const float* flagged_d, int n, int n_u, int n_v, 
     return ECC_OK;
 }
 
-// n handles over one slab stack
-int make_handles(ecc_ctx* ctx, const std::shared_ptr<Slab>& owner, int n, int n_alpha, int n_t, int n_u, int n_v, ecc_dtr** out)
+}  // namespace
+
+namespace ecc_internal {
+// n line-weight handles over one slab stack (ecc_robust_map.hip makes its weights' handles here too)
+int make_weight_handles(ecc_ctx* ctx, const std::shared_ptr<Slab>& owner, int n, int n_alpha, int n_t, int n_u, int n_v, ecc_dtr** out)
 {
     const int64_t slab = ecc_layout_floats(n_alpha, n_t);
     std::vector<ecc_dtr*> made;
@@ -113,8 +116,7 @@ int make_handles(ecc_ctx* ctx, const std::shared_ptr<Slab>& owner, int n, int n_
     for (int k = 0; k < n; ++k) out[k] = made[k];
     return ECC_OK;
 }
-
-}  // namespace
+}  // namespace ecc_internal
 
 ECC_EXPORT void ecc_line_weights_defaults(ecc_line_weights_config* cfg)
 {
@@ -149,7 +151,7 @@ ECC_EXPORT int ecc_radon_line_weights(ecc_ctx* ctx, const float* flagged, int on
     if (staging || rc) (void)hipStreamSynchronize(ctx->stream);
     if (staging) (void)hipFree(staging);
     if (rc) return rc;
-    return make_handles(ctx, owner, n, n_alpha, n_t, n_u, n_v, out);
+    return make_weight_handles(ctx, owner, n, n_alpha, n_t, n_u, n_v, out);
 }
 
 ECC_EXPORT int ecc_radon_line_weights_into(ecc_ctx* ctx, const float* flagged_d, int n, int n_u, int n_v, int n_alpha, int n_t,
@@ -185,5 +187,5 @@ ECC_EXPORT int ecc_dtr_line_weights(ecc_ctx* ctx, const ecc_dtr* lengths, const 
     HIP_TRY(hipMalloc((void**)&owner->ptr, (size_t)slab * sizeof(float)));
     HIP_TRY(ecc_launch_clip_min(lengths->base, slab, owner->ptr, slab, 1, lengths->n_alpha, lengths->n_t, lengths->pitch, use.guard_bins,
                                 use.zero_at_px, ctx->stream));
-    return make_handles(ctx, owner, 1, lengths->n_alpha, lengths->n_t, lengths->n_u, lengths->n_v, out);
+    return make_weight_handles(ctx, owner, 1, lengths->n_alpha, lengths->n_t, lengths->n_u, lengths->n_v, out);
 }

@@ -161,6 +161,7 @@ ECC_EXPORT int ecc_metric_refresh_dtrs(ecc_metric* m, int first, int count)
     if (first < 0 || count < 0 || first > n || count > n - first) return fail(ECC_ERR_INVALID_ARGUMENT, "dtr range outside the metric's list");
     if (count == 0) return ECC_OK;
     m->cache.valid = false;
+    m->map_valid = false;  // the held robust map belongs to the old contents
     int rc = set_device(m->ctx);
     if (rc) return rc;
     const int64_t paired_floats = (int64_t)(m->n_alpha + 1) * m->pitch * 2;
@@ -303,6 +304,7 @@ ECC_EXPORT int ecc_metric_set_params(ecc_metric* m, double object_radius_mm, dou
     m->dkappa = dkappa;
     m->use_corr = use_corr;
     m->cache.valid = false;
+    m->map_valid = false;  // the held robust map belongs to the old parameters
     return ECC_OK;
 }
 
@@ -332,7 +334,8 @@ ECC_EXPORT int ecc_metric_device_bytes(const ecc_metric* m, int64_t* paired_byte
                           m->PinvTs_d.bytes() + m->pair_values_d.bytes() + m->cost_d.bytes() + m->indices_d.bytes() + m->K01_d.bytes() +
                           m->records_d.bytes() + m->cache_values_d.bytes() + m->pose_PinvTs_d.bytes() + m->pose_Cs_d.bytes() +
                           m->pose_idx_d.bytes() + m->pose_values_d.bytes() + m->pose_records_d.bytes() + m->pose_partial_d.bytes() +
-                          m->pose_lists_d.bytes() + m->transform_radii_d.bytes() + m->sum_scratch_d.bytes() + m->sum_d.bytes();
+                          m->pose_lists_d.bytes() + m->transform_radii_d.bytes() + m->sum_scratch_d.bytes() + m->sum_d.bytes() +
+                          m->map_fixed_d.bytes() + m->map_planes_d.bytes() + m->map_slot_d.bytes();
     if (paired_bytes) *paired_bytes = m->paired_d.bytes();
     if (quad_bytes) *quad_bytes = m->quads_d.bytes();
     if (other_bytes) *other_bytes = other;

@@ -803,6 +803,52 @@ int ecc_metric_evaluate_robust_pairs(ecc_metric* m, const int32_t* idx4, int n_p
                                      double* inlier_mass, float* pair_terms);
 double ecc_host_robust_scale(const float* pair_terms, int64_t n_pairs, double k);
 
+/* Where the robust loss rejects (csrc/ecc_robust_map.hip, csrc/robust_map_kernel.hip): ecc_metric_evaluate_robust
+ * with every sample's distrust, 1 - w, accumulated where the sample was taken, in each view's own Radon space.
+ *
+ * ecc_metric_evaluate_robust_map / _map_pairs take the metric, loss, delta (+infinity allowed), value, inlier_mass and pair_terms of
+ * ecc_metric_evaluate_robust / _robust_pairs and return THEIR BITS in them: the kernel forms the same positions, residuals d,
+ * weights w and per-lane sums in the same order.  Beside that, per +-kappa sample of a pair and per view of the pair that is MAPPED:
+ * the sample's 2 x 2 footprint -- the clamped cells (i0, i1) x (j0, j1) its gather reads, with the fractions fx (angle) and fy
+ * (distance) -- and b = (1 - fx)(1 - fy), fx (1 - fy), (1 - fx) fy, fx fy, float32 products,
+ *     HITS[cell] += b          REJ[cell] += b * (1 - w)          ((1 - w) and the product float32)
+ * in that view's planes; view i's two samples of a kappa step lie in view i's planes and view j's in view j's; clamped cells that
+ * coincide receive both deposits (the map is the adjoint of the sampling).  On the device the planes are unsigned 64-bit fixed
+ * point with quantum 2^-32 (a deposit is the float32 value times 2^32, exact), summed with integer atomics: the same arguments give
+ * the same bits on every call, in any order of an index list.  hits, rejected (host, either may be NULL): n_mapped planes of
+ * n_t x n_alpha floats, alpha fastest, plane k for views[k]; an entry is (float)((double)q * 2^-32).
+ *   views, n_mapped   distinct indices of Radon intermediates, in [0, n_views) for the all-pairs call and in [0, n_dtrs) for the list
+ *                     call, where the view of a sample is the tuple's data index (D0 or D1); n_mapped == 0: every one, in order.
+ *                     A view that is not listed receives nothing and costs nothing.  A pair listed twice deposits twice.
+ *   delta = +infinity REJ is exactly 0 everywhere, value has ecc_metric_evaluate_all's bits.
+ * Memory: 16 bytes per padded bin and mapped view on the device, owned by the metric, grown geometrically, freed with it, plus the
+ * float planes (8 bytes per bin and mapped view), which the metric HOLDS until the next map call, ecc_metric_refresh_dtrs or
+ * ecc_metric_set_params.
+ *   - Errors before anything is launched or written, in this order: those of ecc_metric_evaluate_robust[_pairs] in their order
+ *     (use_corr: ECC_ERR_UNSUPPORTED); then n_mapped < 0, views == NULL with n_mapped > 0, an index out of range, a duplicate:
+ *     ECC_ERR_INVALID_ARGUMENT.  After them the list call with n_pairs == 0 is ECC_OK: planes of zeros, no map held.
+ * Launches: the record kernel, the planes' memset, pairs_robust_map_kernel (the reference kernels under the reference arithmetic)
+ * between the timing events, the sums of c and u, robust_map_finish_kernel, the copies, one wait.  A diagnostic, meant to be called
+ * once per outer iteration of an optimiser: the deposits are 8 to 16 atomics per sample and mapped view.
+ *
+ * ecc_metric_robust_map_weights: the held map as line weights, one intermediate per mapped view in out[0 .. n_mapped), handles of the
+ * kind ecc_dtr_line_weights returns (release them with ecc_dtr_destroy), ready to be the second half of a 2 n metric.  With h and r
+ * the float32 plane values of a bin: mu = 1.0f where h < min_hits, else (float)fmax(0.0, 1.0 - (double)gain * ((double)r / (double)h))
+ * -- every operation an IEEE float64 one.  One elementwise launch, no wait.
+ *   - Errors, ECC_ERR_INVALID_ARGUMENT: m == NULL, out == NULL, min_hits or gain negative or not finite; no map held (no map call yet,
+ *     or the map was dropped by ecc_metric_refresh_dtrs / ecc_metric_set_params).
+ * Not built: the map's batches of pose deltas and of transforms, its range, group and RCCL forms; the map under line weights (a 2 n
+ * metric) and under use_corr; an IRLS loop inside the library. */
+int ecc_metric_evaluate_robust_map(ecc_metric* m, int loss, float delta, const int32_t* views, int n_mapped, float* hits, float* rejected,
+                                   double* value, double* inlier_mass, float* pair_terms);
+int ecc_metric_evaluate_robust_map_pairs(ecc_metric* m, const int32_t* idx4, int n_pairs, int loss, float delta, const int32_t* views,
+                                         int n_mapped, float* hits, float* rejected, double* value, double* inlier_mass, float* pair_terms);
+int ecc_metric_robust_map_weights(ecc_metric* m, float min_hits, float gain, ecc_dtr** out);
+/* Debug: the fixed-point sums of the held map themselves -- every HITS plane, then every REJ plane, each (n_alpha + 2) rows of
+ * `pitch` cells in the padded geometry of a Radon intermediate on the device (cell (row, bin) for the bin (row - 1, bin - 1), the
+ * border rows and columns folding into the clamped bins); capacity in cells.  For tests that add maps in fixed point. */
+int ecc_debug_robust_map_fixed(ecc_metric* m, uint64_t* out, int64_t capacity);
+
 /* The robust loss for optimisers (csrc/ecc_robust_batches.hip): a population of poses or of source-to-target
  * transforms per call, as ecc_metric_evaluate_pose_deltas / ecc_metric_evaluate_transforms take them for the plain metric and the
  * weighted siblings for line weights.  The losses, delta, the three float32 columns {c, u, r} per pair and the value convention are
