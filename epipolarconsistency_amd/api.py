@@ -969,6 +969,58 @@ class MetricRadonIntermediate:
         bins = np.ascontiguousarray(q[:2 * k, 1:-1, 1:-1].transpose(0, 2, 1))
         return bins[:k], bins[k:]
 
+    def _weighted_map_views(self, views):
+        """(the int32 list or None, how many planes a weighted map call returns): None maps the n_views data intermediates"""
+        if views is None:
+            return None, len(self._dtrs) // 2
+        return self._robust_map_views(views)
+
+    def evaluate_weighted_robust_map(self, loss, delta, views=None, want_pairs=False):
+        """ecc_metric_evaluate_weighted_robust_map: evaluate_weighted_robust(loss, delta) on a 2 * n_views metric -- the same bits in
+        value, coverage, inlier_mass and pairs -- and WHERE the loss rejected under the metric's line weights: per mapped view a
+        HITS plane, the bilinear footprints of every sample taken in that view times the sample's weight product mu = W_i W_j, and a
+        REJ plane, the same times 1 - w.  REJ / HITS is the rejected share among the lines the weights trust.  views: data indices
+        in [0, n_views) (distinct), None: every view in order.  Returns (value, coverage, inlier_mass, hits, rejected[, pairs]);
+        hits, rejected: (len(views), n_t, n_alpha) float32, pairs (n_pairs, 4) rows {c, u, k, r}.  Fixed-point sums on the device:
+        the same call gives the same bits.  weighted_robust_map_weights multiplies the held map's factor into the weights it was
+        made under.  Weights outside [0, 1]: value, coverage, inlier_mass and pairs as evaluate_weighted_robust, planes unspecified."""
+        n = 0 if self._Ps is None else len(self._Ps)  # (no matrices: the library reports it)
+        v, k = self._weighted_map_views(views)
+        hits, rejected = self._robust_map_planes(k)
+        value, coverage, mass = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
+        pairs = np.zeros((n * (n - 1) // 2, 4), np.float32) if want_pairs else None
+        check(_lib.lib().ecc_metric_evaluate_weighted_robust_map(self._h, int(loss), float(delta), _ptr(v), 0 if v is None else len(v),
+                                                                 _ptr(hits), _ptr(rejected), C.byref(value), C.byref(coverage),
+                                                                 C.byref(mass), _ptr(pairs)))
+        self._robust_map_count = k
+        return _with_pairs((value.value, coverage.value, mass.value, hits, rejected), pairs, want_pairs)
+
+    def evaluate_weighted_robust_map_pairs(self, idx4, loss, delta, views=None, want_pairs=False):
+        """ecc_metric_evaluate_weighted_robust_map_pairs: evaluate_weighted_robust_map over an index list of (P0, P1, D0, D1) tuples
+        as evaluate_weighted_robust_pairs takes them: D0, D1 and `views` index the data intermediates, in [0, n_views); weight and
+        map follow the data index.  A pair listed twice deposits twice; the planes do not depend on the order of the list."""
+        idx = _idx4_list(idx4)
+        v, k = self._weighted_map_views(views)
+        hits, rejected = self._robust_map_planes(k)
+        value, coverage, mass = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
+        pairs = np.zeros((len(idx), 4), np.float32) if want_pairs else None
+        check(_lib.lib().ecc_metric_evaluate_weighted_robust_map_pairs(self._h, _ptr(idx), len(idx), int(loss), float(delta), _ptr(v),
+                                                                       0 if v is None else len(v), _ptr(hits), _ptr(rejected),
+                                                                       C.byref(value), C.byref(coverage), C.byref(mass), _ptr(pairs)))
+        self._robust_map_count = k
+        return _with_pairs((value.value, coverage.value, mass.value, hits, rejected), pairs, want_pairs)
+
+    def weighted_robust_map_weights(self, min_hits=1.0, gain=1.0):
+        """ecc_metric_weighted_robust_map_weights: the next pass's line weights from the map the last
+        evaluate_weighted_robust_map[_pairs] call left on the device -- a list of RadonIntermediate (FILTER_NONE), one per mapped
+        view in the order of `views`: W_v * factor in float32, W_v the metric's current weights of that view and factor
+        robust_map_weights' rule on the held planes (1 where h < min_hits, else float32(max(0, 1 - gain * r / h)) in float64).
+        Raises if no map is held or the held map is evaluate_robust_map's."""
+        k = getattr(self, "_robust_map_count", 0)
+        hs = (C.c_void_p * max(k, 1))()
+        check(_lib.lib().ecc_metric_weighted_robust_map_weights(self._h, float(min_hits), float(gain), hs))
+        return [RadonIntermediate(self.ctx, C.c_void_p(h)) for h in hs[:k]]
+
     def evaluate_weighted_robust(self, loss, delta, want_pairs=False):
         """ecc_metric_evaluate_weighted_robust: line weights and the robust loss together, for scans that have both kinds of bad
         data -- lines somebody flagged (line_weights) and an instrument nobody did.  The metric holds 2 * n_views Radon
@@ -1659,6 +1711,53 @@ def weighted_robust_scale(pair_terms, k=1.0):
     if rows.ndim != 2 or rows.shape[1] != 4:
         raise ValueError("pair_terms must be (n_pairs, 4) rows {c, u, k, r}")
     return float(_lib.lib().ecc_host_weighted_robust_scale(C.c_void_p(rows.ctypes.data) if len(rows) else None, len(rows), float(k)))
+
+
+def refine_line_weights(ctx, Ps, data, weights=None, loss=_lib.LOSS_TRUNCATED, k=0.5, passes=2, min_hits=1.0, gain=1.0, sampling="auto"):
+    """Line weights from the robust loss, iterated: the loss says where it rejects, the map becomes line weights, and the next pass
+    maps the metric under those weights.  data: the n Radon intermediates of the views Ps; weights: n line-weight
+    intermediates to start from (a collimator flag from line_weights, say) or None.  Pass 1 is evaluate_robust_map +
+    robust_map_weights on the n-metric when weights is None, otherwise evaluate_weighted_robust_map + weighted_robust_map_weights
+    on the 2 n metric over `weights`; every later pass is the weighted map on a 2 n metric over the previous pass's weights.
+    delta = k x robust_scale / weighted_robust_scale of the first pass's rows at delta = inf and is then held: a scale taken again
+    from the weighted rows shrinks with the weights, and the iteration degrades from the third pass on.  Returns (the final n weight
+    intermediates -- the caller closes them --, one dict per pass: delta, coverage, inlier_mass, rejected_share (n,) = sum REJ /
+    sum HITS per view, 0 where a view has no hits).  Every metric and every intermediate weight set made here is closed."""
+    data = list(data)
+    n = len(data)
+    if int(passes) < 1:
+        raise ValueError("passes must be at least 1")
+    if weights is not None and len(weights) != n:
+        raise ValueError("weights: one intermediate per view, or None")
+    current, owned = (None if weights is None else list(weights)), False
+    delta, records = None, []
+    try:
+        for _ in range(int(passes)):
+            m = MetricRadonIntermediate(ctx, Ps, data if current is None else data + current).setSampling(sampling)
+            try:
+                if current is None:
+                    delta = robust_scale(m.evaluate_robust(loss, float("inf"), want_pairs=True)[2], k)
+                    _, mass, hits, rej = m.evaluate_robust_map(loss, delta)
+                    coverage, new = 1.0, m.robust_map_weights(min_hits, gain)
+                else:
+                    if delta is None:
+                        delta = weighted_robust_scale(m.evaluate_weighted_robust(loss, float("inf"), want_pairs=True)[3], k)
+                    _, coverage, mass, hits, rej = m.evaluate_weighted_robust_map(loss, delta)
+                    new = m.weighted_robust_map_weights(min_hits, gain)
+            finally:
+                m.close()
+            if owned:
+                for w in current:
+                    w.close()
+            current, owned = new, True
+            h, r = hits.astype(np.float64).sum(axis=(1, 2)), rej.astype(np.float64).sum(axis=(1, 2))
+            records.append(dict(delta=delta, coverage=coverage, inlier_mass=mass, rejected_share=np.where(h > 0, r / np.where(h > 0, h, 1.0), 0.0)))
+    except BaseException:
+        if owned:
+            for w in current:
+                w.close()
+        raise
+    return current, records
 
 
 def _line_weights_config(zero_at_px, guard_bins, dilate_px):

@@ -1065,6 +1065,63 @@ public:
         return ecc_host_weighted_robust_scale(pair_terms.empty() ? 0x0 : pair_terms.data(), (int64_t)(pair_terms.size() / 4), k);
     }
 
+    /// Not in the reference: ecc_metric_evaluate_weighted_robust_map -- evaluateWeightedRobust (the same bits in the result, coverage,
+    /// inlier_mass and pair_terms) and WHERE the loss rejected under the metric's line weights: per mapped view a HITS plane (the
+    /// footprints of the samples taken in that view times the sample's weight product) and a REJ plane (the same times 1 - w).
+    /// views: distinct data indices in [0, n_views), empty: every view in order.  hits, rejected (nullable): resized to views x n_t x
+    /// n_alpha floats, alpha fastest.  Fixed-point sums on the device: the same call gives the same bits (ecc_hip.h).  Single device only.
+    double evaluateWeightedRobustMap(int loss, float delta, const std::vector<int>& views, std::vector<float>* hits,
+                                     std::vector<float>* rejected, double* coverage = 0x0, double* inlier_mass = 0x0,
+                                     std::vector<float>* pair_terms = 0x0)
+    {
+        if (m_gh) throw std::runtime_error("evaluateWeightedRobustMap: not available on a device group");
+        const size_t n = Ps.size();
+        if (pair_terms) pair_terms->assign(4 * (n * (n > 0 ? n - 1 : 0) / 2), 0.f);
+        const std::vector<int32_t> v(views.begin(), views.end());
+        sizeMapPlanes(v.empty() ? n : v.size(), hits, rejected);
+        double value = 0.0;
+        detail::check(ecc_metric_evaluate_weighted_robust_map(m_h, loss, delta, v.empty() ? 0x0 : v.data(), (int)v.size(), dataOrNull(hits),
+                                                              dataOrNull(rejected), &value, coverage, inlier_mass, dataOrNull(pair_terms)));
+        m_map_planes = v.empty() ? n : v.size();
+        return value;
+    }
+
+    /// Not in the reference: ecc_metric_evaluate_weighted_robust_map_pairs -- evaluateWeightedRobustMap over an index list of
+    /// (P0, P1, D0, D1) tuples as evaluateWeightedRobustPairs takes them; D0, D1 and `views` (empty: every view) index the data
+    /// intermediates, in [0, n_views).  Single device only.
+    double evaluateWeightedRobustMapPairs(const std::vector<int>& indices, int loss, float delta, const std::vector<int>& views,
+                                          std::vector<float>* hits, std::vector<float>* rejected, double* coverage = 0x0,
+                                          double* inlier_mass = 0x0, std::vector<float>* pair_terms = 0x0)
+    {
+        if (m_gh) throw std::runtime_error("evaluateWeightedRobustMapPairs: not available on a device group");
+        if (indices.size() % 4) throw std::runtime_error("evaluateWeightedRobustMapPairs: four indices per tuple");
+        const std::vector<int32_t> idx(indices.begin(), indices.end());
+        if (pair_terms) pair_terms->assign(4 * (idx.size() / 4), 0.f);
+        const std::vector<int32_t> v(views.begin(), views.end());
+        sizeMapPlanes(v.empty() ? Ps.size() : v.size(), hits, rejected);
+        double value = 0.0;
+        if (coverage) *coverage = 0.0;
+        if (inlier_mass) *inlier_mass = 0.0;
+        detail::check(ecc_metric_evaluate_weighted_robust_map_pairs(m_h, idx.empty() ? 0x0 : idx.data(), (int)(idx.size() / 4), loss, delta,
+                                                                    v.empty() ? 0x0 : v.data(), (int)v.size(), dataOrNull(hits),
+                                                                    dataOrNull(rejected), &value, coverage, inlier_mass, dataOrNull(pair_terms)));
+        m_map_planes = idx.empty() ? 0 : (v.empty() ? Ps.size() : v.size());
+        return value;
+    }
+
+    /// Not in the reference: ecc_metric_weighted_robust_map_weights -- the next pass's line weights from the map the last
+    /// evaluateWeightedRobustMap[Pairs] call left on the device, one intermediate per mapped view (Filter None): the view's current
+    /// weights times the factor of robustMapWeights' rule on the held planes.  The caller owns the results.
+    std::vector<RadonIntermediate*> weightedRobustMapWeights(float min_hits = 1.0f, float gain = 1.0f)
+    {
+        if (m_gh) throw std::runtime_error("weightedRobustMapWeights: not available on a device group");
+        std::vector<ecc_dtr*> hs(m_map_planes ? m_map_planes : 1, (ecc_dtr*)0x0);
+        detail::check(ecc_metric_weighted_robust_map_weights(m_h, min_hits, gain, hs.data()));
+        std::vector<RadonIntermediate*> out;
+        for (size_t k = 0; k < m_map_planes; ++k) out.push_back(new RadonIntermediate(hs[k]));
+        return out;
+    }
+
     /// Not in the reference: ecc_metric_evaluate_weighted_pose_deltas -- evaluatePoseDeltas for the metric with per-line weights
     /// (intermediates as for evaluateWeighted).  values[k] and coverages[k] (coverages nullable) are bit-identical to replacing the
     /// views moved_views[k] by moved_Ps[k], setProjectionMatrices and evaluateWeighted(); the current matrices stay.  Single device only.

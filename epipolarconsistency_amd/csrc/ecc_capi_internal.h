@@ -430,6 +430,10 @@ struct ecc_metric {
     DeviceArray<float> map_planes_d;
     int map_n_mapped = 0;
     bool map_valid = false;
+    // which kind of map is held: ecc_metric_evaluate_weighted_robust_map's (ecc_weighted_robust_map.hip: deposits under the line
+    // weights of a 2 n metric) or the n-metric's; map_slot_d is the plane table (map_n_slots entries), then the mapped intermediates
+    bool map_weighted = false;
+    int map_n_slots = 0;
     // ecc_debug_step_stamps: host clock (seconds, steady) at fixed points of the last set_projections / synchronous evaluation
     double stamps[ECC_STEP_STAMPS] = {0};
 };
@@ -500,6 +504,8 @@ int channel_form_check(const ecc_metric* m, int n_channels, const char* range_te
 int weighted_check(const ecc_metric* m);
 // ecc_robust.hip: the argument checks of the robust calls (value: the required result pointer)
 int robust_check(const ecc_metric* m, const double* value, int loss, float delta);
+// ecc_weighted_robust.hip: robust_check's conditions, then weighted_check's
+int weighted_robust_check(const ecc_metric* m, const double* value, int loss, float delta);
 
 // The distance of two channels' row-paired and row-quad copies, for the pair forms that read more than one copy per view (g: any
 // of their parameter structs).

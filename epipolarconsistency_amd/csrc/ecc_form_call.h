@@ -51,6 +51,9 @@ struct PairForm {
 PairForm weighted_form(double* values, double* coverages);
 // ecc_robust.hip: T = 3, S = 2, columns {c, u, r}; values[k] = sum c / count, inlier_masses[k] (nullable) = sum u / count
 PairForm robust_form(int loss, float delta, double* values, double* inlier_masses);
+// ecc_weighted_robust.hip: T = 4, S = 3, columns {c, u, k, r}; values[k] = sum c / sum u, coverages[k] (nullable) = sum u / count,
+// inlier_masses[k] (nullable) = sum k / sum u
+PairForm weighted_robust_form(int loss, float delta, double* values, double* coverages, double* inlier_masses);
 
 // poses per batch: the sum's grid is slices x poses x 2 columns, half a million workgroups at most
 constexpr size_t FORM_BATCH_MAX_POSES = (1 << 19) / (2 * ecc_sum::SLICES);

@@ -1,5 +1,6 @@
-// ecc_robust_map.h -- what robust_map_kernel.hip and ecc_robust_map.hip share: the parameters of the map launch and the geometry of
-// its planes.
+// ecc_robust_map.h -- what the two map kernels (robust_map_kernel.hip, weighted_robust_map_kernel.hip) and their host files
+// (ecc_robust_map.hip, ecc_weighted_robust_map.hip) share: the parameters of the map launches, the geometry of the planes, the
+// deposits (for the kernel files) and the launch sequence of a map call (for the host files).
 //
 // The map of a view is two planes, HITS and REJ, of unsigned 64-bit fixed point with quantum 2^-32.  On the device a plane has the
 // geometry of the view's slab (ecc_layout.h): (n_alpha + 2) rows of `pitch` cells, cell (row, bin) for the padded element
@@ -26,6 +27,22 @@ struct EccRobustMapParams {
     int64_t rej_cells;           // cells from a view's HITS plane to its REJ plane: mapped views * plane_cells
 };
 
+// The map under line weights (weighted_robust_map_kernel.hip): EccWeightedRobustParams' fields -- 2 n_views channel-major
+// intermediates, four columns {c, u, k, r} -- then the planes as above; slot_of has n_views entries, one per DATA intermediate.
+struct EccWeightedRobustMapParams {
+    int64_t paired_channel_bytes;  // as in EccGramParams
+    int64_t quad_channel_bytes;
+    float* values;                 // 4 columns of col_stride floats
+    int64_t col_stride;
+    int loss;
+    float delta;
+    float inv_delta;
+    unsigned long long* planes;
+    const int32_t* slot_of;
+    int64_t plane_cells;
+    int64_t rej_cells;
+};
+
 #if defined(__HIPCC__)
 extern "C" hipError_t ecc_launch_pairs_robust_map(const EccPairParams* p, const EccRobustMapParams* g, hipStream_t stream);
 // fixed[n_planes][plane_cells] -> out[n_planes][n_t][n_alpha] floats, (float)((double)q * 2^-32) of the folded sums
@@ -34,6 +51,98 @@ extern "C" hipError_t ecc_launch_robust_map_finish(const unsigned long long* fix
 // hits, rejected: n_views float planes each (n_t x n_alpha) -> n_views weight slabs in the private layout, written completely
 extern "C" hipError_t ecc_launch_robust_map_weights(const float* hits, const float* rejected, float* slabs, int n_views, int n_alpha, int n_t,
                                                     int pitch, float min_hits, float gain, hipStream_t stream);
+extern "C" hipError_t ecc_launch_pairs_weighted_robust_map(const EccPairParams* p, const EccWeightedRobustMapParams* g, hipStream_t stream);
+// slabs[k] = weights[views[k]] * factor(hits[k], rejected[k]) per padded element, k in [0, n_mapped): weights are the slabs of the
+// metric's weight intermediates (device table), views the mapped data indices (device), written completely
+extern "C" hipError_t ecc_launch_weighted_robust_map_weights(const float* hits, const float* rejected, const float* const* weights,
+                                                             const int32_t* views, float* slabs, int n_mapped, int n_alpha, int n_t, int pitch,
+                                                             float min_hits, float gain, hipStream_t stream);
+#endif
+
+// ---- the deposits: for the kernel files, behind ecc_pair_forms.h ---------------------------------------------------------------
+#if defined(ECC_PAIR_FORMS_H)
+namespace {
+
+// a deposit in fixed point: exact for a float32 in [0, 2^32)
+__device__ __forceinline__ void deposit(unsigned long long* cell, float x)
+{
+    atomicAdd(cell, (unsigned long long)(x * 4294967296.0f));
+}
+
+// The footprint of one sample into the HITS plane `hits` and the REJ plane `rej_cells` cells behind it.  c00 = (i0, j0), c10 = (i1, j0),
+// c01 = (i0, j1), c11 = (i1, j1) as cell indices; fx runs over i (angle rows), fy over j (distance bins).  mu: the sample's product of
+// line weights, one float32 multiply per cell (the literal 1.0f for the map without weights: x * 1.0f is x and the compiler drops
+// both the multiply and the test).  Deposits of zero are skipped, they change no bit: all of them where mu == 0.0f, the REJ half
+// where w == 1.0f.  No address depends on mu or w.
+__device__ __forceinline__ void deposit_footprint(unsigned long long* hits, long long rej_cells, unsigned c00, unsigned c10, unsigned c01,
+                                                  unsigned c11, float fx, float fy, float w, float mu)
+{
+    if (mu == 0.0f) return;
+    const float gx = 1.0f - fx, gy = 1.0f - fy;
+    const float b00 = (gx * gy) * mu, b10 = (fx * gy) * mu, b01 = (gx * fy) * mu, b11 = (fx * fy) * mu;
+    deposit(hits + c00, b00);
+    deposit(hits + c10, b10);
+    deposit(hits + c01, b01);
+    deposit(hits + c11, b11);
+    if (w != 1.0f) {
+        const float q = 1.0f - w;
+        unsigned long long* rej = hits + rej_cells;
+        deposit(rej + c00, b00 * q);
+        deposit(rej + c10, b10 * q);
+        deposit(rej + c01, b01 * q);
+        deposit(rej + c11, b11 * q);
+    }
+}
+
+// What a map form knows of its planes (wave-uniform, set in the form's begin hook), and the deposits of the three loop kinds.
+struct MapPlanes {
+    long long rej_cells;        // cells from a HITS plane to its REJ plane
+    unsigned pitch, last_cell;  // cells per row; the last cell of a plane
+
+    // a footprint whose first cell is `cell` of the padded plane: the gather's own four cells (never past the plane: a footprint the
+    // gather may read lies inside the paired copy, one row shorter than the plane; the comparison is the deposit's own guard)
+    __device__ __forceinline__ void deposit_at(unsigned long long* hits, unsigned cell, float fx, float fy, float w, float mu) const
+    {
+        if (cell + pitch + 1u > last_cell) return;
+        deposit_footprint(hits, rej_cells, cell, cell + pitch, cell + 1u, cell + pitch + 1u, fx, fy, w, mu);
+    }
+
+    // byte offset of a footprint inside a copy of the layout PITCH4 -> its first cell
+    template <int PITCH4>
+    __device__ __forceinline__ unsigned cell_of_offset(unsigned off) const
+    {
+        if (PITCH4 != ECC_QUAD_LAYOUT) return off >> 3;
+        // row-quad copy (footprint_offset): group (r >> 2) of pitch * 64 bytes, 64 bytes per bin, 16 per row of the group
+        const unsigned line = off >> 6, group = line / pitch;
+        return ((group << 2) + ((off >> 4) & 3u)) * pitch + (line - group * pitch);
+    }
+
+    // the footprint of slab_tex2d_norm at (a, d): its cell, its fractions and its four clamped texels, as padded cells
+    __device__ __forceinline__ void deposit_plain(unsigned long long* hits, const EccPairParams& p, const PlainTap t, float w, float mu) const
+    {
+        const float x = t.a * (float)p.n_alpha, y = t.d * (float)p.n_t;
+        const float xb = x - 0.5f, yb = y - 0.5f;
+        const float fi = floorf(xb), fj = floorf(yb);
+        const float fx = xb - fi, fy = yb - fj;
+        const int i = (int)fmaxf(fminf(fi, 1e9f), -1e9f), j = (int)fmaxf(fminf(fj, 1e9f), -1e9f);
+        const unsigned r0 = (unsigned)(min(max(i, 0), p.n_alpha - 1) + 1), r1 = (unsigned)(min(max(i + 1, 0), p.n_alpha - 1) + 1);
+        const unsigned b0 = (unsigned)(min(max(j, 0), p.n_t - 1) + 1), b1 = (unsigned)(min(max(j + 1, 0), p.n_t - 1) + 1);
+        deposit_footprint(hits, rej_cells, r0 * pitch + b0, r1 * pitch + b0, r0 * pitch + b1, r1 * pitch + b1, fx, fy, w, mu);
+    }
+};
+
+}  // namespace
+#endif
+
+// ---- the launch sequence of a map call: for the host files, behind ecc_form_call.h ---------------------------------------------
+#if defined(ECC_FORM_CALL_H)
+namespace ecc_internal {
+// ecc_robust_map.hip: everything of a map call behind the checks of its evaluation.  f: the evaluation's form with the map kernels
+// behind its launch; nD: the intermediates a sample can lie in (the entries of the plane table); weighted: which kind of map the
+// metric holds afterwards.
+int robust_map_call(ecc_metric* m, const PairForm& f, bool weighted, const int32_t* idx4, int64_t count, int nD, const int32_t* views,
+                    int n_mapped, float* hits, float* rejected, float* pair_terms);
+}  // namespace ecc_internal
 #endif
 
 #endif

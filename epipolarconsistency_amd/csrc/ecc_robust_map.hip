@@ -7,7 +7,8 @@
 // The launch sequence is a column-form call's (ecc_column_call.h) with robust_form's columns and division (ecc_robust.hip): the
 // checks, column_call_begin -- the planes' room as its more_scratch, the plane table's upload and the planes' memset as its
 // upload_more --, the map form's pair launch between the timing events, column_call_finish with the finishing kernel and the
-// planes' copies as its queue_more, the one wait.
+// planes' copies as its queue_more, the one wait.  It is written once, over the form (robust_map_call): the map under line weights
+// (ecc_weighted_robust_map.hip) runs it with weighted_robust_form's columns.
 #include "ecc_form_call.h"
 #include "ecc_robust_map.h"
 
@@ -63,43 +64,51 @@ int map_slots(const int32_t* views, int n_mapped, int nD, std::vector<int32_t>* 
     return ECC_OK;
 }
 
-// Everything behind the checks of the robust calls.  nD: the intermediates a sample can lie in.
-int robust_map_call(ecc_metric* m, const int32_t* idx4, int64_t count, int nD, int loss, float delta, const int32_t* views, int n_mapped,
-                    float* hits, float* rejected, double* value, double* inlier_mass, float* pair_terms)
+}  // namespace
+
+// Everything of a map call behind the checks of its evaluation (ecc_robust_map.h); ecc_weighted_robust_map.hip calls it with the
+// weighted form.  The plane table is followed by the list of mapped intermediates, slot by slot, which the weighted map's weights
+// kernel reads.
+int ecc_internal::robust_map_call(ecc_metric* m, const PairForm& f, bool weighted, const int32_t* idx4, int64_t count, int nD,
+                                  const int32_t* views, int n_mapped, float* hits, float* rejected, float* pair_terms)
 {
     std::vector<int32_t> slot_of;
     int n_map = 0;
     int rc = map_slots(views, n_mapped, nD, &slot_of, &n_map);
     if (rc) return rc;
     if (2 * (int64_t)n_map > 65535) return fail(ECC_ERR_INVALID_ARGUMENT, "more than 32767 mapped views");
+    slot_of.resize((size_t)nD + (size_t)n_map);
+    for (int v = 0; v < nD; ++v)
+        if (slot_of[v] >= 0) slot_of[(size_t)nD + slot_of[v]] = v;
     const int64_t bins = (int64_t)m->n_alpha * m->n_t, cells = ecc_robust_map_plane_cells(m->n_alpha, m->n_t);
     m->map_valid = false;
+    m->map_weighted = weighted;
     m->map_n_mapped = n_map;
+    m->map_n_slots = nD;
     if (count == 0) {  // an empty list: nothing was sampled
         if (hits) std::fill(hits, hits + (size_t)n_map * bins, 0.0f);
         if (rejected) std::fill(rejected, rejected + (size_t)n_map * bins, 0.0f);
         return ECC_OK;
     }
     ecc_ctx* ctx = m->ctx;
-    const PairForm f = robust_map_form(loss, delta, value, inlier_mass);
     ColumnCall c;
     rc = column_call_begin(
         m, idx4, count, f.T, f.S, &c,
         [&]() -> int {
             int e = ensure_geometric(m->map_fixed_d, 2 * (int64_t)n_map * cells, ctx->stream);
             if (!e) e = ensure_geometric(m->map_planes_d, 2 * (int64_t)n_map * bins, ctx->stream);
-            if (!e) e = ensure_geometric(m->map_slot_d, (int64_t)nD, ctx->stream);
+            if (!e) e = ensure_geometric(m->map_slot_d, (int64_t)slot_of.size(), ctx->stream);
             return e;
         },
         [&]() -> int {
-            HIP_TRY(hipMemcpyAsync(m->map_slot_d.ptr, slot_of.data(), sizeof(int32_t) * (size_t)nD, hipMemcpyHostToDevice, ctx->stream));
+            HIP_TRY(hipMemcpyAsync(m->map_slot_d.ptr, slot_of.data(), sizeof(int32_t) * slot_of.size(), hipMemcpyHostToDevice, ctx->stream));
             HIP_TRY(hipMemsetAsync(m->map_fixed_d.ptr, 0, sizeof(unsigned long long) * 2 * (size_t)n_map * (size_t)cells, ctx->stream));
             return ECC_OK;
         });
     if (rc) return rc;
     HIP_TRY(f.launch(m, c.p, m->gram_values_d.ptr, c.col_stride));
-    double totals[2] = {0.0, 0.0};  // in the order an evaluation of `count` values is added in (ecc_sum_order.h)
-    rc = column_call_finish(m, c, f.S, totals, f.T, m->gram_values_d.ptr, pair_terms, [&]() -> int {
+    std::vector<double> totals((size_t)f.S);  // in the order an evaluation of `count` values is added in (ecc_sum_order.h)
+    rc = column_call_finish(m, c, f.S, totals.data(), f.T, m->gram_values_d.ptr, pair_terms, [&]() -> int {
         // the fixed-point block and the float block are both every HITS plane, then every REJ plane, as the caller's two arrays are
         HIP_TRY(ecc_launch_robust_map_finish(m->map_fixed_d.ptr, m->map_planes_d.ptr, 2 * n_map, m->n_alpha, m->n_t, m->pitch, ctx->stream));
         const size_t bytes = sizeof(float) * (size_t)n_map * (size_t)bins;
@@ -109,12 +118,10 @@ int robust_map_call(ecc_metric* m, const int32_t* idx4, int64_t count, int nD, i
         return ECC_OK;
     });
     if (rc) return rc;
-    f.finish(totals, count, 0);
+    f.finish(totals.data(), count, 0);
     m->map_valid = true;
     return ECC_OK;
 }
-
-}  // namespace
 
 ECC_EXPORT int ecc_metric_evaluate_robust_map(ecc_metric* m, int loss, float delta, const int32_t* views, int n_mapped, float* hits,
                                               float* rejected, double* value, double* inlier_mass, float* pair_terms)
@@ -124,7 +131,8 @@ ECC_EXPORT int ecc_metric_evaluate_robust_map(ecc_metric* m, int loss, float del
     if (rc) return rc;
     if ((int64_t)m->dtrs.size() < (int64_t)m->n_views) return fail(ECC_ERR_INVALID_ARGUMENT, "fewer Radon intermediates than projection matrices");
     const int64_t n = m->n_views;
-    return robust_map_call(m, nullptr, n * (n - 1) / 2, (int)n, loss, delta, views, n_mapped, hits, rejected, value, inlier_mass, pair_terms);
+    return robust_map_call(m, robust_map_form(loss, delta, value, inlier_mass), /*weighted=*/false, nullptr, n * (n - 1) / 2, (int)n, views,
+                           n_mapped, hits, rejected, pair_terms);
 }
 
 ECC_EXPORT int ecc_metric_evaluate_robust_map_pairs(ecc_metric* m, const int32_t* idx4, int n_pairs, int loss, float delta, const int32_t* views,
@@ -138,7 +146,8 @@ ECC_EXPORT int ecc_metric_evaluate_robust_map_pairs(ecc_metric* m, const int32_t
     if (rc) return rc;
     rc = check_index_list(idx4, n_pairs, m->n_views, (int)m->dtrs.size(), "index array contains invalid indices");
     if (rc) return rc;
-    return robust_map_call(m, idx4, n_pairs, (int)m->dtrs.size(), loss, delta, views, n_mapped, hits, rejected, value, inlier_mass, pair_terms);
+    return robust_map_call(m, robust_map_form(loss, delta, value, inlier_mass), /*weighted=*/false, idx4, n_pairs, (int)m->dtrs.size(), views,
+                           n_mapped, hits, rejected, pair_terms);
 }
 
 ECC_EXPORT int ecc_metric_robust_map_weights(ecc_metric* m, float min_hits, float gain, ecc_dtr** out)
@@ -149,6 +158,8 @@ ECC_EXPORT int ecc_metric_robust_map_weights(ecc_metric* m, float min_hits, floa
     if (!(gain >= 0.0f) || !std::isfinite(gain)) return fail(ECC_ERR_INVALID_ARGUMENT, "gain must be finite and not negative");
     if (!m->map_valid || m->map_n_mapped < 1 || !m->map_planes_d.ptr)
         return fail(ECC_ERR_INVALID_ARGUMENT, "no robust map held: call ecc_metric_evaluate_robust_map first (refresh_dtrs and set_params drop it)");
+    if (m->map_weighted)
+        return fail(ECC_ERR_INVALID_ARGUMENT, "the held map was made under line weights: its weights are ecc_metric_weighted_robust_map_weights'");
     ecc_ctx* ctx = m->ctx;
     const int rc = set_device(ctx);
     if (rc) return rc;
@@ -163,8 +174,8 @@ ECC_EXPORT int ecc_metric_robust_map_weights(ecc_metric* m, float min_hits, floa
     return make_weight_handles(ctx, owner, n_map, m->n_alpha, m->n_t, m->n_u, m->n_v, out);
 }
 
-// Debug: the fixed-point planes of the held map as the kernel left them -- every HITS plane, then every REJ plane, (n_alpha + 2) x pitch
-// cells each in the slab's padded geometry -- so that a test can add and compare the integer sums themselves.
+// Debug: the fixed-point planes of the held map, of either kind, as the kernel left them -- every HITS plane, then every REJ plane,
+// (n_alpha + 2) x pitch cells each in the slab's padded geometry -- so that a test can add and compare the integer sums themselves.
 ECC_EXPORT int ecc_debug_robust_map_fixed(ecc_metric* m, uint64_t* out, int64_t capacity)
 {
     if (!m || !out) return fail(ECC_ERR_INVALID_ARGUMENT, "null argument");

@@ -5,14 +5,15 @@
 // the loss alone spends its scale on lines whose badness was known in advance and cannot be called on a 2 n metric's weights at all.
 //
 // The launch sequence is form_call's (ecc_form_call.h); what is this form's own -- its columns, its pair launch, its three results
-// -- is weighted_robust_form below.
+// -- is weighted_robust_form below; the map under line weights (ecc_weighted_robust_map.hip) takes it and weighted_robust_check
+// from here.
 // Not here: the pose-delta and transform batches of this form (the kernel serves them as it stands); range, group and RCCL forms;
 // use_corr; Tukey's biweight; a variance form.
 #include "ecc_form_call.h"
 
 using namespace ecc_internal;
 
-namespace {
+namespace ecc_internal {
 
 // What both calls need of their arguments and of the metric (after the null check of m and the list's own checks), before the device
 // is touched: robust_check's conditions, then weighted_check's, each with its code.  Behind it the metric holds exactly 2 n_views
@@ -47,7 +48,7 @@ PairForm weighted_robust_form(int loss, float delta, double* value, double* cove
             }};
 }
 
-}  // namespace
+}  // namespace ecc_internal
 
 ECC_EXPORT int ecc_metric_evaluate_weighted_robust(ecc_metric* m, int loss, float delta, double* value, double* coverage,
                                                    double* inlier_mass, float* pair_terms)

@@ -19,7 +19,9 @@
 // into a line-weight slab.
 // Whether a view is mapped, and where its planes are, is wave-uniform (the record's two data indices are): a side that is not mapped
 // is skipped by a scalar branch.  The REJ deposits of a sample with w == 1.0f add zero and are skipped: most samples are inliers.
-// Not here (include/ecc_hip.h): pose-delta, transform, range, group and RCCL forms; the map under line weights; use_corr.
+// The deposits themselves (deposit, deposit_footprint, MapPlanes) are in ecc_robust_map.h, shared with the map under line weights,
+// weighted_robust_map_kernel.hip.
+// Not here (include/ecc_hip.h): pose-delta, transform, range, group and RCCL forms; use_corr.
 #include <hip/hip_runtime.h>
 #include <float.h>
 
@@ -33,41 +35,12 @@ namespace {
 // the four per-lane sums, as in robust_kernel.hip: the value, the weight mass, the raw squares, the sample count
 enum { VALUE, MASS, RAW, COUNT, ROBUST_SUMS };
 
-// a deposit in fixed point: exact for a float32 in [0, 2^32)
-__device__ __forceinline__ void deposit(unsigned long long* cell, float x)
-{
-    atomicAdd(cell, (unsigned long long)(x * 4294967296.0f));
-}
-
-// The footprint of one sample into the HITS plane `hits` and the REJ plane `rej_cells` cells behind it.  c00 = (i0, j0), c10 = (i1, j0),
-// c01 = (i0, j1), c11 = (i1, j1) as cell indices; fx runs over i (angle rows), fy over j (distance bins).
-__device__ __forceinline__ void deposit_footprint(unsigned long long* hits, long long rej_cells, unsigned c00, unsigned c10, unsigned c01,
-                                                  unsigned c11, float fx, float fy, float w)
-{
-    const float gx = 1.0f - fx, gy = 1.0f - fy;
-    const float b00 = gx * gy, b10 = fx * gy, b01 = gx * fy, b11 = fx * fy;
-    deposit(hits + c00, b00);
-    deposit(hits + c10, b10);
-    deposit(hits + c01, b01);
-    deposit(hits + c11, b11);
-    if (w != 1.0f) {
-        const float q = 1.0f - w;
-        unsigned long long* rej = hits + rej_cells;
-        deposit(rej + c00, b00 * q);
-        deposit(rej + c10, b10 * q);
-        deposit(rej + c01, b01 * q);
-        deposit(rej + c11, b11 * q);
-    }
-}
-
-struct RobustMapForm : PairFormDefaults {
+struct RobustMapForm : PairFormDefaults, MapPlanes {
     const EccRobustMapParams& g;
     double (&acc)[ROBUST_SUMS];
     RobustLoss L;                      // the launch-uniform loss, in scalar registers
     GlobalFloats d0, d1;               // the reference loop's slabs
     unsigned long long *hits0, *hits1;  // the HITS plane of the pair's two views, null: not mapped (wave-uniform)
-    long long rej_cells;               // cells from a HITS plane to its REJ plane
-    unsigned pitch, last_cell;         // cells per row; the last cell of a plane
 
     __device__ __forceinline__ RobustMapForm(const EccRobustMapParams& g, double (&acc)[ROBUST_SUMS]) : g(g), acc(acc) {}
 
@@ -96,24 +69,6 @@ struct RobustMapForm : PairFormDefaults {
         acc[COUNT] += 2.0;
     }
 
-    // a footprint whose first cell is `cell` of the padded plane: the gather's own four cells (never past the plane: a footprint the
-    // gather may read lies inside the paired copy, one row shorter than the plane; the comparison is the deposit's own guard)
-    __device__ __forceinline__ void deposit_at(unsigned long long* hits, unsigned cell, float fx, float fy, float w) const
-    {
-        if (cell + pitch + 1u > last_cell) return;
-        deposit_footprint(hits, rej_cells, cell, cell + pitch, cell + 1u, cell + pitch + 1u, fx, fy, w);
-    }
-
-    // byte offset of a footprint inside a copy of the layout PITCH4 -> its first cell
-    template <int PITCH4>
-    __device__ __forceinline__ unsigned cell_of_offset(unsigned off) const
-    {
-        if (PITCH4 != ECC_QUAD_LAYOUT) return off >> 3;
-        // row-quad copy (footprint_offset): group (r >> 2) of pitch * 64 bytes, 64 bytes per bin, 16 per row of the group
-        const unsigned line = off >> 6, group = line / pitch;
-        return ((group << 2) + ((off >> 4) & 3u)) * pitch + (line - group * pitch);
-    }
-
     __device__ __forceinline__ void poly_trip(const SlabView sv0, const SlabView sv1, const SampleTap t0p, const SampleTap t1p,
                                               const SampleTap t0m, const SampleTap t1m, float rel_sign, float w06_dkappa)
     {
@@ -123,12 +78,12 @@ struct RobustMapForm : PairFormDefaults {
         const float w_p = robust_weight(L, dp), w_m = robust_weight(L, dm);
         add(fmaf(w_p * dp, dp, (w_m * dm) * dm) * w06_dkappa, w_p, w_m, dp, dm);
         if (hits0) {
-            deposit_at(hits0, t0p.off >> 3, t0p.fx, t0p.fy, w_p);
-            deposit_at(hits0, t0m.off >> 3, t0m.fx, t0m.fy, w_m);
+            deposit_at(hits0, t0p.off >> 3, t0p.fx, t0p.fy, w_p, 1.0f);
+            deposit_at(hits0, t0m.off >> 3, t0m.fx, t0m.fy, w_m, 1.0f);
         }
         if (hits1) {
-            deposit_at(hits1, t1p.off >> 3, t1p.fx, t1p.fy, w_p);
-            deposit_at(hits1, t1m.off >> 3, t1m.fx, t1m.fy, w_m);
+            deposit_at(hits1, t1p.off >> 3, t1p.fx, t1p.fy, w_p, 1.0f);
+            deposit_at(hits1, t1m.off >> 3, t1m.fx, t1m.fy, w_m, 1.0f);
         }
     }
 
@@ -142,12 +97,12 @@ struct RobustMapForm : PairFormDefaults {
         const float w_p = robust_weight(L, dp), w_m = robust_weight(L, dm);
         add((((w_p * dp) * dp + (w_m * dm) * dm) * w06) * dkappa, w_p, w_m, dp, dm);  // ref: ...RadonIntermediate.cu:112,269,254
         if (hits0) {
-            deposit_at(hits0, cell_of_offset<PITCH4>(line_tap_offset(t0p, sv0)), t0p.fx, t0p.fy, w_p);
-            deposit_at(hits0, cell_of_offset<PITCH4>(line_tap_offset(t0m, sv0)), t0m.fx, t0m.fy, w_m);
+            deposit_at(hits0, cell_of_offset<PITCH4>(line_tap_offset(t0p, sv0)), t0p.fx, t0p.fy, w_p, 1.0f);
+            deposit_at(hits0, cell_of_offset<PITCH4>(line_tap_offset(t0m, sv0)), t0m.fx, t0m.fy, w_m, 1.0f);
         }
         if (hits1) {
-            deposit_at(hits1, cell_of_offset<PITCH4>(line_tap_offset(t1p, sv1)), t1p.fx, t1p.fy, w_p);
-            deposit_at(hits1, cell_of_offset<PITCH4>(line_tap_offset(t1m, sv1)), t1m.fx, t1m.fy, w_m);
+            deposit_at(hits1, cell_of_offset<PITCH4>(line_tap_offset(t1p, sv1)), t1p.fx, t1p.fy, w_p, 1.0f);
+            deposit_at(hits1, cell_of_offset<PITCH4>(line_tap_offset(t1m, sv1)), t1m.fx, t1m.fy, w_m, 1.0f);
         }
     }
 
@@ -156,19 +111,6 @@ struct RobustMapForm : PairFormDefaults {
         d0 = (GlobalFloats)p.slabs[iD0];
         d1 = (GlobalFloats)p.slabs[iD1];
         begin(p, iD0, iD1);
-    }
-
-    // the footprint of slab_tex2d_norm at (a, d): its cell, its fractions and its four clamped texels, as padded cells
-    __device__ __forceinline__ void deposit_plain(unsigned long long* hits, const EccPairParams& p, const PlainTap t, float w) const
-    {
-        const float x = t.a * (float)p.n_alpha, y = t.d * (float)p.n_t;
-        const float xb = x - 0.5f, yb = y - 0.5f;
-        const float fi = floorf(xb), fj = floorf(yb);
-        const float fx = xb - fi, fy = yb - fj;
-        const int i = (int)fmaxf(fminf(fi, 1e9f), -1e9f), j = (int)fmaxf(fminf(fj, 1e9f), -1e9f);
-        const unsigned r0 = (unsigned)(min(max(i, 0), p.n_alpha - 1) + 1), r1 = (unsigned)(min(max(i + 1, 0), p.n_alpha - 1) + 1);
-        const unsigned b0 = (unsigned)(min(max(j, 0), p.n_t - 1) + 1), b1 = (unsigned)(min(max(j + 1, 0), p.n_t - 1) + 1);
-        deposit_footprint(hits, rej_cells, r0 * pitch + b0, r1 * pitch + b0, r0 * pitch + b1, r1 * pitch + b1, fx, fy, w);
     }
 
     __device__ __forceinline__ void reference_trip(const EccPairParams& p, bool deriv, const PlainTap t0p, const PlainTap t1p,
@@ -181,12 +123,12 @@ struct RobustMapForm : PairFormDefaults {
         const float consistency = ((w_p * dp) * dp + (w_m * dm) * dm) * w06;  // ref: ...RadonIntermediate.cu:112,254
         add(consistency * dkappa, w_p, w_m, dp, dm);                          // ref: ...RadonIntermediate.cu:269
         if (hits0) {
-            deposit_plain(hits0, p, t0p, w_p);
-            deposit_plain(hits0, p, t0m, w_m);
+            deposit_plain(hits0, p, t0p, w_p, 1.0f);
+            deposit_plain(hits0, p, t0m, w_m, 1.0f);
         }
         if (hits1) {
-            deposit_plain(hits1, p, t1p, w_p);
-            deposit_plain(hits1, p, t1m, w_m);
+            deposit_plain(hits1, p, t1p, w_p, 1.0f);
+            deposit_plain(hits1, p, t1m, w_m, 1.0f);
         }
     }
 };

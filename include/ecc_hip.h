@@ -837,8 +837,9 @@ double ecc_host_robust_scale(const float* pair_terms, int64_t n_pairs, double k)
  * -- every operation an IEEE float64 one.  One elementwise launch, no wait.
  *   - Errors, ECC_ERR_INVALID_ARGUMENT: m == NULL, out == NULL, min_hits or gain negative or not finite; no map held (no map call yet,
  *     or the map was dropped by ecc_metric_refresh_dtrs / ecc_metric_set_params).
- * Not built: the map's batches of pose deltas and of transforms, its range, group and RCCL forms; the map under line weights (a 2 n
- * metric) and under use_corr; an IRLS loop inside the library. */
+ * The map under line weights (a 2 n metric): ecc_metric_evaluate_weighted_robust_map below.
+ * Not built: the map's batches of pose deltas and of transforms, its range, group and RCCL forms; the map under use_corr; an IRLS
+ * loop inside the library. */
 int ecc_metric_evaluate_robust_map(ecc_metric* m, int loss, float delta, const int32_t* views, int n_mapped, float* hits, float* rejected,
                                    double* value, double* inlier_mass, float* pair_terms);
 int ecc_metric_evaluate_robust_map_pairs(ecc_metric* m, const int32_t* idx4, int n_pairs, int loss, float delta, const int32_t* views,
@@ -968,6 +969,46 @@ int ecc_metric_evaluate_weighted_robust(ecc_metric* m, int loss, float delta, do
 int ecc_metric_evaluate_weighted_robust_pairs(ecc_metric* m, const int32_t* idx4, int n_pairs, int loss, float delta,
                                               double* value, double* coverage, double* inlier_mass, float* pair_terms);
 double ecc_host_weighted_robust_scale(const float* pair_terms, int64_t n_pairs, double k);
+
+/* Where the robust loss rejects UNDER LINE WEIGHTS (csrc/ecc_weighted_robust_map.hip, csrc/weighted_robust_map_kernel.hip, DESIGN.md
+ * 4.25): ecc_metric_evaluate_robust_map for a metric that already carries weights -- an earlier pass's, a collimator flag from
+ * ecc_radon_line_weights, both -- so that the loss and the line weights can be iterated.
+ *
+ * ecc_metric_evaluate_weighted_robust_map / _map_pairs take the metric (n_dtrs == 2 * n_views), loss, delta, value, coverage,
+ * inlier_mass and pair_terms of ecc_metric_evaluate_weighted_robust / _weighted_robust_pairs and return THEIR BITS in them, the
+ * n_pairs x 4 rows {c, u, k, r} included.  Beside that, per +-kappa sample of a pair with the weight product mu = W_i * W_j and the
+ * loss weight w of its raw residual, per view of the pair that is mapped and per cell of the sample's footprint in that view, with
+ * the float32 footprint products b of ecc_metric_evaluate_robust_map:
+ *     x = b * mu          HITS[cell] += x          REJ[cell] += x * (1 - w)          (all float32)
+ * mu is the product of BOTH views' weights in either view's planes.  The planes, their fixed point (quantum 2^-32, integer
+ * atomics: the same arguments give the same bits in any order), hits, rejected, views and n_mapped are those of
+ * ecc_metric_evaluate_robust_map, with `views` distinct DATA indices in [0, n_views) for both forms: weight and map follow the data
+ * index.  The metric holds the float planes in the same place, and remembers which kind of map it holds;
+ * ecc_debug_robust_map_fixed serves both kinds.
+ *   delta = +infinity REJ is exactly 0 everywhere; value and coverage have ecc_metric_evaluate_weighted's bits.
+ *   every weight 1.0f the fixed-point sums are those of ecc_metric_evaluate_robust_map on the n-metric over the same data.
+ *   weights          are expected in [0, 1] (what ecc_radon_line_weights, ecc_dtr_line_weights and the map's own weights produce).
+ *                    Outside that range value, coverage, inlier_mass and pair_terms are still ecc_metric_evaluate_weighted_robust's
+ *                    and nothing is written out of bounds; the PLANES ARE UNSPECIFIED.
+ *   - Errors before anything is launched or written, in this order: those of ecc_metric_evaluate_weighted_robust[_pairs] in their
+ *     order; then the views list's as for ecc_metric_evaluate_robust_map.  After them n_pairs == 0 is ECC_OK: planes of zeros, no map
+ *     held.
+ * Launches: ecc_metric_evaluate_robust_map's sequence with pairs_weighted_robust_map_kernel (8 gathers per kappa step) and the sums of
+ * c, u and k.  A diagnostic, once per outer iteration.
+ *
+ * ecc_metric_weighted_robust_map_weights: the next pass's weights from the held map, one intermediate per mapped view v in
+ * out[0 .. n_mapped), handles as ecc_metric_robust_map_weights returns them: per padded element W_v * factor, one float32 multiply,
+ * W_v read from the CURRENT contents of intermediate n_views + v and factor ecc_metric_robust_map_weights' rule on the held float
+ * planes.  One elementwise launch, no wait.  ecc_metric_robust_map_weights itself refuses a map made by these calls.
+ *   - Errors, ECC_ERR_INVALID_ARGUMENT: as ecc_metric_robust_map_weights; the held map is not one of these calls'.
+ * Not built: pose-delta and transform batches of either map; range, group and RCCL forms; use_corr; Tukey's biweight; an IRLS loop
+ * inside the library (the Python layer's refine_line_weights iterates the calls); a wave-level pre-sum of the deposits. */
+int ecc_metric_evaluate_weighted_robust_map(ecc_metric* m, int loss, float delta, const int32_t* views, int n_mapped,
+        float* hits, float* rejected, double* value, double* coverage, double* inlier_mass, float* pair_terms);
+int ecc_metric_evaluate_weighted_robust_map_pairs(ecc_metric* m, const int32_t* idx4, int n_pairs, int loss, float delta,
+        const int32_t* views, int n_mapped, float* hits, float* rejected,
+        double* value, double* coverage, double* inlier_mass, float* pair_terms);
+int ecc_metric_weighted_robust_map_weights(ecc_metric* m, float min_hits, float gain, ecc_dtr** out);
 
 /* Multi-GPU building block: evaluate only pairs ij in [first, first+count) of the get_ij order
  * (ref: EpipolarConsistencyCommon.hxx:52-79); returns the partial sum (float64) -- the caller
