@@ -115,6 +115,8 @@ SIGNATURES = {
     "ecc_host_weighted_robust_scale": (_d, [_vp, _i64, _d]),
     "ecc_metric_evaluate_robust_pose_deltas": (_i, [_vp, _i, _vp, _vp, _vp, _i, C.c_float, _vp, _vp]),
     "ecc_metric_evaluate_robust_transforms": (_i, [_vp, _i, _i, _vp, _i, C.c_float, _vp, _vp, _vp]),
+    "ecc_metric_evaluate_weighted_robust_pose_deltas": (_i, [_vp, _i, _vp, _vp, _vp, _i, C.c_float, _vp, _vp, _vp]),
+    "ecc_metric_evaluate_weighted_robust_transforms": (_i, [_vp, _i, _i, _vp, _i, C.c_float, _vp, _vp, _vp, _vp]),
     "ecc_metric_last_batched_transforms": (_i, [_vp, C.POINTER(_i64)]),
     "ecc_host_compose_transform": (None, [_vp, _vp, _vp]),
     "ecc_metric_evaluate_range": (_i, [_vp, _i64, _i64, _vp, _pd]),

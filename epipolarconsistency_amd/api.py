@@ -725,6 +725,19 @@ class MetricRadonIntermediate:
         return _pose_lists_call(_lib.lib().ecc_metric_evaluate_robust_pose_deltas, self._h, moved_offsets, moved_views, moved_Ps,
                                 (int(loss), float(delta)), 2)
 
+    def evaluate_weighted_robust_pose_deltas(self, moved_views, moved_Ps, loss, delta):
+        """ecc_metric_evaluate_weighted_robust_pose_deltas: evaluate_pose_deltas under line weights and the robust loss together
+        (evaluate_weighted_robust: the metric holds the data of every view, then its line weights; loss, delta as there).  The same
+        lists; returns (values, coverages, inlier_masses), every entry bit-identical to setProjectionMatrices +
+        evaluate_weighted_robust(loss, delta) of that pose; the current matrices stay."""
+        return self.evaluate_weighted_robust_pose_deltas_packed(*_pack_pose_lists(moved_views, moved_Ps), loss, delta)
+
+    def evaluate_weighted_robust_pose_deltas_packed(self, moved_offsets, moved_views, moved_Ps, loss, delta):
+        """The C signature itself, with the arguments of evaluate_pose_deltas_packed, then loss and delta; returns (values,
+        coverages, inlier_masses)."""
+        return _pose_lists_call(_lib.lib().ecc_metric_evaluate_weighted_robust_pose_deltas, self._h, moved_offsets, moved_views, moved_Ps,
+                                (int(loss), float(delta)), 3)
+
     def evaluate_weighted_pairs(self, idx4, want_pairs=False):
         """ecc_metric_evaluate_weighted_pairs: evaluate_weighted over an index list of (P0, P1, D0, D1) tuples -- matrices P*, data
         intermediates D* in [0, n_views); the weights of a sample come from intermediate n_views + D*.  Returns (value, coverage) =
@@ -1106,9 +1119,29 @@ class MetricRadonIntermediate:
                                                                _ptr(pairs)))
         return _with_pairs((values, masses), pairs, want_pairs)
 
+    def evaluate_weighted_robust_transforms(self, n_source, Ts, loss, delta, want_pairs=False):
+        """ecc_metric_evaluate_weighted_robust_transforms: evaluate_transforms under line weights and the robust loss together
+        (evaluate_weighted_robust: 2 * n_views intermediates; loss, delta as there).  n_source and Ts as for evaluate_transforms.
+        Returns (values, coverages, inlier_masses) = per transform (sum c / sum u, sum u / (n_source n_target), sum k / sum u) over the
+        cross pairs -- with want_pairs also pairs (K, n_target, n_source, 4) float32 rows {c, u, k, r}: every number bit-identical to
+        setProjectionMatrices(composed) + evaluate_weighted_robust_pairs(the cross list, loss, delta) per transform; the current
+        matrices stay."""
+        flat = _transforms_colmajor(Ts)
+        n_source = int(n_source)
+        K, n = len(flat), self.getNumberOfProjetions()
+        values, coverages, masses = np.zeros(K, np.float64), np.zeros(K, np.float64), np.zeros(K, np.float64)
+        pairs = np.zeros((K, max(n - n_source, 0), max(n_source, 0), 4), np.float32) if want_pairs else None
+        check(_lib.lib().ecc_metric_evaluate_weighted_robust_transforms(self._h, n_source, K, C.c_void_p(flat.ctypes.data if K else 0),
+                                                                        int(loss), float(delta),
+                                                                        C.c_void_p(values.ctypes.data if K else 0),
+                                                                        C.c_void_p(coverages.ctypes.data if K else 0),
+                                                                        C.c_void_p(masses.ctypes.data if K else 0),
+                                                                        _ptr(pairs)))
+        return _with_pairs((values, coverages, masses), pairs, want_pairs)
+
     def last_batched_transforms(self):
-        """Transforms of the last evaluate_transforms / evaluate_weighted_transforms / evaluate_robust_transforms call that went
-        through the batch (0: the sequential way)."""
+        """Transforms of the last evaluate_transforms / evaluate_weighted_transforms / evaluate_robust_transforms /
+        evaluate_weighted_robust_transforms call that went through the batch (0: the sequential way)."""
         v = C.c_int64(0)
         check(_lib.lib().ecc_metric_last_batched_transforms(self._h, C.byref(v)))
         return v.value

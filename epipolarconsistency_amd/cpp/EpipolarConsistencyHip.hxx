@@ -1195,6 +1195,49 @@ public:
                                                             inlier_masses ? inlier_masses->data() : 0x0, pair_terms));
     }
 
+    /// Not in the reference: ecc_metric_evaluate_weighted_robust_pose_deltas -- evaluatePoseDeltas under line weights AND the robust loss
+    /// of evaluateWeightedRobust (the metric holds 2 n_views intermediates; loss, delta as there).  values[k], coverages[k] and
+    /// inlier_masses[k] (the latter two nullable) are bit-identical to replacing the views moved_views[k] by moved_Ps[k],
+    /// setProjectionMatrices and evaluateWeightedRobust(loss, delta); the current matrices stay.  Single device only.
+    void evaluateWeightedRobustPoseDeltas(const std::vector<std::vector<int> >& moved_views,
+                                          const std::vector<std::vector<Geometry::ProjectionMatrix> >& moved_Ps, int loss, float delta,
+                                          std::vector<double>& values, std::vector<double>* coverages = 0x0,
+                                          std::vector<double>* inlier_masses = 0x0)
+    {
+        if (m_gh) throw std::runtime_error("evaluateWeightedRobustPoseDeltas: not available on a device group");
+        if (moved_views.size() != moved_Ps.size()) throw std::runtime_error("evaluateWeightedRobustPoseDeltas: one matrix list per pose");
+        values.assign(moved_views.size(), 0.0);
+        if (coverages) coverages->assign(moved_views.size(), 0.0);
+        if (inlier_masses) inlier_masses->assign(moved_views.size(), 0.0);
+        if (moved_views.empty()) return;
+        const PackedPoseLists l("evaluateWeightedRobustPoseDeltas", moved_views, moved_Ps);
+        detail::check(ecc_metric_evaluate_weighted_robust_pose_deltas(m_h, (int)moved_views.size(), l.off.data(), l.views_or_null(), l.Ps_or_null(),
+                                                                      loss, delta, values.data(), coverages ? coverages->data() : 0x0,
+                                                                      inlier_masses ? inlier_masses->data() : 0x0));
+    }
+
+    /// Not in the reference: ecc_metric_evaluate_weighted_robust_transforms -- evaluateTransforms under line weights AND the robust
+    /// loss (n_source and Ts as for evaluateTransforms).  Per transform values[k] = sum c / sum u over the cross pairs under Ts[k],
+    /// coverages (nullable): sum u / (n_source n_target), inlier_masses (nullable): sum k / sum u; pair_terms (nullable): Ts.size() x
+    /// n_target x n_source x 4 floats, per transform its rows {c, u, k, r} with the source index fast.  Every number is bit-identical to
+    /// Ps[i] * Ts[k] by ecc_host_compose_transform, setProjectionMatrices and evaluateWeightedRobustPairs of the cross list per
+    /// transform; the current matrices stay (ecc_hip.h).  Single device only.
+    void evaluateWeightedRobustTransforms(int n_source, const std::vector<Geometry::RP3Homography>& Ts, int loss, float delta,
+                                          std::vector<double>& values, std::vector<double>* coverages = 0x0,
+                                          std::vector<double>* inlier_masses = 0x0, float* pair_terms = 0x0)
+    {
+        if (m_gh) throw std::runtime_error("evaluateWeightedRobustTransforms: not available on a device group");
+        values.assign(Ts.size(), 0.0);
+        if (coverages) coverages->assign(Ts.size(), 0.0);
+        if (inlier_masses) inlier_masses->assign(Ts.size(), 0.0);
+        std::vector<double> flat(16 * Ts.size());
+        for (size_t k = 0; k < Ts.size(); ++k)
+            for (int q = 0; q < 16; ++q) flat[16 * k + q] = Ts[k].data()[q];
+        detail::check(ecc_metric_evaluate_weighted_robust_transforms(m_h, n_source, (int)Ts.size(), flat.data(), loss, delta, values.data(),
+                                                                     coverages ? coverages->data() : 0x0,
+                                                                     inlier_masses ? inlier_masses->data() : 0x0, pair_terms));
+    }
+
     /// Not in the reference: ecc_metric_evaluate_view_hessian -- the quadratic form of the per-view channel coefficients as a matrix:
     /// metric(a) = a^T H a, gradient 2 H a, with the index c * n_views + i of evaluateViewCoefficients' coeffs.  Intermediates as for
     /// evaluateGram.  H: (n_views n_channels)^2, symmetric bit for bit; pair_blocks (nullable): n_pairs x (K (K + 1) + K^2) doubles,

@@ -68,6 +68,13 @@ extern "C" hipError_t ecc_launch_sum_weighted_poses(const float* base_cols, long
                                                     double* partial_d, double* out_host_dev, hipStream_t stream);
 extern "C" hipError_t ecc_launch_sum_weighted_transforms(const float* val_cols, long long col_stride, long long count, int K, int slices,
                                                          double* partial_d, double* out_host_dev, hipStream_t stream);
+// the same sums over the S leading columns in one walk, results at word S k + col (form_sums_kernel.hip; S == 3, anything else is
+// hipErrorInvalidValue)
+extern "C" hipError_t ecc_launch_sum_form_poses(const float* base_cols, long long base_stride, long long count, int n, int Q,
+                                                const int32_t* lists_d, int K, const float* val_cols, long long vals_stride, int S, int slices,
+                                                double* partial_d, double* out_host_dev, hipStream_t stream);
+extern "C" hipError_t ecc_launch_sum_form_transforms(const float* val_cols, long long col_stride, long long count, int K, int S, int slices,
+                                                     double* partial_d, double* out_host_dev, hipStream_t stream);
 extern "C" hipError_t ecc_launch_dilate_max(const float* src, float* dst, int64_t stride, int n_img, int n_u, int n_v, int radius,
                                             hipStream_t stream);
 extern "C" hipError_t ecc_launch_clip_min(const float* lengths, int64_t lengths_stride, float* dst, int64_t dst_stride, int n_img,

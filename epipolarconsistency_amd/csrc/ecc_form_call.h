@@ -27,8 +27,10 @@
 //                    sum_weighted_transforms_kernel over columns 0 and 1 -> 2 K result words; the pair terms: one copy of the T
 //                    columns and the transposition to transform-major rows; with batching off or a list longer than a batch the
 //                    transforms one at a time through the form's list call
-// The two segmented sums read columns 0 and 1 of a column-form buffer and know nothing of what the columns mean, so a batch has two
-// sums per pose or transform whatever the form's T.
+// The segmented sums read the S leading columns of a column-form buffer and know nothing of what the columns mean: S == 2 goes
+// through sum_weighted_poses_kernel / sum_weighted_transforms_kernel as above, whatever the form's T; S == 3 (the weighted-robust
+// form) through sum_form_poses_kernel / sum_form_transforms_kernel (form_sums_kernel.hip), which take all S columns in one walk ->
+// S K result words, word S k + col.
 #ifndef ECC_FORM_CALL_H
 #define ECC_FORM_CALL_H
 
@@ -55,7 +57,8 @@ PairForm robust_form(int loss, float delta, double* values, double* inlier_masse
 // inlier_masses[k] (nullable) = sum k / sum u
 PairForm weighted_robust_form(int loss, float delta, double* values, double* coverages, double* inlier_masses);
 
-// poses per batch: the sum's grid is slices x poses x 2 columns, half a million workgroups at most
+// poses per batch: the two-column sum's grid is slices x poses x 2 columns, half a million workgroups at most (the S-column sum has
+// no z dimension and takes the same limit)
 constexpr size_t FORM_BATCH_MAX_POSES = (1 << 19) / (2 * ecc_sum::SLICES);
 static_assert(FORM_BATCH_MAX_POSES < 65536, "poses are the y dimension of sum_weighted_poses_kernel's grid");
 // transforms per batch: they are the y dimension of the sum's grid
@@ -112,7 +115,7 @@ inline int form_call_all_pairs(ecc_metric* m, const PairForm& f, float* pair_ter
 }
 
 // One batch: poses with off[0] = 0 ... off[K] = Q columns over the base matrices `base`, whose columns are in m->gram_values_d
-// (base_c).  sums[2 k], sums[2 k + 1]: the sums of columns 0 and 1 of pose k over all pairs.
+// (base_c).  sums[S k + col], S = f.S: the sum of column col of pose k over all pairs.
 inline int form_pose_batch(ecc_metric* m, const PairForm& f, const double* base, const ColumnCall& base_c, int K, const int32_t* off,
                            const int32_t* views, const double* moved_Ps, double* sums)
 {
@@ -123,11 +126,12 @@ inline int form_pose_batch(ecc_metric* m, const PairForm& f, const double* base,
     const int64_t vals_stride = (std::max<int64_t>(entries, 1) + 3) & ~(int64_t)3;
     volatile uint64_t* out = nullptr;
     double* out_dev = nullptr;
-    int rc = stage_pose_grid(m, base, K, off, views, moved_Ps, 2 * K, &out, &out_dev);
+    const int words = f.S * K;
+    int rc = stage_pose_grid(m, base, K, off, views, moved_Ps, words, &out, &out_dev);
     if (!rc) rc = m->pose_values_d.ensure(f.T * vals_stride, ctx->stream);
-    if (!rc) rc = m->pose_partial_d.ensure((int64_t)2 * K * ecc_sum::SLICES, ctx->stream);
+    if (!rc) rc = m->pose_partial_d.ensure((int64_t)words * ecc_sum::SLICES, ctx->stream);
     if (rc) return rc;
-    HIP_TRY(launch_pose_list(m, K, Q, 2 * K));
+    HIP_TRY(launch_pose_list(m, K, Q, words));
     if (entries > 0) {
         EccPairParams p = base_c.p;  // the sampling mode of an all-pairs evaluation; n_views stays n
         p.PinvTs = m->pose_PinvTs_d.ptr;
@@ -139,11 +143,15 @@ inline int form_pose_batch(ecc_metric* m, const PairForm& f, const double* base,
         HIP_TRY(ecc_launch_k01(&p, ctx->stream));
         HIP_TRY(f.launch(m, p, m->pose_values_d.ptr, vals_stride));
     }
-    arm_pose_results(out, 2 * K);
+    arm_pose_results(out, words);
     const int slices = ecc_sum::slices(n_pairs, m->sum_scratch_d.ptr != nullptr);  // the all-pairs call's choice
-    HIP_TRY(ecc_launch_sum_weighted_poses(m->gram_values_d.ptr, base_c.col_stride, n_pairs, (int)n, Q, m->pose_lists_d.ptr, K,
-                                          m->pose_values_d.ptr, vals_stride, slices, m->pose_partial_d.ptr, out_dev, ctx->stream));
-    return wait_pose_results(ctx, out, 2 * K, sums);
+    if (f.S == 2)
+        HIP_TRY(ecc_launch_sum_weighted_poses(m->gram_values_d.ptr, base_c.col_stride, n_pairs, (int)n, Q, m->pose_lists_d.ptr, K,
+                                              m->pose_values_d.ptr, vals_stride, slices, m->pose_partial_d.ptr, out_dev, ctx->stream));
+    else  // all f.S columns in one walk of the pose's entries
+        HIP_TRY(ecc_launch_sum_form_poses(m->gram_values_d.ptr, base_c.col_stride, n_pairs, (int)n, Q, m->pose_lists_d.ptr, K,
+                                          m->pose_values_d.ptr, vals_stride, f.S, slices, m->pose_partial_d.ptr, out_dev, ctx->stream));
+    return wait_pose_results(ctx, out, words, sums);
 }
 
 // The batched poses of a call; what the batch does not take goes into not_batched.
@@ -166,10 +174,10 @@ inline int form_pose_deltas_batched(ecc_metric* m, const PairForm& f, int n_pose
         n_poses, off, views, moved_Ps, max_cols, FORM_BATCH_MAX_POSES,
         [&](int c, const int32_t* vk, const double* Pk) { return pose_keeps_radius(m, base_radius, c, vk, Pk); },
         [&](const ecc_pose_batches::Batch& b) -> int {
-            sums.resize(2 * b.pose.size());
+            sums.resize(f.S * b.pose.size());
             const int e = form_pose_batch(m, f, base.data(), base_c, (int)b.pose.size(), b.off.data(), b.views.data(), b.Ps.data(), sums.data());
             if (e) return e;
-            for (size_t q = 0; q < b.pose.size(); ++q) f.finish(&sums[2 * q], n_pairs, b.pose[q]);
+            for (size_t q = 0; q < b.pose.size(); ++q) f.finish(&sums[f.S * q], n_pairs, b.pose[q]);
             m->last_batched_poses += (int64_t)b.pose.size();
             return ECC_OK;
         },
@@ -199,26 +207,26 @@ inline int form_pose_deltas(ecc_metric* m, const PairForm& f, int n_poses, const
     return pose_deltas_sequential(m, rest, off, views, moved_Ps, evaluate_pose);
 }
 
-// One batch: K transforms Ts (16 doubles each) of the base matrices (n x 12).  sums[2 k], sums[2 k + 1]: the sums of columns 0 and
-// 1 of transform k over its cross list; pair_terms (nullable, host): K x count rows of T.  batch_noun: wait_pose_results' word for
-// the batch.
+// One batch: K transforms Ts (16 doubles each) of the base matrices (n x 12).  sums[S k + col], S = f.S: the sum of column col of
+// transform k over its cross list; pair_terms (nullable, host): K x count rows of T.  batch_noun: wait_pose_results' word for the
+// batch.
 inline int form_transform_batch(ecc_metric* m, const PairForm& f, const double* base, int n_source, int K, const double* Ts,
                                 const char* batch_noun, double* sums, float* pair_terms)
 {
     ecc_ctx* ctx = m->ctx;
-    const int T = f.T;
+    const int T = f.T, words = f.S * K;
     const int64_t n = m->n_views, count = (int64_t)n_source * (n - n_source), entries = count * K;
     const int64_t vals_stride = (entries + 3) & ~(int64_t)3;
     volatile uint64_t* out = nullptr;
     double* out_dev = nullptr;
-    int rc = stage_transform_grid(m, base, n_source, K, Ts, 2 * K, &out, &out_dev);
+    int rc = stage_transform_grid(m, base, n_source, K, Ts, words, &out, &out_dev);
     if (!rc) rc = m->pose_values_d.ensure(T * vals_stride, ctx->stream);
-    if (!rc) rc = m->pose_partial_d.ensure((int64_t)2 * K * ecc_sum::SLICES, ctx->stream);
+    if (!rc) rc = m->pose_partial_d.ensure((int64_t)words * ecc_sum::SLICES, ctx->stream);
     if (rc) return rc;
     EccPairParams p;
     rc = fill_pair_params(m, &p, count, /*need_e1=*/false);  // the sampling mode of a list of `count` tuples
     if (rc) return rc;
-    HIP_TRY(launch_transform_list(m, n_source, K, (long long)((count + 3) & ~(int64_t)3), 2 * K));
+    HIP_TRY(launch_transform_list(m, n_source, K, (long long)((count + 3) & ~(int64_t)3), words));
     p.PinvTs = m->pose_PinvTs_d.ptr;
     p.Cs = m->pose_Cs_d.ptr;
     p.indices = m->pose_idx_d.ptr;
@@ -228,15 +236,18 @@ inline int form_transform_batch(ecc_metric* m, const PairForm& f, const double* 
     if (m->object_radius_mm > 0) HIP_TRY(ecc_launch_k01(&p, ctx->stream));
     else HIP_TRY(ecc_launch_k01_radii(&p, m->transform_radii_d.ptr, K, ctx->stream));  // every transform the radius of its composed view 0
     HIP_TRY(f.launch(m, p, m->pose_values_d.ptr, vals_stride));  // (p.n_views stays n: the weight copy of data copy D is n copies behind it)
-    arm_pose_results(out, 2 * K);
+    arm_pose_results(out, words);
     const int slices = ecc_sum::slices(count, m->sum_scratch_d.ptr != nullptr);  // the list call's choice
-    HIP_TRY(ecc_launch_sum_weighted_transforms(m->pose_values_d.ptr, vals_stride, count, K, slices, m->pose_partial_d.ptr, out_dev, ctx->stream));
+    if (f.S == 2)
+        HIP_TRY(ecc_launch_sum_weighted_transforms(m->pose_values_d.ptr, vals_stride, count, K, slices, m->pose_partial_d.ptr, out_dev, ctx->stream));
+    else  // all f.S columns from one set of strided addresses
+        HIP_TRY(ecc_launch_sum_form_transforms(m->pose_values_d.ptr, vals_stride, count, K, f.S, slices, m->pose_partial_d.ptr, out_dev, ctx->stream));
     std::vector<float> cols;
     if (pair_terms) {
         cols.resize(T * (size_t)vals_stride);
         HIP_TRY(hipMemcpyAsync(cols.data(), m->pose_values_d.ptr, sizeof(float) * cols.size(), hipMemcpyDeviceToHost, ctx->stream));
     }
-    rc = wait_pose_results(ctx, out, 2 * K, sums, batch_noun);
+    rc = wait_pose_results(ctx, out, words, sums, batch_noun);
     if (rc || !pair_terms) return rc;
     HIP_TRY(wait_stream_spin(ctx->stream));  // the copy behind the sums
     for (int k = 0; k < K; ++k)
@@ -264,10 +275,10 @@ inline int form_transforms(ecc_metric* m, const PairForm& f, int n_source, int n
                                      [&](int k, const int32_t* idx, int len) { return evaluate_list(k, idx, len, rows_of(k)); });
     std::vector<double> sums;
     return transforms_batched(m, count, n_transforms, FORM_TRANSFORM_BATCH_MAX, [&](int64_t k0, int K) -> int {
-        sums.resize(2 * (size_t)K);
+        sums.resize(f.S * (size_t)K);
         const int e = form_transform_batch(m, f, base.data(), n_source, K, Ts + 16 * (size_t)k0, batch_noun, sums.data(), rows_of(k0));
         if (e) return e;
-        for (int k = 0; k < K; ++k) f.finish(&sums[2 * k], count, k0 + k);
+        for (int k = 0; k < K; ++k) f.finish(&sums[f.S * k], count, k0 + k);
         return ECC_OK;
     });
 }

@@ -9,8 +9,8 @@
 // ecc_metric_evaluate_robust_transforms   form_transforms with it: values[k] = sum c / count, inlier_masses[k] = sum u / count
 // Every result has the bits of the sequential calls (tests/test_gpu_robust_poses.py, tests/test_gpu_robust_transforms.py); what a
 // batch does not take is evaluated that way inside the call.
-// Not here: base columns kept between calls; the full-matrices and strided pose forms; range, group and RCCL forms; these batches
-// for the loss combined with line weights (ecc_weighted_robust.hip has its all-pairs and list forms); the loss under use_corr.
+// Not here: base columns kept between calls; the full-matrices and strided pose forms; range, group and RCCL forms; the loss under
+// use_corr.  (These batches for the loss combined with line weights: ecc_weighted_robust_batches.hip.)
 #include "ecc_form_call.h"
 
 using namespace ecc_internal;

@@ -3,8 +3,8 @@
 //
 // Every promise of "the same bits as set_projections + evaluate_all" (pose batches, the one-launch evaluation, the pose-delta
 // mode) is a promise about this order, so it is stated here once and used by sum_pairs_kernel / sum_pairs_split_kernel
-// (sum_kernel.hip), sum_poses_kernel / finish_poses_kernel (ecc_poses.hip), sum_weighted_poses_kernel (weighted_poses_kernel.hip)
-// and the host (sum_on_host, ecc_evaluate.hip):
+// (sum_kernel.hip), sum_poses_kernel / finish_poses_kernel (ecc_poses.hip), sum_weighted_poses_kernel (weighted_poses_kernel.hip),
+// sum_form_poses_kernel / sum_form_transforms_kernel (form_sums_kernel.hip) and the host (sum_on_host, ecc_evaluate.hip):
 //   * the values are read as float4 k = 0 .. n4 - 1, n4 = count / 4, cut into `slices` contiguous slices of
 //     per = ceil(n4 / slices) float4 (slice_bounds); slices = 1 below SPLIT_MIN_COUNT values, else SLICES (slices);
 //   * a slice is added by THREADS threads: thread t adds the components x, y, z, w of its float4 k = lo + t, lo + t + THREADS,

@@ -7,8 +7,8 @@
 // The launch sequence is form_call's (ecc_form_call.h); what is this form's own -- its columns, its pair launch, its three results
 // -- is weighted_robust_form below; the map under line weights (ecc_weighted_robust_map.hip) takes it and weighted_robust_check
 // from here.
-// Not here: the pose-delta and transform batches of this form (the kernel serves them as it stands); range, group and RCCL forms;
-// use_corr; Tukey's biweight; a variance form.
+// The pose-delta and transform batches of this form are ecc_weighted_robust_batches.hip's.
+// Not here: range, group and RCCL forms; use_corr; Tukey's biweight; a variance form.
 #include "ecc_form_call.h"
 
 using namespace ecc_internal;

@@ -1010,6 +1010,48 @@ int ecc_metric_evaluate_weighted_robust_map_pairs(ecc_metric* m, const int32_t* 
         double* value, double* coverage, double* inlier_mass, float* pair_terms);
 int ecc_metric_weighted_robust_map_weights(ecc_metric* m, float min_hits, float gain, ecc_dtr** out);
 
+/* Line weights and the robust loss together, for optimisers (csrc/ecc_weighted_robust_batches.hip, csrc/form_sums_kernel.hip,
+ * DESIGN.md 4.26): a population of poses or of source-to-target transforms per call, as the plain, the weighted and the robust
+ * siblings take them.  This block supersedes the "Not built" sentences of the robust-batches block and of the weighted-robust block
+ * above where they name the pose-delta and transform batches of the combined form: they are built here.  The metric, the losses,
+ * delta, the four float32 columns {c, u, k, r} per pair and the three results are exactly those of
+ * ecc_metric_evaluate_weighted_robust: n_dtrs == 2 * n_views, value = sum c / sum u, coverage = sum u / count, inlier mass =
+ * sum k / sum u; sum u == 0 gives 0.0 for all three and ECC_OK.
+ *
+ * ecc_metric_evaluate_weighted_robust_pose_deltas: the lists of ecc_metric_evaluate_pose_deltas; n_poses < 1: ECC_OK.  values[k],
+ * coverages[k] and inlier_masses[k] (the latter two nullable) have THE BITS of ecc_metric_set_projections(pose k) +
+ * ecc_metric_evaluate_weighted_robust(loss, delta) (tests/test_gpu_weighted_robust_poses.py).  The steps are those of
+ * ecc_metric_evaluate_robust_pose_deltas with the weighted-robust pair launch, and in step 4 ONE segmented float64 sum per pose of the
+ * three columns c, u and k in one walk of the pose's grid entries (r is not summed).  The fallbacks (more than
+ * ECC_POSE_BATCH_MAX_MOVED moved views, view 0 moved under the automatic object radius, batching off), the cut at 2^20 grid entries
+ * and ecc_metric_last_batched_poses are the siblings'.
+ *
+ * ecc_metric_evaluate_weighted_robust_transforms: views, transforms, the cross list and the batching of
+ * ecc_metric_evaluate_transforms; count = n_source * n_target.  values[k] (required), coverages[k], inlier_masses[k] (nullable) and
+ *   pair_terms (host, nullable): n_transforms x n_target x n_source x 4 float32, per transform its count rows {c, u, k, r} in list
+ *   order
+ * have THE BITS of ecc_metric_set_projections(the composed matrices) + ecc_metric_evaluate_weighted_robust_pairs(that list, loss,
+ * delta) (tests/test_gpu_weighted_robust_transforms.py).  A transform whose list alone exceeds a batch, and every transform after
+ * ecc_metric_set_pose_batching(m, 0), is evaluated the sequential way inside the call (same bits);
+ * ecc_metric_last_batched_transforms counts the batched ones.  n_transforms == 0 (after the checks): ECC_OK, nothing written.
+ *
+ * Both: delta = +infinity (or FLT_MAX) gives values and coverages the bits of ecc_metric_evaluate_weighted_pose_deltas /
+ * ecc_metric_evaluate_weighted_transforms and every inlier mass 1.0; weights of 1.0f give values and inlier masses the bits of
+ * ecc_metric_evaluate_robust_pose_deltas / ecc_metric_evaluate_robust_transforms on the n_views metric and every coverage 1.0.  The
+ * calls leave the metric as they found it, as the siblings do.
+ * Errors are returned before anything is launched or written.  Pose form, in this order: m == NULL; moved_offsets or values NULL:
+ * ECC_ERR_INVALID_ARGUMENT; (n_poses < 1: ECC_OK); the list arrays NULL with moved_offsets[n_poses] > 0; the conditions of
+ * ecc_metric_evaluate_weighted_robust in its order (use_corr: ECC_ERR_UNSUPPORTED; n_dtrs != 2 * n_views); a bad list.  Transform
+ * form: m == NULL; n_transforms < 0; Ts or values NULL with n_transforms > 0; the conditions of ecc_metric_evaluate_weighted_robust;
+ * n_source outside [1, n_views).
+ * Not built: kept base columns; the full-matrices and strided pose forms; range, group and RCCL forms; use_corr; the batches of the
+ * maps (ecc_metric_evaluate_robust_map, ecc_metric_evaluate_weighted_robust_map). */
+int ecc_metric_evaluate_weighted_robust_pose_deltas(ecc_metric* m, int n_poses, const int32_t* moved_offsets, const int32_t* moved_views,
+                                                    const double* moved_Ps, int loss, float delta, double* values, double* coverages,
+                                                    double* inlier_masses);
+int ecc_metric_evaluate_weighted_robust_transforms(ecc_metric* m, int n_source, int n_transforms, const double* Ts, int loss, float delta,
+                                                   double* values, double* coverages, double* inlier_masses, float* pair_terms);
+
 /* Multi-GPU building block: evaluate only pairs ij in [first, first+count) of the get_ij order
  * (ref: EpipolarConsistencyCommon.hxx:52-79); returns the partial sum (float64) -- the caller
  * all-reduces {sum, count}.  pair_values (host, nullable) receives `count` floats. */
