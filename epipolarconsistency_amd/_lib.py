@@ -140,6 +140,10 @@ SIGNATURES = {
     "ecc_direct_lines_bound": (_i, [_vp, _pi]),
     "ecc_direct_evaluate_for_image_pair": (_i, [_vp, _i, _i, _i, _pi, _vp, _vp, _vp, _vp, _pd]),
     "ecc_direct_evaluate_for_image_pair_kappas": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _pd]),
+    "ecc_direct_evaluate_pairs": (_i, [_vp, _vp, _i64, _vp, _i, _vp, _vp]),
+    "ecc_direct_evaluate_pose_deltas": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ecc_direct_pose_pairs_bound": (_i, [_vp, _i, _vp, C.POINTER(_i64)]),
+    "ecc_debug_set_direct_batch": (_i, [_vp, _i64]),
     "ecc_preprocess_defaults": (None, [_vp]),
     "ecc_preprocess": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp]),
     "ecc_host_intrinsics": (None, [_vp, _pf, _pf, _pf]),

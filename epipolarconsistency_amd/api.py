@@ -1523,6 +1523,50 @@ class MetricDirect:
         n = n.value
         return m.value, dict(redundant_samples0=s0[:n], redundant_samples1=s1[:n], kappas=kap[:n], lines=lines[:n])
 
+    def evaluate_pairs(self, idx4, segments=None, want_pairs=False):
+        """ecc_direct_evaluate_pairs: the reference's index list of (P0, P1, I0, I1) tuples -- P* rows of the matrix table given to
+        setProjectionMatrices (it may hold more matrices than there are images: candidates), I* images.  Every entry has the bits of
+        evaluateForImagePair's metric.  segments: S + 1 non-decreasing offsets into the list (first 0, last its length) -> the S
+        float64 sums; None -> the sum of the whole list as a float.  With want_pairs: (sums, pair values in list order)."""
+        idx = _idx4_list(idx4)
+        off = None if segments is None else np.ascontiguousarray(segments, np.int64).reshape(-1)
+        if off is not None and len(off) < 1:
+            raise ValueError("segments must hold at least one offset")
+        sums = np.zeros(1 if off is None else len(off) - 1, np.float64)
+        pairs = np.zeros(len(idx), np.float64) if want_pairs else None
+        # (an empty output still has an address here: the C call refuses only two null outputs)
+        check(_lib.lib().ecc_direct_evaluate_pairs(self._h, _ptr(idx), len(idx), None if off is None else C.c_void_p(off.ctypes.data),
+                                                   len(sums), None if pairs is None else C.c_void_p(pairs.ctypes.data),
+                                                   C.c_void_p(sums.ctypes.data)))
+        total = float(sums[0]) if off is None else sums
+        return (total, pairs) if want_pairs else total
+
+    def evaluate_pose_deltas(self, moved_views, moved_Ps, want_pairs=False):
+        """ecc_direct_evaluate_pose_deltas: pose k = the set matrices with the views moved_views[k] replaced by moved_Ps[k] (as
+        MetricRadonIntermediate.evaluate_pose_deltas takes them).  Returns the K sums over the pairs that contain a moved view --
+        the pairs without one are a constant of the batch that the caller owns (evaluate_pairs over them, once).  With want_pairs:
+        (sums, terms, their (i, j, i, j) tuples), pose after pose in direct_pose_pairs order.  The set matrices stay."""
+        return self.evaluate_pose_deltas_packed(*_pack_pose_lists(moved_views, moved_Ps), want_pairs=want_pairs)
+
+    def evaluate_pose_deltas_packed(self, moved_offsets, moved_views, moved_Ps, want_pairs=False):
+        """The C signature itself: moved_offsets (K + 1 int32, [0] = 0), moved_views (Q int32), moved_Ps ((Q, 12) float64)."""
+        off, views, flat = _check_pose_lists(moved_offsets, moved_views, moved_Ps)
+        K = len(off) - 1
+        sums = np.zeros(K, np.float64)
+        pairs = tuples = None
+        if want_pairs:
+            n = C.c_int64()
+            check(_lib.lib().ecc_direct_pose_pairs_bound(self._h, K, C.c_void_p(off.ctypes.data), C.byref(n)))
+            pairs, tuples = np.zeros(n.value, np.float64), np.zeros((n.value, 4), np.int32)
+        check(_lib.lib().ecc_direct_evaluate_pose_deltas(self._h, K, C.c_void_p(off.ctypes.data), _ptr(views), _ptr(flat),
+                                                         _ptr(sums), _ptr(pairs), _ptr(tuples)))
+        return (sums, pairs, tuples) if want_pairs else sums
+
+    def debug_set_batch(self, max_pairs=0):
+        """ecc_debug_set_direct_batch: at most max_pairs list entries per internal batch (0: the library's bound).  Same bits."""
+        check(_lib.lib().ecc_debug_set_direct_batch(self._h, int(max_pairs)))
+        return self
+
     def close(self):
         if self._h and self.ctx._h:
             _lib.lib().ecc_direct_destroy(self._h)
@@ -1533,6 +1577,16 @@ class MetricDirect:
             self.close()
         except Exception:
             pass
+
+
+def direct_pose_pairs(n_images, moved_views):
+    """The tuples MetricDirect.evaluate_pose_deltas evaluates for ONE pose that moves `moved_views`, in its order: (i, j, i, j) for
+    every pair i < j < n_images with at least one moved view, each once, ascending in (i, j).  (n_pairs, 4) int32.  Pure Python."""
+    moved = {int(v) for v in np.atleast_1d(moved_views)} if np.size(moved_views) else set()
+    if any(v < 0 or v >= n_images for v in moved):
+        raise ValueError("moved view out of range")
+    rows = [(i, j, i, j) for i in range(n_images) for j in range(i + 1, n_images) if i in moved or j in moved]
+    return np.asarray(rows, np.int32).reshape(-1, 4)
 
 
 def slab_floats(n_alpha, n_t):

@@ -608,6 +608,28 @@ public:
                                         std::vector<float>* redundant_samples1 = 0x0, std::vector<float>* kappas = 0x0) = 0;
 };
 
+// The pose lists of the evaluate*PoseDeltas calls as the C calls take them: off[0] = 0 ... off[K] = Q, the Q moved views, their
+// Q x 12 matrices.  views_or_null() / Ps_or_null(): what the calls pass for them.
+struct PackedPoseLists {
+    std::vector<int32_t> off, views;
+    std::vector<double> flat;
+    PackedPoseLists(const char* who, const std::vector<std::vector<int> >& moved_views,
+                    const std::vector<std::vector<Geometry::ProjectionMatrix> >& moved_Ps)
+        : off(1, 0)
+    {
+        for (size_t k = 0; k < moved_views.size(); ++k) {
+            if (moved_views[k].size() != moved_Ps[k].size()) throw std::runtime_error(std::string(who) + ": one matrix per moved view");
+            for (size_t q = 0; q < moved_views[k].size(); ++q) {
+                views.push_back(moved_views[k][q]);
+                flat.insert(flat.end(), moved_Ps[k][q].data(), moved_Ps[k][q].data() + 12);
+            }
+            off.push_back((int32_t)views.size());
+        }
+    }
+    const int32_t* views_or_null() const { return views.empty() ? 0x0 : views.data(); }
+    const double* Ps_or_null() const { return flat.empty() ? 0x0 : flat.data(); }
+};
+
 /// ref: class MetricRadonIntermediate : public Metric
 class MetricRadonIntermediate : public Metric {
     std::vector<RadonIntermediate*> dtrs;
@@ -1272,28 +1294,6 @@ private:
         detail::check(ecc_metric_evaluate_view_hessian(m_h, n_channels, h, b));
     }
 
-    // The pose lists of the evaluate*PoseDeltas calls as the C calls take them: off[0] = 0 ... off[K] = Q, the Q moved views, their
-    // Q x 12 matrices.  views_or_null() / Ps_or_null(): what the calls pass for them.
-    struct PackedPoseLists {
-        std::vector<int32_t> off, views;
-        std::vector<double> flat;
-        PackedPoseLists(const char* who, const std::vector<std::vector<int> >& moved_views,
-                        const std::vector<std::vector<Geometry::ProjectionMatrix> >& moved_Ps)
-            : off(1, 0)
-        {
-            for (size_t k = 0; k < moved_views.size(); ++k) {
-                if (moved_views[k].size() != moved_Ps[k].size()) throw std::runtime_error(std::string(who) + ": one matrix per moved view");
-                for (size_t q = 0; q < moved_views[k].size(); ++q) {
-                    views.push_back(moved_views[k][q]);
-                    flat.insert(flat.end(), moved_Ps[k][q].data(), moved_Ps[k][q].data() + 12);
-                }
-                off.push_back((int32_t)views.size());
-            }
-        }
-        const int32_t* views_or_null() const { return views.empty() ? 0x0 : views.data(); }
-        const double* Ps_or_null() const { return flat.empty() ? 0x0 : flat.data(); }
-    };
-
 public:
     /// The metric borrows the dtrs: "DO NOT delete or change _dtrs during lifetime" (ref: .h:45).
     MetricRadonIntermediate& setRadonIntermediates(const std::vector<RadonIntermediate*>& _dtrs)
@@ -1464,6 +1464,54 @@ public:
         if (redundant_samples1) redundant_samples1->assign(s1.begin(), s1.begin() + n);
         if (kappas) kappas->assign(kp.begin(), kp.begin() + n);
         return metric;
+    }
+
+    /// ref: Metric::evaluate(const std::vector<Eigen::Vector4i>& indices, float* out) for this metric -- ecc_direct_evaluate_pairs:
+    /// (P0, P1, I0, I1) tuples, P* rows of the matrix table of setProjectionMatrices (it may hold more matrices than there are
+    /// images: candidates), I* images.  Returns the SUM over the list (evaluate() returns the sum as well) and writes the
+    /// per-entry values to out (n_pairs floats, nullable), in list order.  The float64 values: evaluate_indices' `values`.
+#ifdef ECC_ADAPTER_HAVE_EIGEN
+    double evaluate(const std::vector<Eigen::Vector4i>& _indices, float* _out = 0x0)
+    {
+        std::vector<int32_t> idx(4 * _indices.size());
+        for (size_t i = 0; i < _indices.size(); ++i)
+            for (int k = 0; k < 4; ++k) idx[4 * i + k] = _indices[i][k];
+        return evaluate_indices(idx.data(), (int)_indices.size(), _out);
+    }
+#endif
+    /// Same with a flat int32 array of 4-tuples (what the Eigen overload forwards to); values: the float64 entries, nullable.
+    double evaluate_indices(const int32_t* idx4, int n_pairs, float* _out = 0x0, std::vector<double>* values = 0x0)
+    {
+        double sum = 0;
+        std::vector<double> v(_out || values ? (size_t)n_pairs : 0);
+        detail::check(ecc_direct_evaluate_pairs(m_h, idx4, n_pairs, 0x0, 1, v.empty() ? 0x0 : v.data(), &sum));
+        for (size_t q = 0; _out && q < v.size(); ++q) _out[q] = (float)v[q];
+        if (values) values->swap(v);
+        return sum;
+    }
+
+    /// Not in the reference: ecc_direct_evaluate_pose_deltas -- pose k = the set matrices with the views moved_views[k] replaced by
+    /// moved_Ps[k]; returns per pose the sum over the pairs that contain a moved view (the other pairs are a constant of the batch
+    /// that the caller owns).  terms / tuples (nullable): those pairs' values and (i, j, i, j) tuples, pose after pose.  The set
+    /// matrices stay.
+    std::vector<double> evaluatePoseDeltas(const PackedPoseLists& l, std::vector<double>* terms = 0x0, std::vector<int32_t>* tuples = 0x0)
+    {
+        const int K = (int)l.off.size() - 1;
+        std::vector<double> sums((size_t)K);
+        int64_t n = 0;
+        if (terms || tuples) detail::check(ecc_direct_pose_pairs_bound(m_h, K, l.off.data(), &n));
+        if (terms) terms->assign((size_t)n, 0.0);
+        if (tuples) tuples->assign(4 * (size_t)n, 0);
+        detail::check(ecc_direct_evaluate_pose_deltas(m_h, K, l.off.data(), l.views_or_null(), l.Ps_or_null(), sums.empty() ? 0x0 : sums.data(),
+                                                      terms && n ? terms->data() : 0x0, tuples && n ? tuples->data() : 0x0));
+        return sums;
+    }
+    std::vector<double> evaluatePoseDeltas(const std::vector<std::vector<int> >& moved_views,
+                                           const std::vector<std::vector<Geometry::ProjectionMatrix> >& moved_Ps,
+                                           std::vector<double>* terms = 0x0, std::vector<int32_t>* tuples = 0x0)
+    {
+        if (moved_views.size() != moved_Ps.size()) throw std::runtime_error("evaluatePoseDeltas: one matrix list per pose");
+        return evaluatePoseDeltas(PackedPoseLists("evaluatePoseDeltas", moved_views, moved_Ps), terms, tuples);
     }
 
     /// ref: setFanBeamConsistency: use the rectified fan-beam weighting instead of the derivative.

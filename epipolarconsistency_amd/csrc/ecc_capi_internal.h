@@ -53,6 +53,9 @@ extern "C" hipError_t ecc_launch_direct_views(const double* Ps_d, int n, EccDire
                                               hipStream_t stream);
 extern "C" hipError_t ecc_launch_direct_transpose(const float* src, float* dst, int n, int W, int H, hipStream_t stream);
 extern "C" hipError_t ecc_launch_direct_batch(const EccDirectParams* p, double* total, hipStream_t stream);
+extern "C" hipError_t ecc_launch_direct_list_batch(const EccDirectListParams* q, hipStream_t stream);
+extern "C" hipError_t ecc_launch_direct_segment_sums(const double* vals, const int64_t* offsets, int n_segments, double* sums,
+                                                     hipStream_t stream);
 extern "C" hipError_t ecc_launch_pair_samples(const EccPairSamplesParams* p, hipStream_t stream);
 extern "C" hipError_t ecc_launch_sum_pairs(const float* vals, long long count, double* out, void* scratch, hipStream_t stream);
 extern "C" hipError_t ecc_launch_sum_pairs_to_host(const float* vals, long long count, double* out, float* values_host, hipStream_t stream);

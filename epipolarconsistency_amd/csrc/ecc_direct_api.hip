@@ -1,40 +1,12 @@
 // ecc_direct_api.hip -- MetricDirect / FBCC behind the C ABI (host code only; the kernels are direct_kernel.hip).
 // ref: EpipolarConsistencyDirect.{h,cpp,cu}, RectifiedFBCC.h.
-#include "ecc_capi_internal.h"
+#include "ecc_direct_internal.h"
 
 #define ECC_EXPORT extern "C" __attribute__((visibility("default")))
 
 using namespace ecc_internal;
 
-// ---- MetricDirect ---------------------------------------------------------------------------------
-struct ecc_direct {
-    ecc_ctx* ctx = nullptr;
-    int n_images = 0, n_u = 0, n_v = 0, n_views = 0;
-    const float* images_d = nullptr;
-    float* owned_images = nullptr;
-    float* imagesT_d = nullptr;  // transposed copies (see direct_lines_kernel); refreshed by ecc_direct_update_images
-    double object_radius_mm = 0, dkappa = 0;
-    int use_fbcc = 0;
-    std::vector<double> P_first;
-    double* Ps_d = nullptr;
-    EccDirectView* views_d = nullptr;
-    int view_capacity = 0;
-    // scratch, grown on demand
-    EccDirectPair* pairs_d = nullptr;
-    float* samples_d = nullptr;
-    double* pair_metric_d = nullptr;
-    int64_t batch_capacity = 0;
-    int n_max_capacity = 0;
-    double* total_d = nullptr;
-    float* cost_d = nullptr;
-    int cost_capacity = 0;
-    // per view: source position (4) and object radius, on the host; per pair: the plane-angle range (see direct_ranges)
-    std::vector<double> centers, radii, ranges;
-    double* ranges_d = nullptr;
-    int64_t ranges_capacity = 0;
-};
-
-namespace {
+namespace ecc_internal {
 
 int direct_n_max(const ecc_direct* d, int* n_max)
 {
@@ -72,6 +44,23 @@ int direct_scratch(ecc_direct* d, int64_t batch, int n_max)
     return ECC_OK;
 }
 
+double direct_range(const double* C0, const double* C1, double user_radius, double r0, double r1)
+{
+    const double Pi = 3.14159265358979323846264338327950288419716939937510582;
+    double B[6];
+    ecc_host::join_points(C0, C1, B);
+    double radius = user_radius;
+    if (radius <= 0) radius = r0 > r1 ? r0 : r1;
+    const double mom = std::sqrt(B[3] * B[3] + B[1] * B[1] + B[0] * B[0]);
+    const double dir = std::sqrt(B[2] * B[2] + B[4] * B[4] + B[5] * B[5]);
+    const double baseline_dist = mom / dir;
+    return baseline_dist <= radius ? 0.5 * Pi : std::fabs(std::asin(radius / baseline_dist));
+}
+
+}  // namespace ecc_internal
+
+namespace {
+
 // ref: estimateAngularRange (EpipolarConsistency.cpp:49-59) as computeForImagePair calls it (...Direct.cpp:84-96): the
 // upper end of the plane-angle range of `count` pairs (idx2, or get_ij order from `first`), in the arithmetic of
 // direct_pair_kernel but with the host's asin -- the library the reference and the oracle compute it with.  Left on
@@ -89,7 +78,6 @@ int direct_ranges(ecc_direct* d, int64_t first, int64_t count, const int* idx2)
     d->ranges.resize((size_t)count);
     const int n = d->n_images;
     const double user_radius = direct_radius(d);
-    const double Pi = 3.14159265358979323846264338327950288419716939937510582;
     int i = 0, j = 1;
     if (!idx2) ecc_get_ij(first, n, &i, &j);
     for (int64_t q = 0; q < count; ++q) {
@@ -97,14 +85,7 @@ int direct_ranges(ecc_direct* d, int64_t first, int64_t count, const int* idx2)
             i = idx2[2 * q];
             j = idx2[2 * q + 1];
         }
-        double B[6];
-        ecc_host::join_points(&d->centers[4 * (size_t)i], &d->centers[4 * (size_t)j], B);
-        double radius = user_radius;
-        if (radius <= 0) radius = d->radii[i] > d->radii[j] ? d->radii[i] : d->radii[j];
-        const double mom = std::sqrt(B[3] * B[3] + B[1] * B[1] + B[0] * B[0]);
-        const double dir = std::sqrt(B[2] * B[2] + B[4] * B[4] + B[5] * B[5]);
-        const double baseline_dist = mom / dir;
-        d->ranges[(size_t)q] = baseline_dist <= radius ? 0.5 * Pi : std::fabs(std::asin(radius / baseline_dist));
+        d->ranges[(size_t)q] = direct_range(&d->centers[4 * (size_t)i], &d->centers[4 * (size_t)j], user_radius, d->radii[i], d->radii[j]);
         if (!idx2 && ++j >= n) {
             ++i;
             j = i + 1;

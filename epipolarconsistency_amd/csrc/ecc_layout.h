@@ -364,6 +364,14 @@ struct EccDirectParams {
                                 // libm (ecc_direct_api.hip, direct_ranges), so that the grid is the reference's bit for bit
 };
 
+// Index lists (direct_list_kernel.hip): entry q of a batch is the tuple idx4[4 q ..] = (P0, P1, I0, I1).  Its record
+// b.pairs[q] is made from rows P0 and P1 of b.views (a table that may hold more matrices than there are images) and keeps
+// them as i and j; the pixels of its two sides are images I0 and I1, read from the tuple.  b.idx2 is unused.
+struct EccDirectListParams {
+    EccDirectParams b;
+    const int32_t* idx4;        // b.count tuples, device
+};
+
 // ---- evaluateForImagePair (E7, visualisation) -------------------------------------------------
 struct EccPairSamplesParams {
     const float* dtr0;       // slab of view i

@@ -1141,6 +1141,45 @@ int ecc_direct_evaluate_for_image_pair_kappas(ecc_direct* d, int i, int j, int n
                                               float* redundant_samples0, float* redundant_samples1, float* lines01,
                                               double* metric);
 
+/* Index lists and pose batches for optimisers that move ONE view (or a few) between evaluations of images that change --
+ * the setting MetricDirect is for (ref: Metric::evaluate(indices, out); Gui/SingleImageMotion.h builds the list
+ * (input_index, i, input_index, i) of every other view i).  Only the pairs that contain a moved view change, and these calls
+ * integrate only those.  DESIGN.md 4.27 says when this beats the Radon route (few poses x few reference views, or new pixels
+ * per evaluation) and when it does not.
+ *
+ * ecc_direct_evaluate_pairs: idx4 holds n_pairs tuples (P0, P1, I0, I1) -- P0, P1 rows of the matrix table of
+ * ecc_direct_set_projections (which may hold MORE matrices than there are images: that is how candidate matrices are passed),
+ * I0, I1 image indices.  Entries are evaluated as written, in order, nothing reordered or merged.  pair_values[q] (host,
+ * nullable) has THE BITS of the `metric` of ecc_direct_evaluate_for_image_pair on a metric whose matrices of views I0, I1 are
+ * rows P0, P1; object radius, plane step and the FBCC switch are the metric's, as ecc_direct_evaluate applies them.
+ * segment_offsets: n_segments + 1 non-decreasing offsets into the list, the first 0, the last n_pairs; segment_sums[s] (host,
+ * nullable) is the float64 sum of pair_values[segment_offsets[s] .. segment_offsets[s + 1]) in the fixed order ecc_direct_evaluate
+ * adds one batch in (1024 strided partials, a shuffle tree per wave, the 16 wave sums in order): the list of all pairs in get_ij
+ * order as one segment has the bits of ecc_direct_evaluate's sum while that runs as one batch.  A null segment_offsets is one
+ * segment holding the whole list.  Not both outputs null.  n_pairs == 0: ECC_OK, sums zeroed.
+ *
+ * ecc_direct_evaluate_pose_deltas: the packed lists of ecc_metric_evaluate_pose_deltas -- pose k = the SET matrices with the views
+ * moved_views[moved_offsets[k] .. moved_offsets[k + 1]) (any order, each once) replaced by the blocks moved_Ps[12 q ..] of the same
+ * entries q.  sums[k] = the sum (order as above) over the pairs i < j < n_images with at least one moved view, each once, in
+ * ascending (i, j) order.  The pairs WITHOUT a moved view are a constant of the batch (the one the comment in the reference's
+ * SingleImageMotion::evaluate speaks of): the caller owns it -- add ecc_direct_evaluate_pairs over those pairs, computed once,
+ * where absolute values are wanted; differences between poses of the same moved views do not need it.  Under the automatic
+ * object radius a pose that moves view 0 takes the radius of ITS view 0, as ecc_direct_set_projections + the single-pair call
+ * would.  The set matrices are unchanged by the call.  pair_values / pair_idx4 (host, nullable): the terms and their (i, j, i, j)
+ * tuples, pose after pose, ecc_direct_pose_pairs_bound entries (it is exact).  n_poses < 1: ECC_OK.
+ *
+ * Both refuse with ECC_ERR_INVALID_ARGUMENT and a text naming the entry: matrices not set, an index out of range, P0 == P1, a
+ * view named twice in a pose, offsets that decrease or end elsewhere than the list, more than 2^20 pairs in a call.  (A caller's
+ * kappa grid exists for the single-pair call only; these calls have no argument for one.)  They allocate nothing once their
+ * scratch has grown, and wait for the device once, at the end.  The list runs in batches of at most 256 MB of line integrals;
+ * ecc_debug_set_direct_batch lowers the batch to max_pairs entries (0: the library's bound) -- same bits, for tests. */
+int ecc_direct_evaluate_pairs(ecc_direct* d, const int32_t* idx4, int64_t n_pairs, const int64_t* segment_offsets,
+                              int n_segments, double* pair_values, double* segment_sums);
+int ecc_direct_evaluate_pose_deltas(ecc_direct* d, int n_poses, const int32_t* moved_offsets, const int32_t* moved_views,
+                                    const double* moved_Ps, double* sums, double* pair_values, int32_t* pair_idx4);
+int ecc_direct_pose_pairs_bound(const ecc_direct* d, int n_poses, const int32_t* moved_offsets, int64_t* n_pairs);
+int ecc_debug_set_direct_batch(ecc_direct* d, int64_t max_pairs);
+
 /* Debug: what the pair-geometry kernel fitted for pairs ij in [first, first+count): per pair
  * ECC_POLY_RECORD_FLOATS floats = { degree evaluated (4, 6, 8, 10; 0 = exact path; + 0.5 when the fit's bound says that no sample
  * of the pair can reach a clamp of the pair kernel, which then runs its clamp-free loop), x_scale, fold0, fold1 (1 = folded on the +kappa side),

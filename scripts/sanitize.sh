@@ -6,6 +6,7 @@
 #   3b. the pose batch's host-side comparison (csrc/ecc_pose_diff.h) under ThreadSanitizer: 1 and 8 threads, the same result
 #   3c. the change scan and pair lists of the evaluation paths (csrc/ecc_view_changes.h) under AddressSanitizer + UBSan
 #   3d. the host statement of the pair total's order (csrc/ecc_sum_order.h) under AddressSanitizer + UBSan
+#   3e. the list checks and pose-pair enumeration of MetricDirect's lists (csrc/ecc_direct_lists_host.h) under AddressSanitizer + UBSan
 #   4. host code of libecc_hip.so under UndefinedBehaviorSanitizer: the no-GPU ABI / host-function tests
 # usage: scripts/sanitize.sh [logfile]     (default profiles/r03_sanitize.log)
 set -u
@@ -43,6 +44,10 @@ g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefin
 echo; echo "== 3d. ecc_sum_order.h: -fsanitize=address,undefined (tests/c/sum_order.cpp)"
 g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer tests/c/sum_order.cpp \
   -o $TMP/sum_order && ASAN_OPTIONS=abort_on_error=1 $TMP/sum_order || fail=1
+
+echo; echo "== 3e. ecc_direct_lists_host.h: -fsanitize=address,undefined (tests/c/direct_lists_host.cpp)"
+g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -Iepipolarconsistency_amd/csrc \
+  tests/c/direct_lists_host.cpp -o $TMP/direct_lists_host && ASAN_OPTIONS=abort_on_error=1 $TMP/direct_lists_host || fail=1
 
 echo; echo "== 4. libecc_hip.so host code: -Xarch_host -fsanitize=undefined (ECC_HIP_LIB), no-GPU ABI and host-function tests"
 python - <<PY || fail=1
