@@ -751,6 +751,32 @@ class MetricRadonIntermediate:
                                                             _ptr(pairs)))
         return _with_pairs((value.value, coverage.value), pairs, want_pairs)
 
+    def evaluate_variance_pairs(self, idx4, floor, want_pairs=False):
+        """ecc_metric_evaluate_variance_pairs: evaluate_variance over an index list of (P0, P1, D0, D1) tuples -- matrices P*, data
+        intermediates D* in [0, n_views); the variance of a sample comes from intermediate n_views + D*.  Returns (value, mean_weight)
+        = (sum c / sum u, sum u / n_pairs) over the list -- with want_pairs (value, mean_weight, pairs), pairs (n_pairs, 2) float32
+        rows {c, u} in list order.  The sampling mode resolves from the list's length, as evaluate(indices) resolves it."""
+        idx = _idx4_list(idx4)
+        value, mean_weight = C.c_double(0.0), C.c_double(0.0)
+        pairs = np.zeros((len(idx), 2), np.float32) if want_pairs else None
+        check(_lib.lib().ecc_metric_evaluate_variance_pairs(self._h, _ptr(idx), len(idx), float(floor),
+                                                            C.byref(value), C.byref(mean_weight),
+                                                            _ptr(pairs)))
+        return _with_pairs((value.value, mean_weight.value), pairs, want_pairs)
+
+    def evaluate_variance_pose_deltas(self, moved_views, moved_Ps, floor):
+        """ecc_metric_evaluate_variance_pose_deltas: evaluate_pose_deltas for the metric with inverse-variance sample weights
+        (evaluate_variance: the metric holds the data of every view, then its variance field; floor as there).  The same lists;
+        returns (values, mean_weights), every entry bit-identical to setProjectionMatrices + evaluate_variance(floor) of that pose;
+        the current matrices stay."""
+        return self.evaluate_variance_pose_deltas_packed(*_pack_pose_lists(moved_views, moved_Ps), floor)
+
+    def evaluate_variance_pose_deltas_packed(self, moved_offsets, moved_views, moved_Ps, floor):
+        """The C signature itself, with the arguments of evaluate_pose_deltas_packed, then the floor; returns (values,
+        mean_weights)."""
+        return _pose_lists_call(_lib.lib().ecc_metric_evaluate_variance_pose_deltas, self._h, moved_offsets, moved_views, moved_Ps,
+                                (float(floor),), 2)
+
     def setPoseBatching(self, on=True):
         """ecc_metric_set_pose_batching: off = evaluate_poses runs every pose as its own stream-ordered evaluation."""
         check(_lib.lib().ecc_metric_set_pose_batching(self._h, 1 if on else 0))
@@ -881,6 +907,22 @@ class MetricRadonIntermediate:
         check(_lib.lib().ecc_metric_evaluate_weighted(self._h, C.byref(value), C.byref(coverage),
                                                       _ptr(pairs)))
         return _with_pairs((value.value, coverage.value), pairs, want_pairs)
+
+    def evaluate_variance(self, floor, want_pairs=False):
+        """ecc_metric_evaluate_variance: the metric with inverse-variance sample weights.  The metric holds 2 * n_views Radon
+        intermediates, channel-major: the data of every view, then the variance field V of every view on the same bin grid
+        (variance_intermediates; FILTER_NONE).  Per +-kappa sample of the pair i < j the squared difference of evaluate() counts with
+        omega = 1 / max(V_i(sample) + V_j(sample), floor), floor > 0 in the units of V (variance_floor proposes one).  Returns (value,
+        mean_weight): value = sum c / sum u over the pairs, mean_weight = sum u / n_pairs -- with want_pairs (value, mean_weight,
+        pairs), pairs (n_pairs, 2) float32 in the pair order of evaluate(cost): per pair c, its weighted value, and u = (sum omega) /
+        (number of samples), its mean weight.  V == 0.5 with floor <= 1: the bits of evaluate() and mean weight 1; a common factor on
+        all V and the floor leaves value as it is.  The current matrices and everything the metric keeps stay."""
+        n = 0 if self._Ps is None else len(self._Ps)  # (no matrices: the library reports it)
+        value, mean_weight = C.c_double(0.0), C.c_double(0.0)
+        pairs = np.zeros((n * (n - 1) // 2, 2), np.float32) if want_pairs else None
+        check(_lib.lib().ecc_metric_evaluate_variance(self._h, float(floor), C.byref(value), C.byref(mean_weight),
+                                                      _ptr(pairs)))
+        return _with_pairs((value.value, mean_weight.value), pairs, want_pairs)
 
     def evaluate_robust(self, loss, delta, want_pairs=False):
         """ecc_metric_evaluate_robust: the metric under a per-sample robust loss rho(d) = w(d) d^2 -- loss one of LOSS_HUBER,
@@ -1100,6 +1142,25 @@ class MetricRadonIntermediate:
                                                                  C.c_void_p(coverages.ctypes.data if K else 0),
                                                                  _ptr(pairs)))
         return _with_pairs((values, coverages), pairs, want_pairs)
+
+    def evaluate_variance_transforms(self, n_source, Ts, floor, want_pairs=False):
+        """ecc_metric_evaluate_variance_transforms: evaluate_transforms for the metric with inverse-variance sample weights
+        (evaluate_variance: 2 * n_views intermediates; floor as there; the variance follows the data, not the transformed matrix).
+        n_source and Ts as for evaluate_transforms.  Returns (values, mean_weights) = per transform (sum c / sum u, sum u / (n_source
+        n_target)) over the cross pairs -- with want_pairs (values, mean_weights, pairs), pairs (K, n_target, n_source, 2) float32 rows
+        {c, u}: every number bit-identical to setProjectionMatrices(composed) + evaluate_variance_pairs(the cross list, floor) per
+        transform; the current matrices stay."""
+        flat = _transforms_colmajor(Ts)
+        n_source = int(n_source)
+        K, n = len(flat), self.getNumberOfProjetions()
+        values, mean_weights = np.zeros(K, np.float64), np.zeros(K, np.float64)
+        pairs = np.zeros((K, max(n - n_source, 0), max(n_source, 0), 2), np.float32) if want_pairs else None
+        check(_lib.lib().ecc_metric_evaluate_variance_transforms(self._h, n_source, K, C.c_void_p(flat.ctypes.data if K else 0),
+                                                                 float(floor),
+                                                                 C.c_void_p(values.ctypes.data if K else 0),
+                                                                 C.c_void_p(mean_weights.ctypes.data if K else 0),
+                                                                 _ptr(pairs)))
+        return _with_pairs((values, mean_weights), pairs, want_pairs)
 
     def evaluate_robust_transforms(self, n_source, Ts, loss, delta, want_pairs=False):
         """ecc_metric_evaluate_robust_transforms: evaluate_transforms under the per-sample robust loss of evaluate_robust (loss, delta
@@ -1778,6 +1839,36 @@ def line_weights(ctx, flagged, size_alpha, size_t, zero_at_px=1.0, guard_bins=1)
         d.close()
         out.append(RadonIntermediate.from_host(ctx, w, n_u, n_v, FILTER_NONE))
     return out[0] if single else out
+
+
+def variance_intermediates(ctx, pixel_variances, size_alpha, size_t):
+    """Variance fields for MetricRadonIntermediate.evaluate_variance from images of pixel variances.  The model: V is the line
+    integral of the pixel variances -- the variance of a line integral of independent pixels --, up to a constant factor that cancels
+    in value.  For derivative data the same field is used, which ignores the correlation of the two neighbouring lines of the finite
+    difference.  pixel_variances: (n_v, n_u) float32, or (n, n_v, n_u) / a list of such images, for which a list is returned.
+    Returns RadonIntermediate(s) with FILTER_NONE on the bin grid size_alpha x size_t: RadonIntermediate.compute_batch with
+    FILTER_NONE / POST_IDENTITY, nothing else."""
+    arr = np.asarray(pixel_variances, np.float32)
+    single = arr.ndim == 2
+    if arr.ndim not in (2, 3):
+        raise ValueError("pixel_variances must be (n_v, n_u) or (n, n_v, n_u)")
+    out = RadonIntermediate.compute_batch(ctx, arr[None] if single else arr, size_alpha, size_t, FILTER_NONE, POST_IDENTITY)
+    return out[0] if single else out
+
+
+def variance_floor(fields, fraction=1e-3):
+    """ecc_host_variance_floor: a floor for evaluate_variance from the variance fields themselves -- fraction x the median of their
+    strictly positive finite entries (float32).  fields: one array or a sequence of arrays (RadonIntermediate.readback() of the
+    variance intermediates).  Raises EccError when no entry is positive or the fraction is not in (0, inf)."""
+    if isinstance(fields, np.ndarray):
+        flat = np.ascontiguousarray(fields, np.float32).reshape(-1)
+    else:
+        parts = [np.asarray(f, np.float32).reshape(-1) for f in fields]
+        flat = np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(0, np.float32))
+    out = C.c_float(0.0)
+    check(_lib.lib().ecc_host_variance_floor(C.c_void_p(flat.ctypes.data) if flat.size else None, flat.size, float(fraction),
+                                             C.cast(C.byref(out), C.c_void_p)))
+    return float(out.value)
 
 
 def robust_scale(pair_terms, k=1.0):

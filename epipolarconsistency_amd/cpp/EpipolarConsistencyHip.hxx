@@ -1180,6 +1180,85 @@ public:
                                                               coverages ? coverages->data() : 0x0, pair_terms));
     }
 
+    /// Not in the reference: ecc_metric_evaluate_variance -- the metric with inverse-variance sample weights.  The Radon
+    /// intermediates are the data of the n_views views, then the variance fields of the n_views views on the same bin grid (no
+    /// filter: the transform of the image of pixel variances): a sample of the pair i < j counts with 1 / max(V_i + V_j, floor),
+    /// floor > 0 in the units of V (varianceFloor proposes one).  Returns sum c / sum u over the pairs; mean_weight (nullable):
+    /// sum u / n_pairs; pair_terms (nullable): n_pairs x 2 floats, pair-major, per pair i < j {c, u}: the weighted value and the mean
+    /// weight of its samples.  V == 0.5 and floor <= 1: the bits of evaluate() (ecc_hip.h).  Single device only.
+    double evaluateVariance(float floor, double* mean_weight = 0x0, std::vector<float>* pair_terms = 0x0)
+    {
+        if (m_gh) throw std::runtime_error("evaluateVariance: not available on a device group");
+        const size_t n = Ps.size();
+        if (pair_terms) pair_terms->assign(n * (n > 0 ? n - 1 : 0), 0.f);
+        double value = 0.0;
+        detail::check(ecc_metric_evaluate_variance(m_h, floor, &value, mean_weight, (pair_terms && !pair_terms->empty()) ? pair_terms->data() : 0x0));
+        return value;
+    }
+
+    /// Not in the reference: ecc_metric_evaluate_variance_pairs -- evaluateVariance over an index list of (P0, P1, D0, D1) tuples
+    /// (indices: 4 ints per tuple; matrices P*, data intermediates D* in [0, n_views), the variance of a sample comes from
+    /// dtrs[n_views + D*]).  Returns sum c / sum u over the list; mean_weight (nullable): sum u / n_pairs; pair_terms (nullable):
+    /// n_pairs x 2 floats {c, u} in list order.  The sampling mode resolves from the list's length (ecc_hip.h).  Single device only.
+    double evaluateVariancePairs(const std::vector<int>& indices, float floor, double* mean_weight = 0x0, std::vector<float>* pair_terms = 0x0)
+    {
+        if (m_gh) throw std::runtime_error("evaluateVariancePairs: not available on a device group");
+        if (indices.size() % 4) throw std::runtime_error("evaluateVariancePairs: four indices per tuple");
+        const std::vector<int32_t> idx(indices.begin(), indices.end());
+        if (pair_terms) pair_terms->assign(idx.size() / 2, 0.f);
+        double value = 0.0;
+        if (mean_weight) *mean_weight = 0.0;
+        detail::check(ecc_metric_evaluate_variance_pairs(m_h, idx.empty() ? 0x0 : idx.data(), (int)(idx.size() / 4), floor, &value, mean_weight,
+                                                         (pair_terms && !pair_terms->empty()) ? pair_terms->data() : 0x0));
+        return value;
+    }
+
+    /// Not in the reference: ecc_metric_evaluate_variance_pose_deltas -- evaluatePoseDeltas for the metric with inverse-variance
+    /// sample weights (intermediates and floor as for evaluateVariance).  values[k] and mean_weights[k] (mean_weights nullable) are
+    /// bit-identical to replacing the views moved_views[k] by moved_Ps[k], setProjectionMatrices and evaluateVariance(floor); the
+    /// current matrices stay.  Single device only.
+    void evaluateVariancePoseDeltas(const std::vector<std::vector<int> >& moved_views,
+                                    const std::vector<std::vector<Geometry::ProjectionMatrix> >& moved_Ps, float floor,
+                                    std::vector<double>& values, std::vector<double>* mean_weights = 0x0)
+    {
+        if (m_gh) throw std::runtime_error("evaluateVariancePoseDeltas: not available on a device group");
+        if (moved_views.size() != moved_Ps.size()) throw std::runtime_error("evaluateVariancePoseDeltas: one matrix list per pose");
+        values.assign(moved_views.size(), 0.0);
+        if (mean_weights) mean_weights->assign(moved_views.size(), 0.0);
+        if (moved_views.empty()) return;
+        const PackedPoseLists l("evaluateVariancePoseDeltas", moved_views, moved_Ps);
+        detail::check(ecc_metric_evaluate_variance_pose_deltas(m_h, (int)moved_views.size(), l.off.data(), l.views_or_null(), l.Ps_or_null(),
+                                                               floor, values.data(), mean_weights ? mean_weights->data() : 0x0));
+    }
+
+    /// Not in the reference: ecc_metric_evaluate_variance_transforms -- evaluateTransforms for the metric with inverse-variance
+    /// sample weights (intermediates and floor as for evaluateVariance; n_source and Ts as for evaluateTransforms).  values[k] =
+    /// sum c / sum u over the n_source x n_target cross pairs under Ts[k]; mean_weights (nullable): sum u / (n_source n_target) per
+    /// transform; pair_terms (nullable): Ts.size() x n_target x n_source x 2 floats, per transform its rows {c, u} with the source
+    /// index fast.  Every number is bit-identical to Ps[i] * Ts[k] by ecc_host_compose_transform, setProjectionMatrices and
+    /// evaluateVariancePairs of the cross list per transform; the current matrices stay (ecc_hip.h).  Single device only.
+    void evaluateVarianceTransforms(int n_source, const std::vector<Geometry::RP3Homography>& Ts, float floor, std::vector<double>& values,
+                                    std::vector<double>* mean_weights = 0x0, float* pair_terms = 0x0)
+    {
+        if (m_gh) throw std::runtime_error("evaluateVarianceTransforms: not available on a device group");
+        values.assign(Ts.size(), 0.0);
+        if (mean_weights) mean_weights->assign(Ts.size(), 0.0);
+        std::vector<double> flat(16 * Ts.size());
+        for (size_t k = 0; k < Ts.size(); ++k)
+            for (int q = 0; q < 16; ++q) flat[16 * k + q] = Ts[k].data()[q];
+        detail::check(ecc_metric_evaluate_variance_transforms(m_h, n_source, (int)Ts.size(), flat.data(), floor, values.data(),
+                                                              mean_weights ? mean_weights->data() : 0x0, pair_terms));
+    }
+
+    /// ecc_host_variance_floor: a floor for evaluateVariance from the variance fields themselves -- fraction x the median of their
+    /// strictly positive finite entries.  Host only.
+    static float varianceFloor(const std::vector<float>& fields, double fraction = 1e-3)
+    {
+        float out = 0.f;
+        detail::check(ecc_host_variance_floor(fields.empty() ? 0x0 : fields.data(), (int64_t)fields.size(), fraction, &out));
+        return out;
+    }
+
     /// Not in the reference: ecc_metric_evaluate_robust_pose_deltas -- evaluatePoseDeltas under the per-sample robust loss of
     /// evaluateRobust (loss, delta as there).  values[k] and inlier_masses[k] (inlier_masses nullable) are bit-identical to replacing
     /// the views moved_views[k] by moved_Ps[k], setProjectionMatrices and evaluateRobust(loss, delta); the current matrices stay.

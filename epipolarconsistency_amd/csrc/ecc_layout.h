@@ -392,4 +392,16 @@ struct EccPairSamplesParams {
     int derivative0, derivative1;
 };
 
+// ---- the metric with inverse-variance sample weights (variance_kernel.hip) ------------------------------
+// 2 n_views channel-major intermediates and copies as for EccWeightedParams: channel 0 the data, channel 1 the variance fields.
+// Two float32 entries per pair i < j -- the weighted value c and the mean weight u -- stored COLUMN-major with the Gram form's
+// col_stride rule.
+struct EccVarianceParams {
+    int64_t paired_channel_bytes;  // as in EccGramParams
+    int64_t quad_channel_bytes;
+    float* values;                 // 2 columns of col_stride floats
+    int64_t col_stride;
+    float floor;                   // the least s = V_i + V_j a sample's weight 1 / s is formed from; finite, > 0
+};
+
 #endif

@@ -624,8 +624,8 @@ int ecc_metric_evaluate_view_hessian(ecc_metric* m, int n_channels, double* hess
  * pair, the position arithmetic of a kappa step once, 8 gathers --, one launch for the two sums.
  * Index lists and pose deltas: ecc_metric_evaluate_weighted_pairs, ecc_metric_evaluate_weighted_pose_deltas below.
  * The registration of two scans: ecc_metric_evaluate_weighted_transforms below.
- * Out of scope: full-matrices pose batches, range, group and RCCL forms; weights under use_corr; a
- * 1 / (sigma0^2 + sigma1^2) variance form.  A per-sample robust loss, for callers who do not know where the bad lines are:
+ * Out of scope: full-matrices pose batches, range, group and RCCL forms; weights under use_corr.  The
+ * 1 / (sigma0^2 + sigma1^2) variance form is ecc_metric_evaluate_variance below.  A per-sample robust loss, for callers who do not know where the bad lines are:
  * ecc_metric_evaluate_robust and its pose-delta and transform forms below (on a metric of n_views intermediates); the loss combined
  * with these weights: ecc_metric_evaluate_weighted_robust below. */
 int ecc_metric_evaluate_weighted(ecc_metric* m, double* value, double* coverage, float* pair_terms);
@@ -738,6 +738,73 @@ void ecc_host_compose_transform(const double* P12, const double* T16, double* ou
  * weights under use_corr. */
 int ecc_metric_evaluate_weighted_transforms(ecc_metric* m, int n_source, int n_transforms, const double* Ts, double* values,
                                             double* coverages, float* pair_terms);
+
+/* The metric with INVERSE-VARIANCE SAMPLE WEIGHTS (csrc/ecc_variance.hip, csrc/variance_kernel.hip): how noisy
+ * a redundant sample is.  In a low-dose or photon-starved scan the variance of a line integral is known from the physics -- it is
+ * the integral of the pixel variances along the line --, and the statistically right weight of the squared difference of two such
+ * integrals is 1 / (sigma0^2 + sigma1^2).  That is not a product of one weight per view, so no line weights W_i express it, and a
+ * robust loss reacts only after the noise has entered d^2.
+ *
+ * The metric holds 2 * n_views Radon intermediates, channel-major as for ecc_metric_evaluate_weighted: dtr i is the data of view i,
+ * dtr n_views + i its VARIANCE FIELD V_i on the same bin grid, normally the unfiltered (ECC_FILTER_NONE) transform of the image of
+ * pixel variances; any finite float is taken as it is.  A +-kappa sample of the pair i < j has the positions, kappa range and
+ * sampling mode of ecc_metric_evaluate_all; d is that evaluation's difference of the two signed data samples.  Per sample
+ *     s     = V_i(sample) + V_j(sample)        one float32 add of two UNSIGNED bilinear samples taken at the data's taps
+ *     omega = 1.0f / (s < floor ? floor : s)   one correctly rounded IEEE float32 division
+ * The fold sign is never applied to a variance sample.  The value term is the weighted form's with omega in mu's place --
+ *     polynomial loops             fmaf(om_p * dp, dp, (om_m * dm) * dm) * w06_dkappa
+ *     exact and reference loops    (((om_p * dp) * dp + (om_m * dm) * dm) * K0[6]) * dkappa
+ * -- accumulated in float64 per lane in the same trip order and reduced by the same wave tree; beside it each lane adds
+ * (double)(om_p + om_m), the weight mass, and 2.0, the sample count.  Per pair q:
+ *     c_q = the float32 value,
+ *     u_q = (float)(mass / count), the MEAN WEIGHT of the pair's samples; a pair without samples has c_q = 0, u_q = 1.0f.
+ *   floor: finite and > 0, in the units of V: the least s a weight is formed from, so that a line through air (V = 0 in both
+ *     views) cannot take the whole sum.  ecc_host_variance_floor proposes one from the fields.
+ *   *value (required) = sum c_q / sum u_q, *mean_weight (nullable) = sum u_q / n_pairs, both sums in the order of
+ *     csrc/ecc_sum_order.h.  sum u_q == 0: 0, 0 and ECC_OK.  Only RELATIVE variances matter to value: a common factor on all V and
+ *     the floor cancels.
+ *   pair_terms (host, nullable): n_pairs x 2 float32, pair-major in the pair order of get_ij, each row {c_q, u_q}.
+ * Model: V is the line integral of the pixel variances up to a constant factor.  For derivative data the same field is used, which
+ * ignores the correlation of the two neighbouring lines of the finite difference.
+ *
+ * The contract (tests/test_gpu_variance.py):
+ *   1. V == 0.5f everywhere and floor <= 1: value and the c column have the bits of ecc_metric_evaluate_all, every u_q and
+ *      mean_weight are 1.0.
+ *   2. V == 0 everywhere and floor == 4: every c_q is exactly 1/4 of ecc_metric_evaluate_all's entry, every u_q is 0.25, value has
+ *      ecc_metric_evaluate_all's bits.
+ *   3. All V and the floor multiplied by 4: every c_q and u_q is multiplied by 1/4 exactly, value keeps its bits.
+ *   4. c_q and u_q agree with a float64 statement (tests/variance_terms.py) to the project's bars.
+ *   - The call changes nothing a later call can see.  (It shares ecc_metric_evaluate_gram's scratch.)
+ *   - Errors before anything is launched or written, ECC_ERR_INVALID_ARGUMENT, checked in this order: m == NULL, value == NULL, no
+ *     matrices set, fewer than two views, n_dtrs != 2 * n_views, a floor that is not finite and > 0.  use_corr set: ECC_ERR_UNSUPPORTED.
+ *
+ * ecc_metric_evaluate_variance_pairs: an index list of n_pairs tuples (P0, P1, D0, D1) as for ecc_metric_evaluate_weighted_pairs: P*
+ * index the current matrices, D* the DATA intermediates in [0, n_views); the variance of a sample comes from dtr n_views + D*.  The
+ * sampling mode resolves from the list's length.  With tuples (i, j, i, j) the rows have the bits of ecc_metric_evaluate_variance's
+ * rows of those pairs under the same resolved mode.  n_pairs == 0: ECC_OK, nothing written.
+ * ecc_metric_evaluate_variance_pose_deltas: the lists of ecc_metric_evaluate_pose_deltas; values[k] and mean_weights[k]
+ * (mean_weights nullable) have THE BITS of ecc_metric_set_projections(pose k) + ecc_metric_evaluate_variance
+ * (tests/test_gpu_variance_batches.py).  The launches, the batches and what the batch does not take are those of
+ * ecc_metric_evaluate_weighted_pose_deltas, with the variance pair kernel in the weighted one's place.
+ * ecc_metric_evaluate_variance_transforms: views, transforms and the cross list of ecc_metric_evaluate_weighted_transforms;
+ * values[k] = sum c / sum u, mean_weights[k] (nullable) = sum u / count over the list of transform k, pair_terms (nullable)
+ * n_transforms x n_target x n_source x 2 floats; all three have THE BITS of ecc_metric_set_projections(the composed matrices) +
+ * ecc_metric_evaluate_variance_pairs(that list).
+ * The argument checks of the three are those of their weighted siblings, then the floor's.
+ *
+ * ecc_host_variance_floor (host only, no device): *floor = (float)(fraction x the median of the strictly positive finite entries of
+ * v[0 .. count)); an even number of them: the mean of the two middle ones.  ECC_ERR_INVALID_ARGUMENT for a null pointer, a negative
+ * count, a fraction that is not in (0, infinity), or no positive entry.
+ * Not built: kept base columns; range, group and RCCL forms; the variance form under use_corr; its combination with the robust
+ * loss; a covariance-aware model for derivative data. */
+int ecc_metric_evaluate_variance(ecc_metric* m, float floor, double* value, double* mean_weight, float* pair_terms);
+int ecc_metric_evaluate_variance_pairs(ecc_metric* m, const int32_t* idx4, int n_pairs, float floor, double* value, double* mean_weight,
+                                       float* pair_terms);
+int ecc_metric_evaluate_variance_pose_deltas(ecc_metric* m, int n_poses, const int32_t* moved_offsets, const int32_t* moved_views,
+                                             const double* moved_Ps, float floor, double* values, double* mean_weights);
+int ecc_metric_evaluate_variance_transforms(ecc_metric* m, int n_source, int n_transforms, const double* Ts, float floor, double* values,
+                                            double* mean_weights, float* pair_terms);
+int ecc_host_variance_floor(const float* v, int64_t count, double fraction, float* floor);
 
 /* The metric under a PER-SAMPLE ROBUST LOSS (csrc/ecc_robust.hip, csrc/robust_kernel.hip): for callers who do NOT
  * know where the bad lines are -- an instrument nobody flagged, a truncated view, a detector defect that appears mid-scan.  The
