@@ -387,9 +387,9 @@ def _check_pose_lists(moved_offsets, moved_views, moved_Ps):
     return off, views, flat
 
 
-def _ptr(a):
-    """The address of an optional array for a C call: None for no array and for an empty one."""
-    return C.c_void_p(a.ctypes.data) if (a is not None and a.size) else None
+def _ptr(a, null=None):
+    """The address of an optional array for a C call: `null` (None) for no array and for an empty one."""
+    return C.c_void_p(a.ctypes.data) if (a is not None and a.size) else null
 
 
 def _idx4_list(idx4):
@@ -420,6 +420,61 @@ def _pose_lists_call(fn, handle, moved_offsets, moved_views, moved_Ps, extra, n_
     check(fn(handle, len(off) - 1, C.c_void_p(off.ctypes.data), _ptr(views), _ptr(flat), *extra,
              *[C.c_void_p(r.ctypes.data) for r in results]))
     return results
+
+
+def _n_all_pairs(Ps):
+    n = 0 if Ps is None else len(Ps)  # (no matrices: the library reports it)
+    return n * (n - 1) // 2
+
+
+def _scalar_form_call(fn, handle, lead, extra, n_scalars, n_rows, n_columns, want_pairs, mid=(), planes=()):
+    """fn(handle, *lead, *extra, *mid, scalar results..., pairs) -> the n_scalars floats, then `planes` -- with want_pairs also pairs,
+    (n_rows, n_columns) float32.  lead: () for all pairs, (the index list's address, its length) for a list; mid: what a map call
+    passes between the scalars going in and those coming out."""
+    scalars = [C.c_double(0.0) for _ in range(n_scalars)]
+    pairs = np.zeros((n_rows, n_columns), np.float32) if want_pairs else None
+    check(fn(handle, *lead, *extra, *mid, *[C.byref(s) for s in scalars], _ptr(pairs)))
+    return _with_pairs(tuple(s.value for s in scalars) + tuple(planes), pairs, want_pairs)
+
+
+def _map_form_call(fn, metric, lead, extra, views, k, n_scalars, n_rows, n_columns, want_pairs):
+    """_scalar_form_call with the views to map (an int32 array, None: all) and their k HITS and k REJ planes; the metric remembers k
+    for its *_map_weights once the call has succeeded.  Returns (scalars..., hits, rejected[, pairs])."""
+    hits, rejected = metric._robust_map_planes(k)
+    out = _scalar_form_call(fn, metric._h, lead, extra, n_scalars, n_rows, n_columns, want_pairs,
+                            (_ptr(views), 0 if views is None else len(views), _ptr(hits), _ptr(rejected)), (hits, rejected))
+    metric._robust_map_count = k
+    return out
+
+
+def _map_weights_call(fn, metric, min_hits, gain):
+    """fn(handle, min_hits, gain, handles) for the map the metric holds -> one RadonIntermediate per mapped view."""
+    k = getattr(metric, "_robust_map_count", 0)
+    hs = (C.c_void_p * max(k, 1))()
+    check(fn(metric._h, float(min_hits), float(gain), hs))
+    return [RadonIntermediate(metric.ctx, C.c_void_p(h)) for h in hs[:k]]
+
+
+_NULL = C.c_void_p(0)  # what the transforms calls pass for an empty array (the other families: None)
+
+
+def _transforms_call(fn, handle, n, n_source, flat, extra, n_results, n_columns, want_pairs):
+    """fn(handle, n_source, K, transforms, *extra, results..., pairs) over the (K, 16) rows of _transforms_colmajor on a metric of n
+    views -> the n_results float64 arrays of K -- with want_pairs also pairs, (K, n_target, n_source, n_columns) float32 (n_columns
+    None: no trailing axis)."""
+    n_source, K = int(n_source), len(flat)
+    results = tuple(np.zeros(K, np.float64) for _ in range(n_results))
+    shape = (K, max(n - n_source, 0), max(n_source, 0)) + (() if n_columns is None else (n_columns,))
+    pairs = np.zeros(shape, np.float32) if want_pairs else None
+    check(fn(handle, n_source, K, _ptr(flat, _NULL), *extra, *[_ptr(r, _NULL) for r in results], _ptr(pairs)))
+    return _with_pairs(results, pairs, want_pairs)
+
+
+def _last_count(fn, handle, ctype=C.c_int64):
+    """fn(handle, &v) of the last_* getters -> v."""
+    v = ctype(0)
+    check(fn(handle, C.byref(v)))
+    return v.value
 
 
 class MetricRadonIntermediate:
@@ -621,9 +676,7 @@ class MetricRadonIntermediate:
 
     def last_evaluated_pairs(self):
         """Pairs the last evaluate() / evaluate_range() actually recomputed."""
-        v = C.c_int64()
-        check(_lib.lib().ecc_metric_last_evaluated_pairs(self._h, C.byref(v)))
-        return v.value
+        return _last_count(_lib.lib().ecc_metric_last_evaluated_pairs, self._h)
 
     # -- evaluation ----------------------------------------------------------------------------
     def evaluate(self, arg=None, out=None):
@@ -744,12 +797,7 @@ class MetricRadonIntermediate:
         (sum c / sum u, sum u / n_pairs) over the list -- with want_pairs (value, coverage, pairs), pairs (n_pairs, 2) float32 rows
         {c, u} in list order.  The sampling mode resolves from the list's length, as evaluate(indices) resolves it."""
         idx = _idx4_list(idx4)
-        value, coverage = C.c_double(0.0), C.c_double(0.0)
-        pairs = np.zeros((len(idx), 2), np.float32) if want_pairs else None
-        check(_lib.lib().ecc_metric_evaluate_weighted_pairs(self._h, _ptr(idx), len(idx),
-                                                            C.byref(value), C.byref(coverage),
-                                                            _ptr(pairs)))
-        return _with_pairs((value.value, coverage.value), pairs, want_pairs)
+        return _scalar_form_call(_lib.lib().ecc_metric_evaluate_weighted_pairs, self._h, (_ptr(idx), len(idx)), (), 2, len(idx), 2, want_pairs)
 
     def evaluate_variance_pairs(self, idx4, floor, want_pairs=False):
         """ecc_metric_evaluate_variance_pairs: evaluate_variance over an index list of (P0, P1, D0, D1) tuples -- matrices P*, data
@@ -757,12 +805,8 @@ class MetricRadonIntermediate:
         = (sum c / sum u, sum u / n_pairs) over the list -- with want_pairs (value, mean_weight, pairs), pairs (n_pairs, 2) float32
         rows {c, u} in list order.  The sampling mode resolves from the list's length, as evaluate(indices) resolves it."""
         idx = _idx4_list(idx4)
-        value, mean_weight = C.c_double(0.0), C.c_double(0.0)
-        pairs = np.zeros((len(idx), 2), np.float32) if want_pairs else None
-        check(_lib.lib().ecc_metric_evaluate_variance_pairs(self._h, _ptr(idx), len(idx), float(floor),
-                                                            C.byref(value), C.byref(mean_weight),
-                                                            _ptr(pairs)))
-        return _with_pairs((value.value, mean_weight.value), pairs, want_pairs)
+        return _scalar_form_call(_lib.lib().ecc_metric_evaluate_variance_pairs, self._h, (_ptr(idx), len(idx)), (float(floor),), 2, len(idx), 2,
+                                 want_pairs)
 
     def evaluate_variance_pose_deltas(self, moved_views, moved_Ps, floor):
         """ecc_metric_evaluate_variance_pose_deltas: evaluate_pose_deltas for the metric with inverse-variance sample weights
@@ -783,9 +827,7 @@ class MetricRadonIntermediate:
         return self
 
     def last_batched_poses(self):
-        v = C.c_int64(0)
-        check(_lib.lib().ecc_metric_last_batched_poses(self._h, C.byref(v)))
-        return v.value
+        return _last_count(_lib.lib().ecc_metric_last_batched_poses, self._h)
 
     def evaluate_gradient(self, view, Ps_plus, Ps_minus, h, want_probes=False):
         """ecc_metric_evaluate_gradient: the metric at the current matrices and its central-difference gradient over p pose
@@ -829,9 +871,7 @@ class MetricRadonIntermediate:
     def last_gradient_path(self):
         """ecc_metric_last_gradient_path: 1 = the pose batch (evaluate_pose_deltas; the default), 0 = every probe sequentially
         (setPoseBatching(False)), 2 = the probes' records and sampling as one launch (debugSetGradientLaunch(True))."""
-        v = C.c_int(0)
-        check(_lib.lib().ecc_metric_last_gradient_path(self._h, C.byref(v)))
-        return v.value
+        return _last_count(_lib.lib().ecc_metric_last_gradient_path, self._h, C.c_int)
 
     def evaluate_gram(self, n_channels, want_pairs=False):
         """ecc_metric_evaluate_gram: the metric as a quadratic form of the coefficients of n_channels fixed channel images per view
@@ -901,12 +941,7 @@ class MetricRadonIntermediate:
         with want_pairs (value, coverage, pairs), pairs (n_pairs, 2) float32 in the pair order of evaluate(cost): per pair c, its
         weighted value, and u = (sum mu) / (number of samples), its coverage.  All weights 1: the bits of evaluate() and coverage 1.
         The current matrices and everything the metric keeps stay."""
-        n = 0 if self._Ps is None else len(self._Ps)  # (no matrices: the library reports it)
-        value, coverage = C.c_double(0.0), C.c_double(0.0)
-        pairs = np.zeros((n * (n - 1) // 2, 2), np.float32) if want_pairs else None
-        check(_lib.lib().ecc_metric_evaluate_weighted(self._h, C.byref(value), C.byref(coverage),
-                                                      _ptr(pairs)))
-        return _with_pairs((value.value, coverage.value), pairs, want_pairs)
+        return _scalar_form_call(_lib.lib().ecc_metric_evaluate_weighted, self._h, (), (), 2, _n_all_pairs(self._Ps), 2, want_pairs)
 
     def evaluate_variance(self, floor, want_pairs=False):
         """ecc_metric_evaluate_variance: the metric with inverse-variance sample weights.  The metric holds 2 * n_views Radon
@@ -917,12 +952,7 @@ class MetricRadonIntermediate:
         pairs), pairs (n_pairs, 2) float32 in the pair order of evaluate(cost): per pair c, its weighted value, and u = (sum omega) /
         (number of samples), its mean weight.  V == 0.5 with floor <= 1: the bits of evaluate() and mean weight 1; a common factor on
         all V and the floor leaves value as it is.  The current matrices and everything the metric keeps stay."""
-        n = 0 if self._Ps is None else len(self._Ps)  # (no matrices: the library reports it)
-        value, mean_weight = C.c_double(0.0), C.c_double(0.0)
-        pairs = np.zeros((n * (n - 1) // 2, 2), np.float32) if want_pairs else None
-        check(_lib.lib().ecc_metric_evaluate_variance(self._h, float(floor), C.byref(value), C.byref(mean_weight),
-                                                      _ptr(pairs)))
-        return _with_pairs((value.value, mean_weight.value), pairs, want_pairs)
+        return _scalar_form_call(_lib.lib().ecc_metric_evaluate_variance, self._h, (), (float(floor),), 2, _n_all_pairs(self._Ps), 2, want_pairs)
 
     def evaluate_robust(self, loss, delta, want_pairs=False):
         """ecc_metric_evaluate_robust: the metric under a per-sample robust loss rho(d) = w(d) d^2 -- loss one of LOSS_HUBER,
@@ -931,12 +961,8 @@ class MetricRadonIntermediate:
         sum c / n_pairs, inlier_mass = sum u / n_pairs -- with want_pairs (value, inlier_mass, pairs), pairs (n_pairs, 3) float32 in
         the pair order of evaluate(cost): per pair c, its value, u, the mean IRLS weight of its samples in (0, 1], and r, their mean
         squared raw residual (robust_scale takes delta from it).  The current matrices and everything the metric keeps stay."""
-        n = 0 if self._Ps is None else len(self._Ps)  # (no matrices: the library reports it)
-        value, mass = C.c_double(0.0), C.c_double(0.0)
-        pairs = np.zeros((n * (n - 1) // 2, 3), np.float32) if want_pairs else None
-        check(_lib.lib().ecc_metric_evaluate_robust(self._h, int(loss), float(delta), C.byref(value), C.byref(mass),
-                                                    _ptr(pairs)))
-        return _with_pairs((value.value, mass.value), pairs, want_pairs)
+        return _scalar_form_call(_lib.lib().ecc_metric_evaluate_robust, self._h, (), (int(loss), float(delta)), 2, _n_all_pairs(self._Ps), 3,
+                                 want_pairs)
 
     def evaluate_robust_pairs(self, idx4, loss, delta, want_pairs=False):
         """ecc_metric_evaluate_robust_pairs: evaluate_robust over an index list of (P0, P1, D0, D1) tuples, as evaluate(indices)
@@ -944,12 +970,8 @@ class MetricRadonIntermediate:
         float32 rows {c, u, r} in list order.  The sampling mode resolves from the list's length; an empty list writes nothing
         (0.0, 0.0)."""
         idx = _idx4_list(idx4)
-        value, mass = C.c_double(0.0), C.c_double(0.0)
-        pairs = np.zeros((len(idx), 3), np.float32) if want_pairs else None
-        check(_lib.lib().ecc_metric_evaluate_robust_pairs(self._h, _ptr(idx), len(idx),
-                                                          int(loss), float(delta), C.byref(value), C.byref(mass),
-                                                          _ptr(pairs)))
-        return _with_pairs((value.value, mass.value), pairs, want_pairs)
+        return _scalar_form_call(_lib.lib().ecc_metric_evaluate_robust_pairs, self._h, (_ptr(idx), len(idx)), (int(loss), float(delta)), 2,
+                                 len(idx), 3, want_pairs)
 
     def _robust_map_views(self, views):
         """(the int32 list or None, how many planes a map call returns)"""
@@ -971,17 +993,11 @@ class MetricRadonIntermediate:
         order.  Returns (value, inlier_mass, hits, rejected[, pairs]); hits, rejected: (len(views), n_t, n_alpha) float32.  The sums
         are fixed point on the device: the same call gives the same bits.  REJ / HITS is the mean distrust of a line;
         robust_map_weights turns the held map into line weights.  delta = inf: rejected is all zeros."""
-        n = 0 if self._Ps is None else len(self._Ps)  # (no matrices: the library reports it)
         v, k = self._robust_map_views(views)
         if views is None:
-            k = n
-        hits, rejected = self._robust_map_planes(k)
-        value, mass = C.c_double(0.0), C.c_double(0.0)
-        pairs = np.zeros((n * (n - 1) // 2, 3), np.float32) if want_pairs else None
-        check(_lib.lib().ecc_metric_evaluate_robust_map(self._h, int(loss), float(delta), _ptr(v), 0 if v is None else len(v),
-                                                        _ptr(hits), _ptr(rejected), C.byref(value), C.byref(mass), _ptr(pairs)))
-        self._robust_map_count = k
-        return _with_pairs((value.value, mass.value, hits, rejected), pairs, want_pairs)
+            k = 0 if self._Ps is None else len(self._Ps)
+        return _map_form_call(_lib.lib().ecc_metric_evaluate_robust_map, self, (), (int(loss), float(delta)), v, k, 2,
+                              _n_all_pairs(self._Ps), 3, want_pairs)
 
     def evaluate_robust_map_pairs(self, idx4, loss, delta, views=None, want_pairs=False):
         """ecc_metric_evaluate_robust_map_pairs: evaluate_robust_map over an index list of (P0, P1, D0, D1) tuples; the view of a
@@ -989,24 +1005,15 @@ class MetricRadonIntermediate:
         twice deposits twice; the planes do not depend on the order of the list."""
         idx = _idx4_list(idx4)
         v, k = self._robust_map_views(views)
-        hits, rejected = self._robust_map_planes(k)
-        value, mass = C.c_double(0.0), C.c_double(0.0)
-        pairs = np.zeros((len(idx), 3), np.float32) if want_pairs else None
-        check(_lib.lib().ecc_metric_evaluate_robust_map_pairs(self._h, _ptr(idx), len(idx), int(loss), float(delta), _ptr(v),
-                                                              0 if v is None else len(v), _ptr(hits), _ptr(rejected), C.byref(value),
-                                                              C.byref(mass), _ptr(pairs)))
-        self._robust_map_count = k
-        return _with_pairs((value.value, mass.value, hits, rejected), pairs, want_pairs)
+        return _map_form_call(_lib.lib().ecc_metric_evaluate_robust_map_pairs, self, (_ptr(idx), len(idx)), (int(loss), float(delta)), v, k, 2,
+                              len(idx), 3, want_pairs)
 
     def robust_map_weights(self, min_hits=1.0, gain=1.0):
         """ecc_metric_robust_map_weights: the map the last evaluate_robust_map[_pairs] call left on the device as line weights, a list of
         RadonIntermediate (FILTER_NONE, values in [0, 1]), one per mapped view in the order of `views`: the second half of a 2 n
         metric for evaluate_weighted / evaluate_weighted_robust.  Per bin with the float32 plane values h and r: 1 where h < min_hits,
         else float32(max(0, 1 - gain * r / h)) in float64.  Raises if no map is held (refresh_dtrs and set_params drop it)."""
-        k = getattr(self, "_robust_map_count", 0)
-        hs = (C.c_void_p * max(k, 1))()
-        check(_lib.lib().ecc_metric_robust_map_weights(self._h, float(min_hits), float(gain), hs))
-        return [RadonIntermediate(self.ctx, C.c_void_p(h)) for h in hs[:k]]
+        return _map_weights_call(_lib.lib().ecc_metric_robust_map_weights, self, min_hits, gain)
 
     def robust_map_fixed(self):
         """ecc_debug_robust_map_fixed: the held map's fixed-point sums (quantum 2^-32) folded to bins, (hits, rejected) of
@@ -1039,16 +1046,9 @@ class MetricRadonIntermediate:
         hits, rejected: (len(views), n_t, n_alpha) float32, pairs (n_pairs, 4) rows {c, u, k, r}.  Fixed-point sums on the device:
         the same call gives the same bits.  weighted_robust_map_weights multiplies the held map's factor into the weights it was
         made under.  Weights outside [0, 1]: value, coverage, inlier_mass and pairs as evaluate_weighted_robust, planes unspecified."""
-        n = 0 if self._Ps is None else len(self._Ps)  # (no matrices: the library reports it)
         v, k = self._weighted_map_views(views)
-        hits, rejected = self._robust_map_planes(k)
-        value, coverage, mass = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
-        pairs = np.zeros((n * (n - 1) // 2, 4), np.float32) if want_pairs else None
-        check(_lib.lib().ecc_metric_evaluate_weighted_robust_map(self._h, int(loss), float(delta), _ptr(v), 0 if v is None else len(v),
-                                                                 _ptr(hits), _ptr(rejected), C.byref(value), C.byref(coverage),
-                                                                 C.byref(mass), _ptr(pairs)))
-        self._robust_map_count = k
-        return _with_pairs((value.value, coverage.value, mass.value, hits, rejected), pairs, want_pairs)
+        return _map_form_call(_lib.lib().ecc_metric_evaluate_weighted_robust_map, self, (), (int(loss), float(delta)), v, k, 3,
+                              _n_all_pairs(self._Ps), 4, want_pairs)
 
     def evaluate_weighted_robust_map_pairs(self, idx4, loss, delta, views=None, want_pairs=False):
         """ecc_metric_evaluate_weighted_robust_map_pairs: evaluate_weighted_robust_map over an index list of (P0, P1, D0, D1) tuples
@@ -1056,14 +1056,8 @@ class MetricRadonIntermediate:
         map follow the data index.  A pair listed twice deposits twice; the planes do not depend on the order of the list."""
         idx = _idx4_list(idx4)
         v, k = self._weighted_map_views(views)
-        hits, rejected = self._robust_map_planes(k)
-        value, coverage, mass = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
-        pairs = np.zeros((len(idx), 4), np.float32) if want_pairs else None
-        check(_lib.lib().ecc_metric_evaluate_weighted_robust_map_pairs(self._h, _ptr(idx), len(idx), int(loss), float(delta), _ptr(v),
-                                                                       0 if v is None else len(v), _ptr(hits), _ptr(rejected),
-                                                                       C.byref(value), C.byref(coverage), C.byref(mass), _ptr(pairs)))
-        self._robust_map_count = k
-        return _with_pairs((value.value, coverage.value, mass.value, hits, rejected), pairs, want_pairs)
+        return _map_form_call(_lib.lib().ecc_metric_evaluate_weighted_robust_map_pairs, self, (_ptr(idx), len(idx)), (int(loss), float(delta)),
+                              v, k, 3, len(idx), 4, want_pairs)
 
     def weighted_robust_map_weights(self, min_hits=1.0, gain=1.0):
         """ecc_metric_weighted_robust_map_weights: the next pass's line weights from the map the last
@@ -1071,10 +1065,7 @@ class MetricRadonIntermediate:
         view in the order of `views`: W_v * factor in float32, W_v the metric's current weights of that view and factor
         robust_map_weights' rule on the held planes (1 where h < min_hits, else float32(max(0, 1 - gain * r / h)) in float64).
         Raises if no map is held or the held map is evaluate_robust_map's."""
-        k = getattr(self, "_robust_map_count", 0)
-        hs = (C.c_void_p * max(k, 1))()
-        check(_lib.lib().ecc_metric_weighted_robust_map_weights(self._h, float(min_hits), float(gain), hs))
-        return [RadonIntermediate(self.ctx, C.c_void_p(h)) for h in hs[:k]]
+        return _map_weights_call(_lib.lib().ecc_metric_weighted_robust_map_weights, self, min_hits, gain)
 
     def evaluate_weighted_robust(self, loss, delta, want_pairs=False):
         """ecc_metric_evaluate_weighted_robust: line weights and the robust loss together, for scans that have both kinds of bad
@@ -1086,12 +1077,8 @@ class MetricRadonIntermediate:
         per pair c, its value, u, its coverage, k, the weight mass the loss keeps, and r, the weighted mean squared raw residual
         (weighted_robust_scale takes delta from r / u).  delta = inf: the bits of evaluate_weighted; all weights 1: the bits of
         evaluate_robust.  The current matrices and everything the metric keeps stay."""
-        n = 0 if self._Ps is None else len(self._Ps)  # (no matrices: the library reports it)
-        value, coverage, mass = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
-        pairs = np.zeros((n * (n - 1) // 2, 4), np.float32) if want_pairs else None
-        check(_lib.lib().ecc_metric_evaluate_weighted_robust(self._h, int(loss), float(delta), C.byref(value), C.byref(coverage), C.byref(mass),
-                                                             _ptr(pairs)))
-        return _with_pairs((value.value, coverage.value, mass.value), pairs, want_pairs)
+        return _scalar_form_call(_lib.lib().ecc_metric_evaluate_weighted_robust, self._h, (), (int(loss), float(delta)), 3,
+                                 _n_all_pairs(self._Ps), 4, want_pairs)
 
     def evaluate_weighted_robust_pairs(self, idx4, loss, delta, want_pairs=False):
         """ecc_metric_evaluate_weighted_robust_pairs: evaluate_weighted_robust over an index list of (P0, P1, D0, D1) tuples as
@@ -1100,12 +1087,8 @@ class MetricRadonIntermediate:
         {c, u, k, r} in list order.  The sampling mode resolves from the list's length; an empty list writes nothing
         (0.0, 0.0, 0.0)."""
         idx = _idx4_list(idx4)
-        value, coverage, mass = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
-        pairs = np.zeros((len(idx), 4), np.float32) if want_pairs else None
-        check(_lib.lib().ecc_metric_evaluate_weighted_robust_pairs(self._h, _ptr(idx), len(idx),
-                                                                   int(loss), float(delta), C.byref(value), C.byref(coverage), C.byref(mass),
-                                                                   _ptr(pairs)))
-        return _with_pairs((value.value, coverage.value, mass.value), pairs, want_pairs)
+        return _scalar_form_call(_lib.lib().ecc_metric_evaluate_weighted_robust_pairs, self._h, (_ptr(idx), len(idx)), (int(loss), float(delta)),
+                                 3, len(idx), 4, want_pairs)
 
     def evaluate_transforms(self, n_source, Ts, want_pairs=False):
         """ecc_metric_evaluate_transforms: the registration of two scans (ref: tools/Registration/Registration3D3D.hxx).  The
@@ -1116,14 +1099,9 @@ class MetricRadonIntermediate:
         bit-identical to setProjectionMatrices(composed) + evaluate(index list) per transform; the current matrices stay.
         Fix the object radius (setObjectRadius) for a sweep whose values are compared with each other."""
         flat = _transforms_colmajor(Ts)
-        n_source = int(n_source)
-        K, n = len(flat), self.getNumberOfProjetions()
-        means = np.zeros(K, np.float64)
-        pairs = np.zeros((K, max(n - n_source, 0), max(n_source, 0)), np.float32) if want_pairs else None
-        check(_lib.lib().ecc_metric_evaluate_transforms(self._h, n_source, K, C.c_void_p(flat.ctypes.data if K else 0),
-                                                        C.c_void_p(means.ctypes.data if K else 0),
-                                                        _ptr(pairs)))
-        return (means, pairs) if want_pairs else means
+        out = _transforms_call(_lib.lib().ecc_metric_evaluate_transforms, self._h, self.getNumberOfProjetions(), n_source, flat, (), 1, None,
+                               want_pairs)
+        return out if want_pairs else out[0]
 
     def evaluate_weighted_transforms(self, n_source, Ts, want_pairs=False):
         """ecc_metric_evaluate_weighted_transforms: evaluate_transforms for the metric with per-line weights (evaluate_weighted: the
@@ -1133,15 +1111,8 @@ class MetricRadonIntermediate:
         number bit-identical to setProjectionMatrices(composed) + evaluate_weighted_pairs(the cross list) per transform; the current
         matrices stay."""
         flat = _transforms_colmajor(Ts)
-        n_source = int(n_source)
-        K, n = len(flat), self.getNumberOfProjetions()
-        values, coverages = np.zeros(K, np.float64), np.zeros(K, np.float64)
-        pairs = np.zeros((K, max(n - n_source, 0), max(n_source, 0), 2), np.float32) if want_pairs else None
-        check(_lib.lib().ecc_metric_evaluate_weighted_transforms(self._h, n_source, K, C.c_void_p(flat.ctypes.data if K else 0),
-                                                                 C.c_void_p(values.ctypes.data if K else 0),
-                                                                 C.c_void_p(coverages.ctypes.data if K else 0),
-                                                                 _ptr(pairs)))
-        return _with_pairs((values, coverages), pairs, want_pairs)
+        return _transforms_call(_lib.lib().ecc_metric_evaluate_weighted_transforms, self._h, self.getNumberOfProjetions(), n_source, flat, (), 2,
+                                2, want_pairs)
 
     def evaluate_variance_transforms(self, n_source, Ts, floor, want_pairs=False):
         """ecc_metric_evaluate_variance_transforms: evaluate_transforms for the metric with inverse-variance sample weights
@@ -1151,16 +1122,8 @@ class MetricRadonIntermediate:
         {c, u}: every number bit-identical to setProjectionMatrices(composed) + evaluate_variance_pairs(the cross list, floor) per
         transform; the current matrices stay."""
         flat = _transforms_colmajor(Ts)
-        n_source = int(n_source)
-        K, n = len(flat), self.getNumberOfProjetions()
-        values, mean_weights = np.zeros(K, np.float64), np.zeros(K, np.float64)
-        pairs = np.zeros((K, max(n - n_source, 0), max(n_source, 0), 2), np.float32) if want_pairs else None
-        check(_lib.lib().ecc_metric_evaluate_variance_transforms(self._h, n_source, K, C.c_void_p(flat.ctypes.data if K else 0),
-                                                                 float(floor),
-                                                                 C.c_void_p(values.ctypes.data if K else 0),
-                                                                 C.c_void_p(mean_weights.ctypes.data if K else 0),
-                                                                 _ptr(pairs)))
-        return _with_pairs((values, mean_weights), pairs, want_pairs)
+        return _transforms_call(_lib.lib().ecc_metric_evaluate_variance_transforms, self._h, self.getNumberOfProjetions(), n_source, flat,
+                                (float(floor),), 2, 2, want_pairs)
 
     def evaluate_robust_transforms(self, n_source, Ts, loss, delta, want_pairs=False):
         """ecc_metric_evaluate_robust_transforms: evaluate_transforms under the per-sample robust loss of evaluate_robust (loss, delta
@@ -1169,16 +1132,8 @@ class MetricRadonIntermediate:
         (K, n_target, n_source, 3) float32 rows {c, u, r}: every number bit-identical to setProjectionMatrices(composed) +
         evaluate_robust_pairs(the cross list, loss, delta) per transform; the current matrices stay."""
         flat = _transforms_colmajor(Ts)
-        n_source = int(n_source)
-        K, n = len(flat), self.getNumberOfProjetions()
-        values, masses = np.zeros(K, np.float64), np.zeros(K, np.float64)
-        pairs = np.zeros((K, max(n - n_source, 0), max(n_source, 0), 3), np.float32) if want_pairs else None
-        check(_lib.lib().ecc_metric_evaluate_robust_transforms(self._h, n_source, K, C.c_void_p(flat.ctypes.data if K else 0),
-                                                               int(loss), float(delta),
-                                                               C.c_void_p(values.ctypes.data if K else 0),
-                                                               C.c_void_p(masses.ctypes.data if K else 0),
-                                                               _ptr(pairs)))
-        return _with_pairs((values, masses), pairs, want_pairs)
+        return _transforms_call(_lib.lib().ecc_metric_evaluate_robust_transforms, self._h, self.getNumberOfProjetions(), n_source, flat,
+                                (int(loss), float(delta)), 2, 3, want_pairs)
 
     def evaluate_weighted_robust_transforms(self, n_source, Ts, loss, delta, want_pairs=False):
         """ecc_metric_evaluate_weighted_robust_transforms: evaluate_transforms under line weights and the robust loss together
@@ -1188,24 +1143,13 @@ class MetricRadonIntermediate:
         setProjectionMatrices(composed) + evaluate_weighted_robust_pairs(the cross list, loss, delta) per transform; the current
         matrices stay."""
         flat = _transforms_colmajor(Ts)
-        n_source = int(n_source)
-        K, n = len(flat), self.getNumberOfProjetions()
-        values, coverages, masses = np.zeros(K, np.float64), np.zeros(K, np.float64), np.zeros(K, np.float64)
-        pairs = np.zeros((K, max(n - n_source, 0), max(n_source, 0), 4), np.float32) if want_pairs else None
-        check(_lib.lib().ecc_metric_evaluate_weighted_robust_transforms(self._h, n_source, K, C.c_void_p(flat.ctypes.data if K else 0),
-                                                                        int(loss), float(delta),
-                                                                        C.c_void_p(values.ctypes.data if K else 0),
-                                                                        C.c_void_p(coverages.ctypes.data if K else 0),
-                                                                        C.c_void_p(masses.ctypes.data if K else 0),
-                                                                        _ptr(pairs)))
-        return _with_pairs((values, coverages, masses), pairs, want_pairs)
+        return _transforms_call(_lib.lib().ecc_metric_evaluate_weighted_robust_transforms, self._h, self.getNumberOfProjetions(), n_source, flat,
+                                (int(loss), float(delta)), 3, 4, want_pairs)
 
     def last_batched_transforms(self):
         """Transforms of the last evaluate_transforms / evaluate_weighted_transforms / evaluate_robust_transforms /
         evaluate_weighted_robust_transforms call that went through the batch (0: the sequential way)."""
-        v = C.c_int64(0)
-        check(_lib.lib().ecc_metric_last_batched_transforms(self._h, C.byref(v)))
-        return v.value
+        return _last_count(_lib.lib().ecc_metric_last_batched_transforms, self._h)
 
     def evaluateForImagePair(self, i, j):
         """ref: evaluateForImagePair(i, j, redundant_samples0, redundant_samples1, kappas, radon_samples0,

@@ -215,6 +215,44 @@ inline ecc_ctx* default_context()
     }
     return ctx;
 }
+// What the members of the metrics share on their way to the C calls.
+/// (P0, P1, D0, D1) tuples, four ints each, as the C calls take them; who: the member's name, for its message.
+inline std::vector<int32_t> widenTuples(const char* who, const std::vector<int>& indices)
+{
+    if (indices.size() % 4) throw std::runtime_error(std::string(who) + ": four indices per tuple");
+    return std::vector<int32_t>(indices.begin(), indices.end());
+}
+/// Ps.size() x 12 doubles, every matrix column-major.
+inline std::vector<double> flattenProjections(const std::vector<Geometry::ProjectionMatrix>& Ps)
+{
+    std::vector<double> flat(12 * Ps.size());
+    for (size_t i = 0; i < Ps.size(); ++i)
+        for (int k = 0; k < 12; ++k) flat[12 * i + k] = Ps[i].data()[k];
+    return flat;
+}
+/// Ts.size() x 16 doubles, every transform column-major.
+inline std::vector<double> flattenTransforms(const std::vector<Geometry::RP3Homography>& Ts)
+{
+    std::vector<double> flat(16 * Ts.size());
+    for (size_t k = 0; k < Ts.size(); ++k)
+        for (int q = 0; q < 16; ++q) flat[16 * k + q] = Ts[k].data()[q];
+    return flat;
+}
+#ifdef ECC_ADAPTER_HAVE_EIGEN
+/// The reference's index tuples as 4 x indices.size() ints of type Int.
+template <typename Int>
+inline std::vector<Int> flattenTuples(const std::vector<Eigen::Vector4i>& indices)
+{
+    std::vector<Int> idx(4 * indices.size());
+    for (size_t i = 0; i < indices.size(); ++i)
+        for (int k = 0; k < 4; ++k) idx[4 * i + k] = indices[i][k];
+    return idx;
+}
+#endif
+/// An optional output sized and zeroed if the caller asked for it; pair_terms: `rows` pairs with `columns` floats each.
+template <typename T>
+inline void assignIfPresent(std::vector<T>* v, size_t n) { if (v) v->assign(n, T(0)); }
+inline void sizePairTerms(std::vector<float>* pair_terms, size_t rows, size_t columns) { assignIfPresent(pair_terms, rows * columns); }
 }  // namespace detail
 
 /// Not in the reference: ecc_radon_set_arithmetic of the default context -- RadonIntermediates computed afterwards use the
@@ -565,9 +603,7 @@ private:
 /// (join_pluecker of their source positions, ref: EpipolarConsistencyDirect.cpp:88-92).
 inline std::vector<double> estimateIsoCenter(const std::vector<ProjectionMatrix>& Ps)
 {
-    std::vector<double> flat(12 * Ps.size()), O(4, 0.0);
-    for (size_t i = 0; i < Ps.size(); ++i)
-        for (int k = 0; k < 12; ++k) flat[12 * i + k] = Ps[i].data()[k];
+    std::vector<double> flat = detail::flattenProjections(Ps), O(4, 0.0);
     ecc_host_iso_center(flat.data(), (int)Ps.size(), O.data());
     return O;
 }
@@ -645,14 +681,25 @@ class MetricRadonIntermediate : public Metric {
     ecc_group* m_group;
     size_t m_map_planes = 0;  // views the map held by the library has (robustMapWeights)
 
-    // the planes of a map call over k views, sized from the first intermediate
-    void sizeMapPlanes(size_t k, std::vector<float>* hits, std::vector<float>* rejected) const
+    // the planes of a map call over k views, sized from the first intermediate; returns k
+    size_t sizeMapPlanes(size_t k, std::vector<float>* hits, std::vector<float>* rejected) const
     {
         const size_t bins = dtrs.empty() ? 0 : (size_t)dtrs[0]->getRadonBinNumber(0) * (size_t)dtrs[0]->getRadonBinNumber(1);
-        if (hits) hits->assign(k * bins, 0.f);
-        if (rejected) rejected->assign(k * bins, 0.f);
+        detail::assignIfPresent(hits, k * bins);
+        detail::assignIfPresent(rejected, k * bins);
+        return k;
     }
     static float* dataOrNull(std::vector<float>* v) { return (v && !v->empty()) ? v->data() : 0x0; }
+    static double* dataOrNull(std::vector<double>* v) { return (v && !v->empty()) ? v->data() : 0x0; }
+    static const int32_t* dataOrNull(const std::vector<int32_t>& v) { return v.empty() ? 0x0 : v.data(); }
+    size_t allPairs() const { return Ps.size() * (Ps.size() > 0 ? Ps.size() - 1 : 0) / 2; }
+    // the map the library holds as intermediates the caller owns, from the handles a *_map_weights call filled in
+    std::vector<RadonIntermediate*> ownMapWeights(const std::vector<ecc_dtr*>& hs) const
+    {
+        std::vector<RadonIntermediate*> out;
+        for (size_t k = 0; k < m_map_planes; ++k) out.push_back(new RadonIntermediate(hs[k]));
+        return out;
+    }
 
     void push_params()
     {
@@ -682,9 +729,7 @@ class MetricRadonIntermediate : public Metric {
     void push_projections()
     {
         if ((!m_h && !m_gh) || Ps.empty()) return;
-        std::vector<double> flat(12 * Ps.size());
-        for (size_t i = 0; i < Ps.size(); ++i)
-            for (int k = 0; k < 12; ++k) flat[12 * i + k] = Ps[i].data()[k];
+        const std::vector<double> flat = detail::flattenProjections(Ps);
         if (m_gh) detail::check(ecc_group_metric_set_projections(m_gh, flat.data(), (int)Ps.size()));
         else detail::check(ecc_metric_set_projections(m_h, flat.data(), (int)Ps.size()));
     }
@@ -804,9 +849,7 @@ public:
     {
         if (m_gh) throw std::runtime_error("evaluateTransforms: not available on a device group");
         means.assign(Ts.size(), 0.0);
-        std::vector<double> flat(16 * Ts.size());
-        for (size_t k = 0; k < Ts.size(); ++k)
-            for (int q = 0; q < 16; ++q) flat[16 * k + q] = Ts[k].data()[q];
+        const std::vector<double> flat = detail::flattenTransforms(Ts);
         detail::check(ecc_metric_evaluate_transforms(m_h, n_source, (int)Ts.size(), flat.data(), means.data(), pair_values));
     }
     /// How many transforms of the last evaluateTransforms went through the batch (0: the sequential way).
@@ -829,12 +872,7 @@ public:
         if (m_gh) throw std::runtime_error("evaluateGradient: not available on a device group");
         if (h.empty() || plus.size() != h.size() || minus.size() != h.size())
             throw std::runtime_error("evaluateGradient: one plus matrix, one minus matrix and one step per parameter");
-        std::vector<double> fp(12 * h.size()), fm(12 * h.size());
-        for (size_t p = 0; p < h.size(); ++p)
-            for (int q = 0; q < 12; ++q) {
-                fp[12 * p + q] = plus[p].data()[q];
-                fm[12 * p + q] = minus[p].data()[q];
-            }
+        const std::vector<double> fp = detail::flattenProjections(plus), fm = detail::flattenProjections(minus);
         grad.assign(h.size(), 0.0);
         if (probes) probes->assign(2 * h.size(), 0.0);
         double value = 0.0;
@@ -898,10 +936,9 @@ public:
     double evaluateWeighted(double* coverage = 0x0, std::vector<float>* pair_terms = 0x0)
     {
         if (m_gh) throw std::runtime_error("evaluateWeighted: not available on a device group");
-        const size_t n = Ps.size();
-        if (pair_terms) pair_terms->assign(n * (n > 0 ? n - 1 : 0), 0.f);
+        detail::sizePairTerms(pair_terms, allPairs(), 2);
         double value = 0.0;
-        detail::check(ecc_metric_evaluate_weighted(m_h, &value, coverage, (pair_terms && !pair_terms->empty()) ? pair_terms->data() : 0x0));
+        detail::check(ecc_metric_evaluate_weighted(m_h, &value, coverage, dataOrNull(pair_terms)));
         return value;
     }
 
@@ -912,13 +949,11 @@ public:
     double evaluateWeightedPairs(const std::vector<int>& indices, double* coverage = 0x0, std::vector<float>* pair_terms = 0x0)
     {
         if (m_gh) throw std::runtime_error("evaluateWeightedPairs: not available on a device group");
-        if (indices.size() % 4) throw std::runtime_error("evaluateWeightedPairs: four indices per tuple");
-        const std::vector<int32_t> idx(indices.begin(), indices.end());
-        if (pair_terms) pair_terms->assign(idx.size() / 2, 0.f);
+        const std::vector<int32_t> idx = detail::widenTuples("evaluateWeightedPairs", indices);
+        detail::sizePairTerms(pair_terms, idx.size() / 4, 2);
         double value = 0.0;
         if (coverage) *coverage = 0.0;
-        detail::check(ecc_metric_evaluate_weighted_pairs(m_h, idx.empty() ? 0x0 : idx.data(), (int)(idx.size() / 4), &value, coverage,
-                                                         (pair_terms && !pair_terms->empty()) ? pair_terms->data() : 0x0));
+        detail::check(ecc_metric_evaluate_weighted_pairs(m_h, dataOrNull(idx), (int)(idx.size() / 4), &value, coverage, dataOrNull(pair_terms)));
         return value;
     }
 
@@ -931,11 +966,9 @@ public:
     double evaluateRobust(int loss, float delta, double* inlier_mass = 0x0, std::vector<float>* pair_terms = 0x0)
     {
         if (m_gh) throw std::runtime_error("evaluateRobust: not available on a device group");
-        const size_t n = Ps.size();
-        if (pair_terms) pair_terms->assign(3 * (n * (n > 0 ? n - 1 : 0) / 2), 0.f);
+        detail::sizePairTerms(pair_terms, allPairs(), 3);
         double value = 0.0;
-        detail::check(ecc_metric_evaluate_robust(m_h, loss, delta, &value, inlier_mass,
-                                                 (pair_terms && !pair_terms->empty()) ? pair_terms->data() : 0x0));
+        detail::check(ecc_metric_evaluate_robust(m_h, loss, delta, &value, inlier_mass, dataOrNull(pair_terms)));
         return value;
     }
 
@@ -947,22 +980,19 @@ public:
                                std::vector<float>* pair_terms = 0x0)
     {
         if (m_gh) throw std::runtime_error("evaluateRobustPairs: not available on a device group");
-        if (indices.size() % 4) throw std::runtime_error("evaluateRobustPairs: four indices per tuple");
-        const std::vector<int32_t> idx(indices.begin(), indices.end());
-        if (pair_terms) pair_terms->assign(3 * (idx.size() / 4), 0.f);
+        const std::vector<int32_t> idx = detail::widenTuples("evaluateRobustPairs", indices);
+        detail::sizePairTerms(pair_terms, idx.size() / 4, 3);
         double value = 0.0;
         if (inlier_mass) *inlier_mass = 0.0;
-        detail::check(ecc_metric_evaluate_robust_pairs(m_h, idx.empty() ? 0x0 : idx.data(), (int)(idx.size() / 4), loss, delta, &value,
-                                                       inlier_mass, (pair_terms && !pair_terms->empty()) ? pair_terms->data() : 0x0));
+        detail::check(ecc_metric_evaluate_robust_pairs(m_h, dataOrNull(idx), (int)(idx.size() / 4), loss, delta, &value, inlier_mass,
+                                                       dataOrNull(pair_terms)));
         return value;
     }
 #ifdef ECC_ADAPTER_HAVE_EIGEN
     double evaluateRobustPairs(const std::vector<Eigen::Vector4i>& indices, int loss, float delta, double* inlier_mass = 0x0,
                                std::vector<float>* pair_terms = 0x0)
     {
-        std::vector<int> idx(4 * indices.size());
-        for (size_t i = 0; i < indices.size(); ++i)
-            for (int k = 0; k < 4; ++k) idx[4 * i + k] = indices[i][k];
+        const std::vector<int> idx = detail::flattenTuples<int>(indices);
         return evaluateRobustPairs(idx, loss, delta, inlier_mass, pair_terms);
     }
 #endif
@@ -976,14 +1006,13 @@ public:
                              double* inlier_mass = 0x0, std::vector<float>* pair_terms = 0x0)
     {
         if (m_gh) throw std::runtime_error("evaluateRobustMap: not available on a device group");
-        const size_t n = Ps.size();
-        if (pair_terms) pair_terms->assign(3 * (n * (n > 0 ? n - 1 : 0) / 2), 0.f);
+        detail::sizePairTerms(pair_terms, allPairs(), 3);
         const std::vector<int32_t> v(views.begin(), views.end());
-        sizeMapPlanes(v.empty() ? n : v.size(), hits, rejected);
+        const size_t planes = sizeMapPlanes(v.empty() ? Ps.size() : v.size(), hits, rejected);
         double value = 0.0;
-        detail::check(ecc_metric_evaluate_robust_map(m_h, loss, delta, v.empty() ? 0x0 : v.data(), (int)v.size(), dataOrNull(hits),
-                                                     dataOrNull(rejected), &value, inlier_mass, dataOrNull(pair_terms)));
-        m_map_planes = v.empty() ? n : v.size();
+        detail::check(ecc_metric_evaluate_robust_map(m_h, loss, delta, dataOrNull(v), (int)v.size(), dataOrNull(hits), dataOrNull(rejected),
+                                                     &value, inlier_mass, dataOrNull(pair_terms)));
+        m_map_planes = planes;
         return value;
     }
 
@@ -994,17 +1023,15 @@ public:
                                   std::vector<float>* pair_terms = 0x0)
     {
         if (m_gh) throw std::runtime_error("evaluateRobustMapPairs: not available on a device group");
-        if (indices.size() % 4) throw std::runtime_error("evaluateRobustMapPairs: four indices per tuple");
-        const std::vector<int32_t> idx(indices.begin(), indices.end());
-        if (pair_terms) pair_terms->assign(3 * (idx.size() / 4), 0.f);
+        const std::vector<int32_t> idx = detail::widenTuples("evaluateRobustMapPairs", indices);
+        detail::sizePairTerms(pair_terms, idx.size() / 4, 3);
         const std::vector<int32_t> v(views.begin(), views.end());
-        sizeMapPlanes(v.empty() ? dtrs.size() : v.size(), hits, rejected);
+        const size_t planes = sizeMapPlanes(v.empty() ? dtrs.size() : v.size(), hits, rejected);
         double value = 0.0;
         if (inlier_mass) *inlier_mass = 0.0;
-        detail::check(ecc_metric_evaluate_robust_map_pairs(m_h, idx.empty() ? 0x0 : idx.data(), (int)(idx.size() / 4), loss, delta,
-                                                           v.empty() ? 0x0 : v.data(), (int)v.size(), dataOrNull(hits), dataOrNull(rejected),
-                                                           &value, inlier_mass, dataOrNull(pair_terms)));
-        m_map_planes = idx.empty() ? 0 : (v.empty() ? dtrs.size() : v.size());
+        detail::check(ecc_metric_evaluate_robust_map_pairs(m_h, dataOrNull(idx), (int)(idx.size() / 4), loss, delta, dataOrNull(v), (int)v.size(),
+                                                           dataOrNull(hits), dataOrNull(rejected), &value, inlier_mass, dataOrNull(pair_terms)));
+        m_map_planes = idx.empty() ? 0 : planes;
         return value;
     }
 
@@ -1017,9 +1044,7 @@ public:
         if (m_gh) throw std::runtime_error("robustMapWeights: not available on a device group");
         std::vector<ecc_dtr*> hs(m_map_planes ? m_map_planes : 1, (ecc_dtr*)0x0);
         detail::check(ecc_metric_robust_map_weights(m_h, min_hits, gain, hs.data()));
-        std::vector<RadonIntermediate*> out;
-        for (size_t k = 0; k < m_map_planes; ++k) out.push_back(new RadonIntermediate(hs[k]));
-        return out;
+        return ownMapWeights(hs);
     }
 
     /// ecc_host_robust_scale: a scale delta for evaluateRobust from the rows {c, u, r} of an earlier call (normally the one with
@@ -1040,11 +1065,9 @@ public:
                                   std::vector<float>* pair_terms = 0x0)
     {
         if (m_gh) throw std::runtime_error("evaluateWeightedRobust: not available on a device group");
-        const size_t n = Ps.size();
-        if (pair_terms) pair_terms->assign(4 * (n * (n > 0 ? n - 1 : 0) / 2), 0.f);
+        detail::sizePairTerms(pair_terms, allPairs(), 4);
         double value = 0.0;
-        detail::check(ecc_metric_evaluate_weighted_robust(m_h, loss, delta, &value, coverage, inlier_mass,
-                                                          (pair_terms && !pair_terms->empty()) ? pair_terms->data() : 0x0));
+        detail::check(ecc_metric_evaluate_weighted_robust(m_h, loss, delta, &value, coverage, inlier_mass, dataOrNull(pair_terms)));
         return value;
     }
 
@@ -1056,24 +1079,20 @@ public:
                                        double* inlier_mass = 0x0, std::vector<float>* pair_terms = 0x0)
     {
         if (m_gh) throw std::runtime_error("evaluateWeightedRobustPairs: not available on a device group");
-        if (indices.size() % 4) throw std::runtime_error("evaluateWeightedRobustPairs: four indices per tuple");
-        const std::vector<int32_t> idx(indices.begin(), indices.end());
-        if (pair_terms) pair_terms->assign(idx.size(), 0.f);
+        const std::vector<int32_t> idx = detail::widenTuples("evaluateWeightedRobustPairs", indices);
+        detail::sizePairTerms(pair_terms, idx.size() / 4, 4);
         double value = 0.0;
         if (coverage) *coverage = 0.0;
         if (inlier_mass) *inlier_mass = 0.0;
-        detail::check(ecc_metric_evaluate_weighted_robust_pairs(m_h, idx.empty() ? 0x0 : idx.data(), (int)(idx.size() / 4), loss, delta,
-                                                                &value, coverage, inlier_mass,
-                                                                (pair_terms && !pair_terms->empty()) ? pair_terms->data() : 0x0));
+        detail::check(ecc_metric_evaluate_weighted_robust_pairs(m_h, dataOrNull(idx), (int)(idx.size() / 4), loss, delta, &value, coverage,
+                                                                inlier_mass, dataOrNull(pair_terms)));
         return value;
     }
 #ifdef ECC_ADAPTER_HAVE_EIGEN
     double evaluateWeightedRobustPairs(const std::vector<Eigen::Vector4i>& indices, int loss, float delta, double* coverage = 0x0,
                                        double* inlier_mass = 0x0, std::vector<float>* pair_terms = 0x0)
     {
-        std::vector<int> idx(4 * indices.size());
-        for (size_t i = 0; i < indices.size(); ++i)
-            for (int k = 0; k < 4; ++k) idx[4 * i + k] = indices[i][k];
+        const std::vector<int> idx = detail::flattenTuples<int>(indices);
         return evaluateWeightedRobustPairs(idx, loss, delta, coverage, inlier_mass, pair_terms);
     }
 #endif
@@ -1097,14 +1116,13 @@ public:
                                      std::vector<float>* pair_terms = 0x0)
     {
         if (m_gh) throw std::runtime_error("evaluateWeightedRobustMap: not available on a device group");
-        const size_t n = Ps.size();
-        if (pair_terms) pair_terms->assign(4 * (n * (n > 0 ? n - 1 : 0) / 2), 0.f);
+        detail::sizePairTerms(pair_terms, allPairs(), 4);
         const std::vector<int32_t> v(views.begin(), views.end());
-        sizeMapPlanes(v.empty() ? n : v.size(), hits, rejected);
+        const size_t planes = sizeMapPlanes(v.empty() ? Ps.size() : v.size(), hits, rejected);
         double value = 0.0;
-        detail::check(ecc_metric_evaluate_weighted_robust_map(m_h, loss, delta, v.empty() ? 0x0 : v.data(), (int)v.size(), dataOrNull(hits),
+        detail::check(ecc_metric_evaluate_weighted_robust_map(m_h, loss, delta, dataOrNull(v), (int)v.size(), dataOrNull(hits),
                                                               dataOrNull(rejected), &value, coverage, inlier_mass, dataOrNull(pair_terms)));
-        m_map_planes = v.empty() ? n : v.size();
+        m_map_planes = planes;
         return value;
     }
 
@@ -1116,18 +1134,17 @@ public:
                                           double* inlier_mass = 0x0, std::vector<float>* pair_terms = 0x0)
     {
         if (m_gh) throw std::runtime_error("evaluateWeightedRobustMapPairs: not available on a device group");
-        if (indices.size() % 4) throw std::runtime_error("evaluateWeightedRobustMapPairs: four indices per tuple");
-        const std::vector<int32_t> idx(indices.begin(), indices.end());
-        if (pair_terms) pair_terms->assign(4 * (idx.size() / 4), 0.f);
+        const std::vector<int32_t> idx = detail::widenTuples("evaluateWeightedRobustMapPairs", indices);
+        detail::sizePairTerms(pair_terms, idx.size() / 4, 4);
         const std::vector<int32_t> v(views.begin(), views.end());
-        sizeMapPlanes(v.empty() ? Ps.size() : v.size(), hits, rejected);
+        const size_t planes = sizeMapPlanes(v.empty() ? Ps.size() : v.size(), hits, rejected);
         double value = 0.0;
         if (coverage) *coverage = 0.0;
         if (inlier_mass) *inlier_mass = 0.0;
-        detail::check(ecc_metric_evaluate_weighted_robust_map_pairs(m_h, idx.empty() ? 0x0 : idx.data(), (int)(idx.size() / 4), loss, delta,
-                                                                    v.empty() ? 0x0 : v.data(), (int)v.size(), dataOrNull(hits),
-                                                                    dataOrNull(rejected), &value, coverage, inlier_mass, dataOrNull(pair_terms)));
-        m_map_planes = idx.empty() ? 0 : (v.empty() ? Ps.size() : v.size());
+        detail::check(ecc_metric_evaluate_weighted_robust_map_pairs(m_h, dataOrNull(idx), (int)(idx.size() / 4), loss, delta, dataOrNull(v),
+                                                                    (int)v.size(), dataOrNull(hits), dataOrNull(rejected), &value, coverage,
+                                                                    inlier_mass, dataOrNull(pair_terms)));
+        m_map_planes = idx.empty() ? 0 : planes;
         return value;
     }
 
@@ -1139,9 +1156,7 @@ public:
         if (m_gh) throw std::runtime_error("weightedRobustMapWeights: not available on a device group");
         std::vector<ecc_dtr*> hs(m_map_planes ? m_map_planes : 1, (ecc_dtr*)0x0);
         detail::check(ecc_metric_weighted_robust_map_weights(m_h, min_hits, gain, hs.data()));
-        std::vector<RadonIntermediate*> out;
-        for (size_t k = 0; k < m_map_planes; ++k) out.push_back(new RadonIntermediate(hs[k]));
-        return out;
+        return ownMapWeights(hs);
     }
 
     /// Not in the reference: ecc_metric_evaluate_weighted_pose_deltas -- evaluatePoseDeltas for the metric with per-line weights
@@ -1154,11 +1169,11 @@ public:
         if (m_gh) throw std::runtime_error("evaluateWeightedPoseDeltas: not available on a device group");
         if (moved_views.size() != moved_Ps.size()) throw std::runtime_error("evaluateWeightedPoseDeltas: one matrix list per pose");
         values.assign(moved_views.size(), 0.0);
-        if (coverages) coverages->assign(moved_views.size(), 0.0);
+        detail::assignIfPresent(coverages, moved_views.size());
         if (moved_views.empty()) return;
         const PackedPoseLists l("evaluateWeightedPoseDeltas", moved_views, moved_Ps);
         detail::check(ecc_metric_evaluate_weighted_pose_deltas(m_h, (int)moved_views.size(), l.off.data(), l.views_or_null(), l.Ps_or_null(),
-                                                               values.data(), coverages ? coverages->data() : 0x0));
+                                                               values.data(), dataOrNull(coverages)));
     }
 
     /// Not in the reference: ecc_metric_evaluate_weighted_transforms -- evaluateTransforms for the metric with per-line weights
@@ -1172,12 +1187,10 @@ public:
     {
         if (m_gh) throw std::runtime_error("evaluateWeightedTransforms: not available on a device group");
         values.assign(Ts.size(), 0.0);
-        if (coverages) coverages->assign(Ts.size(), 0.0);
-        std::vector<double> flat(16 * Ts.size());
-        for (size_t k = 0; k < Ts.size(); ++k)
-            for (int q = 0; q < 16; ++q) flat[16 * k + q] = Ts[k].data()[q];
-        detail::check(ecc_metric_evaluate_weighted_transforms(m_h, n_source, (int)Ts.size(), flat.data(), values.data(),
-                                                              coverages ? coverages->data() : 0x0, pair_terms));
+        detail::assignIfPresent(coverages, Ts.size());
+        const std::vector<double> flat = detail::flattenTransforms(Ts);
+        detail::check(ecc_metric_evaluate_weighted_transforms(m_h, n_source, (int)Ts.size(), flat.data(), values.data(), dataOrNull(coverages),
+                                                              pair_terms));
     }
 
     /// Not in the reference: ecc_metric_evaluate_variance -- the metric with inverse-variance sample weights.  The Radon
@@ -1189,10 +1202,9 @@ public:
     double evaluateVariance(float floor, double* mean_weight = 0x0, std::vector<float>* pair_terms = 0x0)
     {
         if (m_gh) throw std::runtime_error("evaluateVariance: not available on a device group");
-        const size_t n = Ps.size();
-        if (pair_terms) pair_terms->assign(n * (n > 0 ? n - 1 : 0), 0.f);
+        detail::sizePairTerms(pair_terms, allPairs(), 2);
         double value = 0.0;
-        detail::check(ecc_metric_evaluate_variance(m_h, floor, &value, mean_weight, (pair_terms && !pair_terms->empty()) ? pair_terms->data() : 0x0));
+        detail::check(ecc_metric_evaluate_variance(m_h, floor, &value, mean_weight, dataOrNull(pair_terms)));
         return value;
     }
 
@@ -1203,13 +1215,12 @@ public:
     double evaluateVariancePairs(const std::vector<int>& indices, float floor, double* mean_weight = 0x0, std::vector<float>* pair_terms = 0x0)
     {
         if (m_gh) throw std::runtime_error("evaluateVariancePairs: not available on a device group");
-        if (indices.size() % 4) throw std::runtime_error("evaluateVariancePairs: four indices per tuple");
-        const std::vector<int32_t> idx(indices.begin(), indices.end());
-        if (pair_terms) pair_terms->assign(idx.size() / 2, 0.f);
+        const std::vector<int32_t> idx = detail::widenTuples("evaluateVariancePairs", indices);
+        detail::sizePairTerms(pair_terms, idx.size() / 4, 2);
         double value = 0.0;
         if (mean_weight) *mean_weight = 0.0;
-        detail::check(ecc_metric_evaluate_variance_pairs(m_h, idx.empty() ? 0x0 : idx.data(), (int)(idx.size() / 4), floor, &value, mean_weight,
-                                                         (pair_terms && !pair_terms->empty()) ? pair_terms->data() : 0x0));
+        detail::check(ecc_metric_evaluate_variance_pairs(m_h, dataOrNull(idx), (int)(idx.size() / 4), floor, &value, mean_weight,
+                                                         dataOrNull(pair_terms)));
         return value;
     }
 
@@ -1224,11 +1235,11 @@ public:
         if (m_gh) throw std::runtime_error("evaluateVariancePoseDeltas: not available on a device group");
         if (moved_views.size() != moved_Ps.size()) throw std::runtime_error("evaluateVariancePoseDeltas: one matrix list per pose");
         values.assign(moved_views.size(), 0.0);
-        if (mean_weights) mean_weights->assign(moved_views.size(), 0.0);
+        detail::assignIfPresent(mean_weights, moved_views.size());
         if (moved_views.empty()) return;
         const PackedPoseLists l("evaluateVariancePoseDeltas", moved_views, moved_Ps);
         detail::check(ecc_metric_evaluate_variance_pose_deltas(m_h, (int)moved_views.size(), l.off.data(), l.views_or_null(), l.Ps_or_null(),
-                                                               floor, values.data(), mean_weights ? mean_weights->data() : 0x0));
+                                                               floor, values.data(), dataOrNull(mean_weights)));
     }
 
     /// Not in the reference: ecc_metric_evaluate_variance_transforms -- evaluateTransforms for the metric with inverse-variance
@@ -1242,12 +1253,10 @@ public:
     {
         if (m_gh) throw std::runtime_error("evaluateVarianceTransforms: not available on a device group");
         values.assign(Ts.size(), 0.0);
-        if (mean_weights) mean_weights->assign(Ts.size(), 0.0);
-        std::vector<double> flat(16 * Ts.size());
-        for (size_t k = 0; k < Ts.size(); ++k)
-            for (int q = 0; q < 16; ++q) flat[16 * k + q] = Ts[k].data()[q];
+        detail::assignIfPresent(mean_weights, Ts.size());
+        const std::vector<double> flat = detail::flattenTransforms(Ts);
         detail::check(ecc_metric_evaluate_variance_transforms(m_h, n_source, (int)Ts.size(), flat.data(), floor, values.data(),
-                                                              mean_weights ? mean_weights->data() : 0x0, pair_terms));
+                                                              dataOrNull(mean_weights), pair_terms));
     }
 
     /// ecc_host_variance_floor: a floor for evaluateVariance from the variance fields themselves -- fraction x the median of their
@@ -1270,11 +1279,11 @@ public:
         if (m_gh) throw std::runtime_error("evaluateRobustPoseDeltas: not available on a device group");
         if (moved_views.size() != moved_Ps.size()) throw std::runtime_error("evaluateRobustPoseDeltas: one matrix list per pose");
         values.assign(moved_views.size(), 0.0);
-        if (inlier_masses) inlier_masses->assign(moved_views.size(), 0.0);
+        detail::assignIfPresent(inlier_masses, moved_views.size());
         if (moved_views.empty()) return;
         const PackedPoseLists l("evaluateRobustPoseDeltas", moved_views, moved_Ps);
         detail::check(ecc_metric_evaluate_robust_pose_deltas(m_h, (int)moved_views.size(), l.off.data(), l.views_or_null(), l.Ps_or_null(), loss,
-                                                             delta, values.data(), inlier_masses ? inlier_masses->data() : 0x0));
+                                                             delta, values.data(), dataOrNull(inlier_masses)));
     }
 
     /// Not in the reference: ecc_metric_evaluate_robust_transforms -- evaluateTransforms under the per-sample robust loss of
@@ -1288,12 +1297,10 @@ public:
     {
         if (m_gh) throw std::runtime_error("evaluateRobustTransforms: not available on a device group");
         values.assign(Ts.size(), 0.0);
-        if (inlier_masses) inlier_masses->assign(Ts.size(), 0.0);
-        std::vector<double> flat(16 * Ts.size());
-        for (size_t k = 0; k < Ts.size(); ++k)
-            for (int q = 0; q < 16; ++q) flat[16 * k + q] = Ts[k].data()[q];
+        detail::assignIfPresent(inlier_masses, Ts.size());
+        const std::vector<double> flat = detail::flattenTransforms(Ts);
         detail::check(ecc_metric_evaluate_robust_transforms(m_h, n_source, (int)Ts.size(), flat.data(), loss, delta, values.data(),
-                                                            inlier_masses ? inlier_masses->data() : 0x0, pair_terms));
+                                                            dataOrNull(inlier_masses), pair_terms));
     }
 
     /// Not in the reference: ecc_metric_evaluate_weighted_robust_pose_deltas -- evaluatePoseDeltas under line weights AND the robust loss
@@ -1308,13 +1315,12 @@ public:
         if (m_gh) throw std::runtime_error("evaluateWeightedRobustPoseDeltas: not available on a device group");
         if (moved_views.size() != moved_Ps.size()) throw std::runtime_error("evaluateWeightedRobustPoseDeltas: one matrix list per pose");
         values.assign(moved_views.size(), 0.0);
-        if (coverages) coverages->assign(moved_views.size(), 0.0);
-        if (inlier_masses) inlier_masses->assign(moved_views.size(), 0.0);
+        detail::assignIfPresent(coverages, moved_views.size());
+        detail::assignIfPresent(inlier_masses, moved_views.size());
         if (moved_views.empty()) return;
         const PackedPoseLists l("evaluateWeightedRobustPoseDeltas", moved_views, moved_Ps);
         detail::check(ecc_metric_evaluate_weighted_robust_pose_deltas(m_h, (int)moved_views.size(), l.off.data(), l.views_or_null(), l.Ps_or_null(),
-                                                                      loss, delta, values.data(), coverages ? coverages->data() : 0x0,
-                                                                      inlier_masses ? inlier_masses->data() : 0x0));
+                                                                      loss, delta, values.data(), dataOrNull(coverages), dataOrNull(inlier_masses)));
     }
 
     /// Not in the reference: ecc_metric_evaluate_weighted_robust_transforms -- evaluateTransforms under line weights AND the robust
@@ -1329,14 +1335,11 @@ public:
     {
         if (m_gh) throw std::runtime_error("evaluateWeightedRobustTransforms: not available on a device group");
         values.assign(Ts.size(), 0.0);
-        if (coverages) coverages->assign(Ts.size(), 0.0);
-        if (inlier_masses) inlier_masses->assign(Ts.size(), 0.0);
-        std::vector<double> flat(16 * Ts.size());
-        for (size_t k = 0; k < Ts.size(); ++k)
-            for (int q = 0; q < 16; ++q) flat[16 * k + q] = Ts[k].data()[q];
+        detail::assignIfPresent(coverages, Ts.size());
+        detail::assignIfPresent(inlier_masses, Ts.size());
+        const std::vector<double> flat = detail::flattenTransforms(Ts);
         detail::check(ecc_metric_evaluate_weighted_robust_transforms(m_h, n_source, (int)Ts.size(), flat.data(), loss, delta, values.data(),
-                                                                     coverages ? coverages->data() : 0x0,
-                                                                     inlier_masses ? inlier_masses->data() : 0x0, pair_terms));
+                                                                     dataOrNull(coverages), dataOrNull(inlier_masses), pair_terms));
     }
 
     /// Not in the reference: ecc_metric_evaluate_view_hessian -- the quadratic form of the per-view channel coefficients as a matrix:
@@ -1435,9 +1438,7 @@ public:
     /// ref: evaluate(const std::vector<Eigen::Vector4i>& indices, float* out): (P0, P1, dtr0, dtr1) tuples.
     double evaluate(const std::vector<Eigen::Vector4i>& _indices, float* _out)
     {
-        std::vector<int32_t> idx(4 * _indices.size());
-        for (size_t i = 0; i < _indices.size(); ++i)
-            for (int k = 0; k < 4; ++k) idx[4 * i + k] = _indices[i][k];
+        const std::vector<int32_t> idx = detail::flattenTuples<int32_t>(_indices);
         return evaluate_indices(idx.data(), (int)_indices.size(), _out);
     }
 #endif
@@ -1507,9 +1508,7 @@ public:
     {
         Metric::setProjectionMatrices(_Ps);
         if (Ps.empty()) return *this;
-        std::vector<double> flat(12 * Ps.size());
-        for (size_t i = 0; i < Ps.size(); ++i)
-            for (int k = 0; k < 12; ++k) flat[12 * i + k] = Ps[i].data()[k];
+        const std::vector<double> flat = detail::flattenProjections(Ps);
         detail::check(ecc_direct_set_projections(m_h, flat.data(), (int)Ps.size()));
         return *this;
     }
@@ -1552,9 +1551,7 @@ public:
 #ifdef ECC_ADAPTER_HAVE_EIGEN
     double evaluate(const std::vector<Eigen::Vector4i>& _indices, float* _out = 0x0)
     {
-        std::vector<int32_t> idx(4 * _indices.size());
-        for (size_t i = 0; i < _indices.size(); ++i)
-            for (int k = 0; k < 4; ++k) idx[4 * i + k] = _indices[i][k];
+        const std::vector<int32_t> idx = detail::flattenTuples<int32_t>(_indices);
         return evaluate_indices(idx.data(), (int)_indices.size(), _out);
     }
 #endif
