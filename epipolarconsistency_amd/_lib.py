@@ -105,6 +105,11 @@ SIGNATURES = {
     "ecc_metric_evaluate_variance_pose_deltas": (_i, [_vp, _i, _vp, _vp, _vp, C.c_float, _vp, _vp]),
     "ecc_metric_evaluate_variance_transforms": (_i, [_vp, _i, _i, _vp, C.c_float, _vp, _vp, _vp]),
     "ecc_host_variance_floor": (_i, [_vp, _i64, _d, _vp]),
+    "ecc_metric_evaluate_variance_robust": (_i, [_vp, _i, C.c_float, C.c_float, _pd, _pd, _pd, _vp]),
+    "ecc_metric_evaluate_variance_robust_pairs": (_i, [_vp, _vp, _i, _i, C.c_float, C.c_float, _pd, _pd, _pd, _vp]),
+    "ecc_metric_evaluate_variance_robust_pose_deltas": (_i, [_vp, _i, _vp, _vp, _vp, _i, C.c_float, C.c_float, _vp, _vp, _vp]),
+    "ecc_metric_evaluate_variance_robust_transforms": (_i, [_vp, _i, _i, _vp, _i, C.c_float, C.c_float, _vp, _vp, _vp, _vp]),
+    "ecc_host_variance_robust_scale": (_d, [_vp, _i64, _d]),
     "ecc_metric_evaluate_robust": (_i, [_vp, _i, C.c_float, _pd, _pd, _vp]),
     "ecc_metric_evaluate_robust_pairs": (_i, [_vp, _vp, _i, _i, C.c_float, _pd, _pd, _vp]),
     "ecc_host_robust_scale": (_d, [_vp, _i64, _d]),

@@ -821,6 +821,29 @@ class MetricRadonIntermediate:
         return _pose_lists_call(_lib.lib().ecc_metric_evaluate_variance_pose_deltas, self._h, moved_offsets, moved_views, moved_Ps,
                                 (float(floor),), 2)
 
+    def evaluate_variance_robust_pairs(self, idx4, loss, delta, floor, want_pairs=False):
+        """ecc_metric_evaluate_variance_robust_pairs: evaluate_variance_robust over an index list of (P0, P1, D0, D1) tuples as
+        evaluate_variance_pairs takes them: D0, D1 index the data intermediates, in [0, n_views), and the variance follows the data
+        index.  Returns (value, mean_weight, inlier_mass) over the list -- with want_pairs also pairs (n_pairs, 4) float32 rows
+        {c, u, k, r} in list order.  The sampling mode resolves from the list's length; an empty list writes nothing
+        (0.0, 0.0, 0.0)."""
+        idx = _idx4_list(idx4)
+        return _scalar_form_call(_lib.lib().ecc_metric_evaluate_variance_robust_pairs, self._h, (_ptr(idx), len(idx)),
+                                 (int(loss), float(delta), float(floor)), 3, len(idx), 4, want_pairs)
+
+    def evaluate_variance_robust_pose_deltas(self, moved_views, moved_Ps, loss, delta, floor):
+        """ecc_metric_evaluate_variance_robust_pose_deltas: evaluate_pose_deltas under inverse-variance weights and the robust loss
+        of the studentised residual (evaluate_variance_robust: the metric holds the data of every view, then its variance field;
+        loss, delta, floor as there).  The same lists; returns (values, mean_weights, inlier_masses), every entry bit-identical to
+        setProjectionMatrices + evaluate_variance_robust(loss, delta, floor) of that pose; the current matrices stay."""
+        return self.evaluate_variance_robust_pose_deltas_packed(*_pack_pose_lists(moved_views, moved_Ps), loss, delta, floor)
+
+    def evaluate_variance_robust_pose_deltas_packed(self, moved_offsets, moved_views, moved_Ps, loss, delta, floor):
+        """The C signature itself, with the arguments of evaluate_pose_deltas_packed, then loss, delta and the floor; returns
+        (values, mean_weights, inlier_masses)."""
+        return _pose_lists_call(_lib.lib().ecc_metric_evaluate_variance_robust_pose_deltas, self._h, moved_offsets, moved_views, moved_Ps,
+                                (int(loss), float(delta), float(floor)), 3)
+
     def setPoseBatching(self, on=True):
         """ecc_metric_set_pose_batching: off = evaluate_poses runs every pose as its own stream-ordered evaluation."""
         check(_lib.lib().ecc_metric_set_pose_batching(self._h, 1 if on else 0))
@@ -1090,6 +1113,21 @@ class MetricRadonIntermediate:
         return _scalar_form_call(_lib.lib().ecc_metric_evaluate_weighted_robust_pairs, self._h, (_ptr(idx), len(idx)), (int(loss), float(delta)),
                                  3, len(idx), 4, want_pairs)
 
+    def evaluate_variance_robust(self, loss, delta, floor, want_pairs=False):
+        """ecc_metric_evaluate_variance_robust: inverse-variance weights and the robust loss together, the loss in sigma units --
+        for scans with lines whose noise is known (variance_intermediates) and an instrument nobody flagged.  The metric holds
+        2 * n_views Radon intermediates as for evaluate_variance; loss as for evaluate_robust; floor as for evaluate_variance.  Per
+        sample f = omega * w(|d| / sigma): omega = 1 / max(V_i + V_j, floor), sigma its root, w the IRLS weight of the STUDENTISED
+        residual, so delta counts sigmas and a line that is merely noisy, and known to be, is not rejected for it.  Returns (value,
+        mean_weight, inlier_mass): value = sum c / sum u (never divided by the mass the loss keeps), mean_weight = sum u / n_pairs,
+        inlier_mass = sum k / sum u -- with want_pairs (value, mean_weight, inlier_mass, pairs), pairs (n_pairs, 4) float32 in the
+        pair order of evaluate(cost): per pair c, its value, u, its mean weight, k, the weight mass the loss keeps, and r, the mean
+        squared studentised residual (variance_robust_scale takes delta from r: V is a variance only up to a constant factor).
+        delta = inf: the bits of evaluate_variance; V = 0.5 everywhere and floor <= 1: the bits of evaluate_robust.  The current
+        matrices and everything the metric keeps stay."""
+        return _scalar_form_call(_lib.lib().ecc_metric_evaluate_variance_robust, self._h, (), (int(loss), float(delta), float(floor)), 3,
+                                 _n_all_pairs(self._Ps), 4, want_pairs)
+
     def evaluate_transforms(self, n_source, Ts, want_pairs=False):
         """ecc_metric_evaluate_transforms: the registration of two scans (ref: tools/Registration/Registration3D3D.hxx).  The
         current matrices are the base, views [0, n_source) the source scan, the rest the target scan; Ts: anything np.asarray
@@ -1145,6 +1183,18 @@ class MetricRadonIntermediate:
         flat = _transforms_colmajor(Ts)
         return _transforms_call(_lib.lib().ecc_metric_evaluate_weighted_robust_transforms, self._h, self.getNumberOfProjetions(), n_source, flat,
                                 (int(loss), float(delta)), 3, 4, want_pairs)
+
+    def evaluate_variance_robust_transforms(self, n_source, Ts, loss, delta, floor, want_pairs=False):
+        """ecc_metric_evaluate_variance_robust_transforms: evaluate_transforms under inverse-variance weights and the robust loss of
+        the studentised residual (evaluate_variance_robust: 2 * n_views intermediates; loss, delta, floor as there; the variance
+        follows the data, not the transformed matrix).  n_source and Ts as for evaluate_transforms.  Returns (values, mean_weights,
+        inlier_masses) = per transform (sum c / sum u, sum u / (n_source n_target), sum k / sum u) over the cross pairs -- with
+        want_pairs also pairs (K, n_target, n_source, 4) float32 rows {c, u, k, r}: every number bit-identical to
+        setProjectionMatrices(composed) + evaluate_variance_robust_pairs(the cross list, loss, delta, floor) per transform; the
+        current matrices stay."""
+        flat = _transforms_colmajor(Ts)
+        return _transforms_call(_lib.lib().ecc_metric_evaluate_variance_robust_transforms, self._h, self.getNumberOfProjetions(), n_source, flat,
+                                (int(loss), float(delta), float(floor)), 3, 4, want_pairs)
 
     def last_batched_transforms(self):
         """Transforms of the last evaluate_transforms / evaluate_weighted_transforms / evaluate_robust_transforms /
@@ -1833,6 +1883,16 @@ def weighted_robust_scale(pair_terms, k=1.0):
     if rows.ndim != 2 or rows.shape[1] != 4:
         raise ValueError("pair_terms must be (n_pairs, 4) rows {c, u, k, r}")
     return float(_lib.lib().ecc_host_weighted_robust_scale(C.c_void_p(rows.ctypes.data) if len(rows) else None, len(rows), float(k)))
+
+
+def variance_robust_scale(pair_terms, k=1.0):
+    """ecc_host_variance_robust_scale: a scale delta for evaluate_variance_robust from the pair rows {c, u, k, r} of an earlier call
+    (normally the one with delta = inf) -- k x the median over the pairs with r > 0 of sqrt(r), the pair's rms studentised residual;
+    0.0 without such a pair.  V is the line variance only up to a constant factor, so this is what one sigma measures on the data."""
+    rows = np.ascontiguousarray(pair_terms, np.float32)
+    if rows.ndim != 2 or rows.shape[1] != 4:
+        raise ValueError("pair_terms must be (n_pairs, 4) rows {c, u, k, r}")
+    return float(_lib.lib().ecc_host_variance_robust_scale(C.c_void_p(rows.ctypes.data) if len(rows) else None, len(rows), float(k)))
 
 
 def refine_line_weights(ctx, Ps, data, weights=None, loss=_lib.LOSS_TRUNCATED, k=0.5, passes=2, min_hits=1.0, gain=1.0, sampling="auto"):

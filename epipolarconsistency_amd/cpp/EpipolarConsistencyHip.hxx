@@ -1268,6 +1268,98 @@ public:
         return out;
     }
 
+    /// Not in the reference: ecc_metric_evaluate_variance_robust -- inverse-variance weights and the robust loss together, the loss
+    /// in sigma units: for scans with lines whose noise is known and an instrument nobody flagged.  Intermediates and floor as for
+    /// evaluateVariance (2 * n_views: data, then variance fields), loss as for evaluateRobust; per sample the factor is omega * w(z),
+    /// w of the studentised residual z = d / sqrt(max(V_i + V_j, floor)), so delta counts sigmas.  Returns sum c / sum u (never
+    /// divided by the mass the loss keeps); mean_weight (nullable): sum u / n_pairs; inlier_mass (nullable): sum k / sum u;
+    /// pair_terms (nullable): n_pairs x 4 floats, pair-major, per pair i < j {c, u, k, r}, r the mean squared studentised residual
+    /// (ecc_hip.h; varianceRobustScale takes delta from r).  Single device only.
+    double evaluateVarianceRobust(int loss, float delta, float floor, double* mean_weight = 0x0, double* inlier_mass = 0x0,
+                                  std::vector<float>* pair_terms = 0x0)
+    {
+        if (m_gh) throw std::runtime_error("evaluateVarianceRobust: not available on a device group");
+        detail::sizePairTerms(pair_terms, allPairs(), 4);
+        double value = 0.0;
+        detail::check(ecc_metric_evaluate_variance_robust(m_h, loss, delta, floor, &value, mean_weight, inlier_mass, dataOrNull(pair_terms)));
+        return value;
+    }
+
+    /// Not in the reference: ecc_metric_evaluate_variance_robust_pairs -- evaluateVarianceRobust over an index list of
+    /// (P0, P1, D0, D1) tuples as evaluateVariancePairs takes them (4 ints per tuple; D0, D1 in [0, n_views), the variance follows
+    /// the data index).  Returns sum c / sum u over the list; mean_weight, inlier_mass (nullable) as there; pair_terms (nullable):
+    /// n_pairs x 4 floats {c, u, k, r} in list order.  The sampling mode resolves from the list's length (ecc_hip.h).  Single device only.
+    double evaluateVarianceRobustPairs(const std::vector<int>& indices, int loss, float delta, float floor, double* mean_weight = 0x0,
+                                       double* inlier_mass = 0x0, std::vector<float>* pair_terms = 0x0)
+    {
+        if (m_gh) throw std::runtime_error("evaluateVarianceRobustPairs: not available on a device group");
+        const std::vector<int32_t> idx = detail::widenTuples("evaluateVarianceRobustPairs", indices);
+        detail::sizePairTerms(pair_terms, idx.size() / 4, 4);
+        double value = 0.0;
+        if (mean_weight) *mean_weight = 0.0;
+        if (inlier_mass) *inlier_mass = 0.0;
+        detail::check(ecc_metric_evaluate_variance_robust_pairs(m_h, dataOrNull(idx), (int)(idx.size() / 4), loss, delta, floor, &value,
+                                                                mean_weight, inlier_mass, dataOrNull(pair_terms)));
+        return value;
+    }
+#ifdef ECC_ADAPTER_HAVE_EIGEN
+    double evaluateVarianceRobustPairs(const std::vector<Eigen::Vector4i>& indices, int loss, float delta, float floor,
+                                       double* mean_weight = 0x0, double* inlier_mass = 0x0, std::vector<float>* pair_terms = 0x0)
+    {
+        const std::vector<int> idx = detail::flattenTuples<int>(indices);
+        return evaluateVarianceRobustPairs(idx, loss, delta, floor, mean_weight, inlier_mass, pair_terms);
+    }
+#endif
+
+    /// Not in the reference: ecc_metric_evaluate_variance_robust_pose_deltas -- evaluatePoseDeltas under inverse-variance weights AND
+    /// the robust loss of evaluateVarianceRobust (the metric holds 2 n_views intermediates; loss, delta, floor as there).  values[k],
+    /// mean_weights[k] and inlier_masses[k] (the latter two nullable) are bit-identical to replacing the views moved_views[k] by
+    /// moved_Ps[k], setProjectionMatrices and evaluateVarianceRobust(loss, delta, floor); the current matrices stay.  Single device only.
+    void evaluateVarianceRobustPoseDeltas(const std::vector<std::vector<int> >& moved_views,
+                                          const std::vector<std::vector<Geometry::ProjectionMatrix> >& moved_Ps, int loss, float delta,
+                                          float floor, std::vector<double>& values, std::vector<double>* mean_weights = 0x0,
+                                          std::vector<double>* inlier_masses = 0x0)
+    {
+        if (m_gh) throw std::runtime_error("evaluateVarianceRobustPoseDeltas: not available on a device group");
+        if (moved_views.size() != moved_Ps.size()) throw std::runtime_error("evaluateVarianceRobustPoseDeltas: one matrix list per pose");
+        values.assign(moved_views.size(), 0.0);
+        detail::assignIfPresent(mean_weights, moved_views.size());
+        detail::assignIfPresent(inlier_masses, moved_views.size());
+        if (moved_views.empty()) return;
+        const PackedPoseLists l("evaluateVarianceRobustPoseDeltas", moved_views, moved_Ps);
+        detail::check(ecc_metric_evaluate_variance_robust_pose_deltas(m_h, (int)moved_views.size(), l.off.data(), l.views_or_null(), l.Ps_or_null(),
+                                                                      loss, delta, floor, values.data(), dataOrNull(mean_weights),
+                                                                      dataOrNull(inlier_masses)));
+    }
+
+    /// Not in the reference: ecc_metric_evaluate_variance_robust_transforms -- evaluateTransforms under inverse-variance weights AND
+    /// the robust loss (n_source and Ts as for evaluateTransforms).  Per transform values[k] = sum c / sum u over the cross pairs
+    /// under Ts[k], mean_weights (nullable): sum u / (n_source n_target), inlier_masses (nullable): sum k / sum u; pair_terms
+    /// (nullable): Ts.size() x n_target x n_source x 4 floats, per transform its rows {c, u, k, r} with the source index fast.  Every
+    /// number is bit-identical to Ps[i] * Ts[k] by ecc_host_compose_transform, setProjectionMatrices and evaluateVarianceRobustPairs
+    /// of the cross list per transform; the current matrices stay (ecc_hip.h).  Single device only.
+    void evaluateVarianceRobustTransforms(int n_source, const std::vector<Geometry::RP3Homography>& Ts, int loss, float delta, float floor,
+                                          std::vector<double>& values, std::vector<double>* mean_weights = 0x0,
+                                          std::vector<double>* inlier_masses = 0x0, float* pair_terms = 0x0)
+    {
+        if (m_gh) throw std::runtime_error("evaluateVarianceRobustTransforms: not available on a device group");
+        values.assign(Ts.size(), 0.0);
+        detail::assignIfPresent(mean_weights, Ts.size());
+        detail::assignIfPresent(inlier_masses, Ts.size());
+        const std::vector<double> flat = detail::flattenTransforms(Ts);
+        detail::check(ecc_metric_evaluate_variance_robust_transforms(m_h, n_source, (int)Ts.size(), flat.data(), loss, delta, floor, values.data(),
+                                                                     dataOrNull(mean_weights), dataOrNull(inlier_masses), pair_terms));
+    }
+
+    /// ecc_host_variance_robust_scale: a scale delta for evaluateVarianceRobust from the rows {c, u, k, r} of an earlier call
+    /// (normally the one with delta = infinity): k x the median over the pairs with r > 0 of sqrt(r); 0.0 without such a pair.
+    /// Touches no device.
+    static double varianceRobustScale(const std::vector<float>& pair_terms, double k = 1.0)
+    {
+        if (pair_terms.size() % 4) throw std::runtime_error("varianceRobustScale: four floats per pair");
+        return ecc_host_variance_robust_scale(pair_terms.empty() ? 0x0 : pair_terms.data(), (int64_t)(pair_terms.size() / 4), k);
+    }
+
     /// Not in the reference: ecc_metric_evaluate_robust_pose_deltas -- evaluatePoseDeltas under the per-sample robust loss of
     /// evaluateRobust (loss, delta as there).  values[k] and inlier_masses[k] (inlier_masses nullable) are bit-identical to replacing
     /// the views moved_views[k] by moved_Ps[k], setProjectionMatrices and evaluateRobust(loss, delta); the current matrices stay.

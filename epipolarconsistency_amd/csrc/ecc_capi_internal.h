@@ -65,6 +65,7 @@ extern "C" hipError_t ecc_launch_pairs_weighted(const EccPairParams* p, const Ec
 extern "C" hipError_t ecc_launch_pairs_robust(const EccPairParams* p, const EccRobustParams* g, hipStream_t stream);
 extern "C" hipError_t ecc_launch_pairs_weighted_robust(const EccPairParams* p, const EccWeightedRobustParams* g, hipStream_t stream);
 extern "C" hipError_t ecc_launch_pairs_variance(const EccPairParams* p, const EccVarianceParams* g, hipStream_t stream);
+extern "C" hipError_t ecc_launch_pairs_variance_robust(const EccPairParams* p, const EccVarianceRobustParams* g, hipStream_t stream);
 // the segmented sums of columns 0 and 1 of a column-form buffer: per pose over all pairs with the pose's own entries substituted
 // (weighted_poses_kernel.hip), per transform over its cross list (weighted_transforms_kernel.hip)
 extern "C" hipError_t ecc_launch_sum_weighted_poses(const float* base_cols, long long base_stride, long long count, int n, int Q,
@@ -519,6 +520,8 @@ int robust_check(const ecc_metric* m, const double* value, int loss, float delta
 int weighted_robust_check(const ecc_metric* m, const double* value, int loss, float delta);
 // ecc_variance.hip: weighted_check's conditions on the metric and a finite floor > 0, in the order include/ecc_hip.h states
 int variance_check(const ecc_metric* m, float floor);
+// ecc_variance_robust.hip: the robust calls' conditions on value, loss and delta, then variance_check's
+int variance_robust_check(const ecc_metric* m, const double* value, int loss, float delta, float floor);
 
 // The distance of two channels' row-paired and row-quad copies, for the pair forms that read more than one copy per view (g: any
 // of their parameter structs).

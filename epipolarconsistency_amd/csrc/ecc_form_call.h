@@ -2,8 +2,9 @@
 // forms are column-form calls (ecc_column_call.h) whose pair kernels differ in what they store per pair; what a call does around
 // its pair launch does not depend on the form.  A PairForm says what does: how many columns the pair launch stores, how many of
 // them are summed, how to launch the pair kernel into a column buffer, how totals become the caller's results.  weighted_form
-// (ecc_weighted.hip), robust_form (ecc_robust.hip), weighted_robust_form (ecc_weighted_robust.hip) and variance_form
-// (ecc_variance.hip) build one from a call's arguments; the drivers below are written over it and never ask which form it is.
+// (ecc_weighted.hip), robust_form (ecc_robust.hip), weighted_robust_form (ecc_weighted_robust.hip), variance_form
+// (ecc_variance.hip) and variance_robust_form (ecc_variance_robust.hip) build one from a call's arguments; the drivers below are
+// written over it and never ask which form it is.
 //
 // form_call          all pairs of the current matrices, or an index list: E1 (if the device geometry is behind the matrices),
 //                    k01_kernel into the Gram family's records (column_call_begin), the form's pair launch (form_columns),
@@ -29,7 +30,7 @@
 //                    transforms one at a time through the form's list call
 // The segmented sums read the S leading columns of a column-form buffer and know nothing of what the columns mean: S == 2 goes
 // through sum_weighted_poses_kernel / sum_weighted_transforms_kernel as above, whatever the form's T; S == 3 (the weighted-robust
-// form) through sum_form_poses_kernel / sum_form_transforms_kernel (form_sums_kernel.hip), which take all S columns in one walk ->
+// and the variance-robust form) through sum_form_poses_kernel / sum_form_transforms_kernel (form_sums_kernel.hip), which take all S columns in one walk ->
 // S K result words, word S k + col.
 #ifndef ECC_FORM_CALL_H
 #define ECC_FORM_CALL_H
@@ -58,6 +59,9 @@ PairForm robust_form(int loss, float delta, double* values, double* inlier_masse
 PairForm weighted_robust_form(int loss, float delta, double* values, double* coverages, double* inlier_masses);
 // ecc_variance.hip: T = S = 2, columns {c, u}; values[k] = sum c / sum u, mean_weights[k] (nullable) = sum u / count
 PairForm variance_form(float floor, double* values, double* mean_weights);
+// ecc_variance_robust.hip: T = 4, S = 3, columns {c, u, k, r}; values[k] = sum c / sum u, mean_weights[k] (nullable) = sum u / count,
+// inlier_masses[k] (nullable) = sum k / sum u
+PairForm variance_robust_form(int loss, float delta, float floor, double* values, double* mean_weights, double* inlier_masses);
 
 // poses per batch: the two-column sum's grid is slices x poses x 2 columns, half a million workgroups at most (the S-column sum has
 // no z dimension and takes the same limit)

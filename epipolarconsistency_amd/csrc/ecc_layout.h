@@ -404,4 +404,19 @@ struct EccVarianceParams {
     float floor;                   // the least s = V_i + V_j a sample's weight 1 / s is formed from; finite, > 0
 };
 
+// ---- inverse-variance weights and the robust loss of the studentised residual (variance_robust_kernel.hip) ----
+// 2 n_views channel-major intermediates and copies as for EccVarianceParams.  Four float32 entries per pair -- the value c, the mean
+// weight u, the weight mass the loss keeps k and the mean squared studentised residual r -- stored COLUMN-major with the Gram form's
+// col_stride rule.
+struct EccVarianceRobustParams {
+    int64_t paired_channel_bytes;  // as in EccGramParams
+    int64_t quad_channel_bytes;
+    float* values;                 // 4 columns of col_stride floats
+    int64_t col_stride;
+    float floor;                   // as in EccVarianceParams; launch-uniform
+    int loss;                      // ECC_ROBUST_*, launch-uniform
+    float delta;                   // the scale in sigmas, > 0; +infinity: no sample is down-weighted
+    float inv_delta;               // (float)(1.0 / (double)delta), formed on the host
+};
+
 #endif

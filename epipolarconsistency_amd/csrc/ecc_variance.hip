@@ -10,8 +10,9 @@
 // sums are sum_weighted_poses_kernel and sum_weighted_transforms_kernel as they stand.
 // Every value and mean weight of a batch has the bits of ecc_metric_set_projections + the sequential call for that pose or
 // transform (tests/test_gpu_variance_batches.py); what a batch does not take is evaluated that way inside the call.
-// Not here: base columns kept between calls; range, group and RCCL forms; the form under the correlation cost or combined with the
-// robust loss; a covariance-aware model for derivative data.
+// The form combined with the robust loss is ecc_variance_robust.hip; it takes variance_check from here.
+// Not here: base columns kept between calls; range, group and RCCL forms; the form under the correlation cost; a covariance-aware
+// model for derivative data.
 #include "ecc_form_call.h"
 #include "ecc_variance_host.h"
 

@@ -1119,6 +1119,78 @@ int ecc_metric_evaluate_weighted_robust_pose_deltas(ecc_metric* m, int n_poses, 
 int ecc_metric_evaluate_weighted_robust_transforms(ecc_metric* m, int n_source, int n_transforms, const double* Ts, int loss, float delta,
                                                    double* values, double* coverages, double* inlier_masses, float* pair_terms);
 
+/* Inverse-variance sample weights and the robust loss together: the loss in sigma units (csrc/ecc_variance_robust.hip,
+ * csrc/variance_robust_kernel.hip).  This block supersedes the "Not built" sentences of the variance block and of the
+ * weighted-robust block above where they name the combination of the variance form with the robust loss: it is built here.  A
+ * low-dose sequence has photon-starved lines whose variance is known, and an instrument nobody flagged.
+ * ecc_metric_evaluate_robust thresholds the raw residual d, so a line that is merely noisy, and known to be, is rejected as an
+ * outlier; ecc_metric_evaluate_variance keeps the instrument at full weight.  Here the loss is applied to the studentised residual
+ * z = d / sigma with sigma^2 = V_i + V_j, and delta is "so many sigmas".
+ *
+ * The metric is ecc_metric_evaluate_variance's: n_dtrs == 2 * n_views, the data of every view, then its variance field.  Positions,
+ * kappa range, sampling mode and d are those of ecc_metric_evaluate_all.  loss and delta as for ecc_metric_evaluate_robust:
+ * ECC_LOSS_*, float32 > 0, +infinity allowed; inv_delta = (float)(1.0 / (double)delta) is formed on the host.  floor as for
+ * ecc_metric_evaluate_variance: finite, > 0.  Per sample, every operation is one float32 operation, nothing is contracted but the
+ * written fmaf, division and square root are the compiler's correctly rounded ones (no intrinsic, no fast-math flag):
+ *     s   = V_i(sample) + V_j(sample)            unsigned taps, as in the variance form
+ *     sc  = s < floor ? floor : s
+ *     om  = 1.0f / sc
+ *     a   = fabsf(d)
+ *     HUBER, TRUNCATED:   thr = delta * sqrtf(sc);  t = fminf(1.0f, thr / a);   w = t * (2.0f - t)  |  t * t
+ *     GEMAN_MCCLURE:      q = a * inv_delta;        w = 1.0f / fmaf(q * om, q, 1.0f)
+ *     f   = om * w
+ * The value term is the weighted call's with f in mu's place, in the polynomial and in the exact / reference wording.  Beside it,
+ * per +-kappa step: mass (double)(om_p + om_m), kept (double)(f_p + f_m), raw (double)(om_p * (dp * dp)) + (double)(om_m * (dm * dm)),
+ * count 2.0.  Per pair four float32 columns {c, u, k, r}: c the value, u = mass / count the mean weight, k = kept / count the weight
+ * mass the loss keeps, r = raw / count the mean squared studentised residual -- a reduced chi^2 of the pair, free of loss and
+ * delta.  A pair with no trip, or a tuple with P0 == P1, has {0, 1, 1, 0}.  The column sums are added in the order of
+ * ecc_sum_order.h:
+ *     *value       = sum c / sum u     (never divided by the kept mass)
+ *     *mean_weight = sum u / n_pairs   (nullable)
+ *     *inlier_mass = sum k / sum u     (nullable)
+ * sum u == 0 gives 0, 0, 0 and ECC_OK.  pair_terms (host, nullable): n_pairs x 4 float32 rows {c, u, k, r}.
+ *
+ * ecc_host_variance_robust_scale (host only, no device): k x the median of sqrt((double)r_q) over the rows {c, u, k, r} with
+ * r_q > 0; an even count takes the mean of the two middle values; no such row gives 0.0.  V is the line variance only up to a
+ * constant factor, so this call calibrates "one sigma" from the data: one call at delta = +infinity, then delta = scale(terms, n, k).
+ *
+ * By construction (tests/test_gpu_variance_robust.py holds each to the bit):
+ *   1. delta = +infinity gives {c, u}, value and mean_weight the bits of ecc_metric_evaluate_variance; k has u's bits and
+ *      inlier_mass == 1.0.
+ *   2. V == 0.5f everywhere with floor <= 1 gives {c, k, r}, value and inlier_mass the bits of ecc_metric_evaluate_robust's {c, u, r}
+ *      at the same loss and delta on the n_views metric; u == 1.0 and mean_weight == 1.0.
+ *   3. Both together give the bits of ecc_metric_evaluate_all.
+ *   4. All V and the floor x 4 with delta x 1/2 multiply every column by 1/4 exactly; value and inlier_mass keep their bits.
+ *
+ * ecc_metric_evaluate_variance_robust_pairs: an index list as for ecc_metric_evaluate_variance_pairs; with tuples (i, j, i, j) the
+ * rows have the bits of the all-pairs rows under the same resolved sampling mode.
+ * ecc_metric_evaluate_variance_robust_pose_deltas: the lists of ecc_metric_evaluate_pose_deltas; values[k], mean_weights[k] and
+ * inlier_masses[k] (the latter two nullable) have THE BITS of ecc_metric_set_projections(pose k) +
+ * ecc_metric_evaluate_variance_robust; what the batch does not take is evaluated sequentially inside the call.
+ * ecc_metric_evaluate_variance_robust_transforms: views, transforms and the cross list of ecc_metric_evaluate_variance_transforms;
+ * every result and the pair rows (n_transforms x n_target x n_source x 4) have THE BITS of ecc_metric_set_projections(the composed
+ * matrices) + ecc_metric_evaluate_variance_robust_pairs(that list); the fallback is sequential, inside the call.
+ *
+ * Errors are returned before anything is launched or written, in this order: m == NULL; list form: n_pairs < 0, or idx4 == NULL with
+ * n_pairs > 0 (pose form: moved_offsets or values NULL, then n_poses < 1: ECC_OK, then the list arrays NULL with entries; transform
+ * form: n_transforms < 0, Ts or values NULL with n_transforms > 0); value == NULL, loss outside 0..2, delta NaN or <= 0; the
+ * conditions of ecc_metric_evaluate_variance in its order -- no matrices, fewer than two views, n_dtrs != 2 * n_views, a floor that is
+ * not finite and > 0: ECC_ERR_INVALID_ARGUMENT, then use_corr: ECC_ERR_UNSUPPORTED; list form: a bad tuple (pose form: a bad list;
+ * transform form: n_source outside [1, n_views)).  After these checks n_pairs == 0 is ECC_OK with nothing written.  The calls change
+ * nothing a later call can see.
+ * Not built: kept base columns; range, group and RCCL forms; use_corr; the maps of this form; a covariance-aware model for
+ * derivative data. */
+int ecc_metric_evaluate_variance_robust(ecc_metric* m, int loss, float delta, float floor, double* value, double* mean_weight,
+                                        double* inlier_mass, float* pair_terms);
+int ecc_metric_evaluate_variance_robust_pairs(ecc_metric* m, const int32_t* idx4, int n_pairs, int loss, float delta, float floor,
+                                              double* value, double* mean_weight, double* inlier_mass, float* pair_terms);
+int ecc_metric_evaluate_variance_robust_pose_deltas(ecc_metric* m, int n_poses, const int32_t* moved_offsets, const int32_t* moved_views,
+                                                    const double* moved_Ps, int loss, float delta, float floor, double* values,
+                                                    double* mean_weights, double* inlier_masses);
+int ecc_metric_evaluate_variance_robust_transforms(ecc_metric* m, int n_source, int n_transforms, const double* Ts, int loss, float delta,
+                                                   float floor, double* values, double* mean_weights, double* inlier_masses, float* pair_terms);
+double ecc_host_variance_robust_scale(const float* pair_terms, int64_t n_pairs, double k);
+
 /* Multi-GPU building block: evaluate only pairs ij in [first, first+count) of the get_ij order
  * (ref: EpipolarConsistencyCommon.hxx:52-79); returns the partial sum (float64) -- the caller
  * all-reduces {sum, count}.  pair_values (host, nullable) receives `count` floats. */
