@@ -447,11 +447,12 @@ def _map_form_call(fn, metric, lead, extra, views, k, n_scalars, n_rows, n_colum
     return out
 
 
-def _map_weights_call(fn, metric, min_hits, gain):
-    """fn(handle, min_hits, gain, handles) for the map the metric holds -> one RadonIntermediate per mapped view."""
+def _map_weights_call(fn, metric, *rule):
+    """fn(handle, *rule, handles) for the map the metric holds -> one RadonIntermediate per mapped view.  rule: the floats of the
+    feedback rule, (min_hits, gain) for the two weights calls, (floor, min_hits, gain, max_factor) for the variances call."""
     k = getattr(metric, "_robust_map_count", 0)
     hs = (C.c_void_p * max(k, 1))()
-    check(fn(metric._h, float(min_hits), float(gain), hs))
+    check(fn(metric._h, *[float(x) for x in rule], hs))
     return [RadonIntermediate(metric.ctx, C.c_void_p(h)) for h in hs[:k]]
 
 
@@ -1127,6 +1128,39 @@ class MetricRadonIntermediate:
         matrices and everything the metric keeps stay."""
         return _scalar_form_call(_lib.lib().ecc_metric_evaluate_variance_robust, self._h, (), (int(loss), float(delta), float(floor)), 3,
                                  _n_all_pairs(self._Ps), 4, want_pairs)
+
+    def evaluate_variance_robust_map(self, loss, delta, floor, views=None, want_pairs=False):
+        """ecc_metric_evaluate_variance_robust_map: evaluate_variance_robust(loss, delta, floor) on a 2 * n_views metric -- the same
+        bits in value, mean_weight, inlier_mass and pairs -- and WHERE the loss rejected, in sigma units: per mapped view a HITS
+        plane, the bilinear footprints of every sample taken in that view, and a REJ plane, the same times 1 - w, w the loss weight
+        of the STUDENTISED residual.  The deposits are in count units (not multiplied by omega): REJ / HITS is the share of a bin's
+        samples whose |z| exceeded delta.  views: data indices in [0, n_views) (distinct), None: every view in order.  Returns
+        (value, mean_weight, inlier_mass, hits, rejected[, pairs]); hits, rejected: (len(views), n_t, n_alpha) float32, pairs
+        (n_pairs, 4) rows {c, u, k, r}.  Fixed-point sums on the device: the same call gives the same bits.  delta = inf: rejected
+        is all zeros and hits is evaluate_robust_map's on the n-metric.  variance_robust_map_variances turns the held map into the
+        next pass's variance fields."""
+        v, k = self._weighted_map_views(views)
+        return _map_form_call(_lib.lib().ecc_metric_evaluate_variance_robust_map, self, (), (int(loss), float(delta), float(floor)), v, k, 3,
+                              _n_all_pairs(self._Ps), 4, want_pairs)
+
+    def evaluate_variance_robust_map_pairs(self, idx4, loss, delta, floor, views=None, want_pairs=False):
+        """ecc_metric_evaluate_variance_robust_map_pairs: evaluate_variance_robust_map over an index list of (P0, P1, D0, D1) tuples
+        as evaluate_variance_robust_pairs takes them: D0, D1 and `views` index the data intermediates, in [0, n_views); variance
+        and map follow the data index.  A pair listed twice deposits twice; the planes do not depend on the order of the list."""
+        idx = _idx4_list(idx4)
+        v, k = self._weighted_map_views(views)
+        return _map_form_call(_lib.lib().ecc_metric_evaluate_variance_robust_map_pairs, self, (_ptr(idx), len(idx)),
+                              (int(loss), float(delta), float(floor)), v, k, 3, len(idx), 4, want_pairs)
+
+    def variance_robust_map_variances(self, floor, min_hits=1.0, gain=1.0, max_factor=1e4):
+        """ecc_metric_variance_robust_map_variances: the next pass's variance fields from the map the last
+        evaluate_variance_robust_map[_pairs] call left on the device -- a list of RadonIntermediate (FILTER_NONE), one per mapped
+        view in the order of `views`.  Per bin mu is robust_map_weights' rule on the held planes (1 where h < min_hits, else
+        float32(max(0, 1 - gain * r / h)) in float64), factor = max_factor where mu * max_factor <= 1, else 1 / mu (float32), and the
+        field is V where factor == 1, else max(V, floor / 2) * factor (float32), V the metric's current variance of that view.
+        V / mu is the IRLS reading of the loss weight; the raise to floor / 2 lets a clean view's zeros be raised at all.  Raises if
+        no map is held or the held map is another kind's."""
+        return _map_weights_call(_lib.lib().ecc_metric_variance_robust_map_variances, self, floor, min_hits, gain, max_factor)
 
     def evaluate_transforms(self, n_source, Ts, want_pairs=False):
         """ecc_metric_evaluate_transforms: the registration of two scans (ref: tools/Registration/Registration3D3D.hxx).  The
@@ -1938,6 +1972,48 @@ def refine_line_weights(ctx, Ps, data, weights=None, loss=_lib.LOSS_TRUNCATED, k
         if owned:
             for w in current:
                 w.close()
+        raise
+    return current, records
+
+
+def refine_variances(ctx, Ps, data, variances, floor, loss=_lib.LOSS_TRUNCATED, k=2.0, passes=2, min_hits=1.0, gain=1.0, max_factor=1e4,
+                     sampling="auto"):
+    """Variance fields from the robust loss in sigma units, iterated: the loss says where it rejects, the map raises the variance
+    there, and the next pass maps the metric over those variances -- after which evaluate_variance alone, with no
+    loss switched on, is robust.  data: the n Radon intermediates of the views Ps; variances: their n variance fields
+    (variance_intermediates); floor as for evaluate_variance.  Every pass is evaluate_variance_robust_map +
+    variance_robust_map_variances on a 2 n metric over the previous pass's variances.  delta = k x variance_robust_scale of the
+    first pass's rows at delta = inf and is then held, as in refine_line_weights.  Returns (the final n variance intermediates --
+    the caller closes them --, one dict per pass: delta, mean_weight, inlier_mass, rejected_share (n,) = sum REJ / sum HITS per
+    view, 0 where a view has no hits).  Every metric and every intermediate field made here is closed; `variances` is not."""
+    data, current, owned = list(data), list(variances), False
+    n = len(data)
+    if int(passes) < 1:
+        raise ValueError("passes must be at least 1")
+    if len(current) != n:
+        raise ValueError("variances: one intermediate per view")
+    delta, records = None, []
+    try:
+        for _ in range(int(passes)):
+            m = MetricRadonIntermediate(ctx, Ps, data + current).setSampling(sampling)
+            try:
+                if delta is None:
+                    delta = variance_robust_scale(m.evaluate_variance_robust(loss, float("inf"), floor, want_pairs=True)[3], k)
+                _, mean_weight, mass, hits, rej = m.evaluate_variance_robust_map(loss, delta, floor)
+                new = m.variance_robust_map_variances(floor, min_hits, gain, max_factor)
+            finally:
+                m.close()
+            if owned:
+                for v in current:
+                    v.close()
+            current, owned = new, True
+            h, r = hits.astype(np.float64).sum(axis=(1, 2)), rej.astype(np.float64).sum(axis=(1, 2))
+            records.append(dict(delta=delta, mean_weight=mean_weight, inlier_mass=mass,
+                                rejected_share=np.where(h > 0, r / np.where(h > 0, h, 1.0), 0.0)))
+    except BaseException:
+        if owned:
+            for v in current:
+                v.close()
         raise
     return current, records
 

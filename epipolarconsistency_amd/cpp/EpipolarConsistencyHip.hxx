@@ -1360,6 +1360,61 @@ public:
         return ecc_host_variance_robust_scale(pair_terms.empty() ? 0x0 : pair_terms.data(), (int64_t)(pair_terms.size() / 4), k);
     }
 
+    /// Not in the reference: ecc_metric_evaluate_variance_robust_map -- evaluateVarianceRobust (the same bits in the result,
+    /// mean_weight, inlier_mass and pair_terms) and WHERE the loss rejected, in sigma units: per mapped view a HITS plane (the
+    /// footprints of the samples taken in that view) and a REJ plane (the same times 1 - w, w the loss weight of the studentised
+    /// residual).  The deposits are in count units: REJ / HITS is the share of a bin's samples whose |z| exceeded delta.  views:
+    /// distinct data indices in [0, n_views), empty: every view in order.  hits, rejected (nullable): resized to views x n_t x n_alpha
+    /// floats, alpha fastest.  Fixed-point sums on the device: the same call gives the same bits (ecc_hip.h).  Single device only.
+    double evaluateVarianceRobustMap(int loss, float delta, float floor, const std::vector<int>& views, std::vector<float>* hits,
+                                     std::vector<float>* rejected, double* mean_weight = 0x0, double* inlier_mass = 0x0,
+                                     std::vector<float>* pair_terms = 0x0)
+    {
+        if (m_gh) throw std::runtime_error("evaluateVarianceRobustMap: not available on a device group");
+        detail::sizePairTerms(pair_terms, allPairs(), 4);
+        const std::vector<int32_t> v(views.begin(), views.end());
+        const size_t planes = sizeMapPlanes(v.empty() ? Ps.size() : v.size(), hits, rejected);
+        double value = 0.0;
+        detail::check(ecc_metric_evaluate_variance_robust_map(m_h, loss, delta, floor, dataOrNull(v), (int)v.size(), dataOrNull(hits),
+                                                              dataOrNull(rejected), &value, mean_weight, inlier_mass, dataOrNull(pair_terms)));
+        m_map_planes = planes;
+        return value;
+    }
+
+    /// Not in the reference: ecc_metric_evaluate_variance_robust_map_pairs -- evaluateVarianceRobustMap over an index list of
+    /// (P0, P1, D0, D1) tuples as evaluateVarianceRobustPairs takes them; D0, D1 and `views` (empty: every view) index the data
+    /// intermediates, in [0, n_views).  Single device only.
+    double evaluateVarianceRobustMapPairs(const std::vector<int>& indices, int loss, float delta, float floor, const std::vector<int>& views,
+                                          std::vector<float>* hits, std::vector<float>* rejected, double* mean_weight = 0x0,
+                                          double* inlier_mass = 0x0, std::vector<float>* pair_terms = 0x0)
+    {
+        if (m_gh) throw std::runtime_error("evaluateVarianceRobustMapPairs: not available on a device group");
+        const std::vector<int32_t> idx = detail::widenTuples("evaluateVarianceRobustMapPairs", indices);
+        detail::sizePairTerms(pair_terms, idx.size() / 4, 4);
+        const std::vector<int32_t> v(views.begin(), views.end());
+        const size_t planes = sizeMapPlanes(v.empty() ? Ps.size() : v.size(), hits, rejected);
+        double value = 0.0;
+        if (mean_weight) *mean_weight = 0.0;
+        if (inlier_mass) *inlier_mass = 0.0;
+        detail::check(ecc_metric_evaluate_variance_robust_map_pairs(m_h, dataOrNull(idx), (int)(idx.size() / 4), loss, delta, floor,
+                                                                    dataOrNull(v), (int)v.size(), dataOrNull(hits), dataOrNull(rejected), &value,
+                                                                    mean_weight, inlier_mass, dataOrNull(pair_terms)));
+        m_map_planes = idx.empty() ? 0 : planes;
+        return value;
+    }
+
+    /// Not in the reference: ecc_metric_variance_robust_map_variances -- the next pass's variance fields from the map the last
+    /// evaluateVarianceRobustMap[Pairs] call left on the device, one intermediate per mapped view (Filter None): per bin
+    /// max(V, floor / 2) / mu, mu robustMapWeights' rule on the held planes and 1 / mu capped at max_factor; a bin the loss left
+    /// alone keeps V's bits (ecc_hip.h).  The caller owns the results.
+    std::vector<RadonIntermediate*> varianceRobustMapVariances(float floor, float min_hits = 1.0f, float gain = 1.0f, float max_factor = 1e4f)
+    {
+        if (m_gh) throw std::runtime_error("varianceRobustMapVariances: not available on a device group");
+        std::vector<ecc_dtr*> hs(m_map_planes ? m_map_planes : 1, (ecc_dtr*)0x0);
+        detail::check(ecc_metric_variance_robust_map_variances(m_h, floor, min_hits, gain, max_factor, hs.data()));
+        return ownMapWeights(hs);
+    }
+
     /// Not in the reference: ecc_metric_evaluate_robust_pose_deltas -- evaluatePoseDeltas under the per-sample robust loss of
     /// evaluateRobust (loss, delta as there).  values[k] and inlier_masses[k] (inlier_masses nullable) are bit-identical to replacing
     /// the views moved_views[k] by moved_Ps[k], setProjectionMatrices and evaluateRobust(loss, delta); the current matrices stay.

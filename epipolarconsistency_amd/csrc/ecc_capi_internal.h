@@ -291,6 +291,9 @@ struct ValueKey {
 };
 }  // namespace ecc_internal
 
+// the kinds of robust map a metric can hold (ecc_robust_map.h); each kind's *_map_weights / *_map_variances call refuses the others
+enum EccMapKind { ECC_MAP_PLAIN, ECC_MAP_WEIGHTED, ECC_MAP_VARIANCE };
+
 struct ecc_metric {
     template <class T>
     using DeviceArray = ecc_internal::DeviceArray<T>;
@@ -442,9 +445,10 @@ struct ecc_metric {
     DeviceArray<float> map_planes_d;
     int map_n_mapped = 0;
     bool map_valid = false;
-    // which kind of map is held: ecc_metric_evaluate_weighted_robust_map's (ecc_weighted_robust_map.hip: deposits under the line
-    // weights of a 2 n metric) or the n-metric's; map_slot_d is the plane table (map_n_slots entries), then the mapped intermediates
-    bool map_weighted = false;
+    // which kind of map is held: the n-metric's, ecc_metric_evaluate_weighted_robust_map's (ecc_weighted_robust_map.hip: deposits
+    // under the line weights of a 2 n metric) or ecc_metric_evaluate_variance_robust_map's (ecc_variance_robust_map.hip: the loss in
+    // sigma units, deposits in count units); map_slot_d is the plane table (map_n_slots entries), then the mapped intermediates
+    EccMapKind map_kind = ECC_MAP_PLAIN;
     int map_n_slots = 0;
     // ecc_debug_step_stamps: host clock (seconds, steady) at fixed points of the last set_projections / synchronous evaluation
     double stamps[ECC_STEP_STAMPS] = {0};

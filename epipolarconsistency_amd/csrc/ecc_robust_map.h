@@ -1,6 +1,7 @@
-// ecc_robust_map.h -- what the two map kernels (robust_map_kernel.hip, weighted_robust_map_kernel.hip) and their host files
-// (ecc_robust_map.hip, ecc_weighted_robust_map.hip) share: the parameters of the map launches, the geometry of the planes, the
-// deposits (for the kernel files) and the launch sequence of a map call (for the host files) (DESIGN.md 4.24, 4.25).
+// ecc_robust_map.h -- what the three map kernels (robust_map_kernel.hip, weighted_robust_map_kernel.hip,
+// variance_robust_map_kernel.hip) and their host files (ecc_robust_map.hip, ecc_weighted_robust_map.hip,
+// ecc_variance_robust_map.hip) share: the parameters of the map launches, the geometry of the planes, the
+// deposits (for the kernel files) and the launch sequence of a map call (for the host files) (DESIGN.md 4.24, 4.25, 4.31).
 //
 // The map of a view is two planes, HITS and REJ, of unsigned 64-bit fixed point with quantum 2^-32.  On the device a plane has the
 // geometry of the view's slab (ecc_layout.h): (n_alpha + 2) rows of `pitch` cells, cell (row, bin) for the padded element
@@ -43,6 +44,24 @@ struct EccWeightedRobustMapParams {
     int64_t rej_cells;
 };
 
+// The map in sigma units (variance_robust_map_kernel.hip): EccVarianceRobustParams' fields -- 2 n_views channel-major intermediates,
+// the data and their variance fields, four columns {c, u, k, r} -- then the planes as above; slot_of has n_views entries, one per
+// DATA intermediate.
+struct EccVarianceRobustMapParams {
+    int64_t paired_channel_bytes;  // as in EccGramParams
+    int64_t quad_channel_bytes;
+    float* values;                 // 4 columns of col_stride floats
+    int64_t col_stride;
+    float floor;                   // as in EccVarianceParams; launch-uniform
+    int loss;
+    float delta;                   // the scale in sigmas
+    float inv_delta;
+    unsigned long long* planes;
+    const int32_t* slot_of;
+    int64_t plane_cells;
+    int64_t rej_cells;
+};
+
 #if defined(__HIPCC__)
 extern "C" hipError_t ecc_launch_pairs_robust_map(const EccPairParams* p, const EccRobustMapParams* g, hipStream_t stream);
 // fixed[n_planes][plane_cells] -> out[n_planes][n_t][n_alpha] floats, (float)((double)q * 2^-32) of the folded sums
@@ -57,6 +76,13 @@ extern "C" hipError_t ecc_launch_pairs_weighted_robust_map(const EccPairParams* 
 extern "C" hipError_t ecc_launch_weighted_robust_map_weights(const float* hits, const float* rejected, const float* const* weights,
                                                              const int32_t* views, float* slabs, int n_mapped, int n_alpha, int n_t, int pitch,
                                                              float min_hits, float gain, hipStream_t stream);
+extern "C" hipError_t ecc_launch_pairs_variance_robust_map(const EccPairParams* p, const EccVarianceRobustMapParams* g, hipStream_t stream);
+// slabs[k] = the next pass's variance field of view views[k] per padded element, k in [0, n_mapped), written completely: variances
+// are the slabs of the metric's variance intermediates (device table), views the mapped data indices (device); the rule is
+// include/ecc_hip.h's (ecc_metric_variance_robust_map_variances), half = 0.5f * floor
+extern "C" hipError_t ecc_launch_variance_robust_map_variances(const float* hits, const float* rejected, const float* const* variances,
+                                                               const int32_t* views, float* slabs, int n_mapped, int n_alpha, int n_t, int pitch,
+                                                               float floor, float min_hits, float gain, float max_factor, hipStream_t stream);
 #endif
 
 // ---- the deposits: for the kernel files, behind ecc_pair_forms.h ---------------------------------------------------------------
@@ -138,10 +164,14 @@ struct MapPlanes {
 #if defined(ECC_FORM_CALL_H)
 namespace ecc_internal {
 // ecc_robust_map.hip: everything of a map call behind the checks of its evaluation.  f: the evaluation's form with the map kernels
-// behind its launch; nD: the intermediates a sample can lie in (the entries of the plane table); weighted: which kind of map the
+// behind its launch; nD: the intermediates a sample can lie in (the entries of the plane table); kind: which kind of map the
 // metric holds afterwards.
-int robust_map_call(ecc_metric* m, const PairForm& f, bool weighted, const int32_t* idx4, int64_t count, int nD, const int32_t* views,
+int robust_map_call(ecc_metric* m, const PairForm& f, EccMapKind kind, const int32_t* idx4, int64_t count, int nD, const int32_t* views,
                     int n_mapped, float* hits, float* rejected, float* pair_terms);
+// ecc_robust_map.hip: everything of a feedback call (the held map as the next pass's weights or variances) behind its own argument
+// checks and its held-map check: one slab per mapped view on the metric's device, launch(hits, rejected, slabs, n_mapped) on the
+// context's stream -- hits and rejected the held float planes --, no wait, and the handles over the slabs in out[0 .. n_mapped).
+int robust_map_feedback(ecc_metric* m, const std::function<hipError_t(const float*, const float*, float*, int)>& launch, ecc_dtr** out);
 }  // namespace ecc_internal
 #endif
 

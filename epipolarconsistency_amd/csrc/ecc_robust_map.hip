@@ -8,7 +8,8 @@
 // checks, column_call_begin -- the planes' room as its more_scratch, the plane table's upload and the planes' memset as its
 // upload_more --, the map form's pair launch between the timing events, column_call_finish with the finishing kernel and the
 // planes' copies as its queue_more, the one wait.  It is written once, over the form (robust_map_call): the map under line weights
-// (ecc_weighted_robust_map.hip) runs it with weighted_robust_form's columns.
+// (ecc_weighted_robust_map.hip) runs it with weighted_robust_form's columns, the map in sigma units (ecc_variance_robust_map.hip)
+// with variance_robust_form's.
 #include "ecc_form_call.h"
 #include "ecc_robust_map.h"
 
@@ -67,9 +68,9 @@ int map_slots(const int32_t* views, int n_mapped, int nD, std::vector<int32_t>* 
 }  // namespace
 
 // Everything of a map call behind the checks of its evaluation (ecc_robust_map.h); ecc_weighted_robust_map.hip calls it with the
-// weighted form.  The plane table is followed by the list of mapped intermediates, slot by slot, which the weighted map's weights
-// kernel reads.
-int ecc_internal::robust_map_call(ecc_metric* m, const PairForm& f, bool weighted, const int32_t* idx4, int64_t count, int nD,
+// weighted form, ecc_variance_robust_map.hip with the variance-robust form.  The plane table is followed by the list of mapped
+// intermediates, slot by slot, which the weighted map's weights kernel and the variance map's variances kernel read.
+int ecc_internal::robust_map_call(ecc_metric* m, const PairForm& f, EccMapKind kind, const int32_t* idx4, int64_t count, int nD,
                                   const int32_t* views, int n_mapped, float* hits, float* rejected, float* pair_terms)
 {
     std::vector<int32_t> slot_of;
@@ -82,7 +83,7 @@ int ecc_internal::robust_map_call(ecc_metric* m, const PairForm& f, bool weighte
         if (slot_of[v] >= 0) slot_of[(size_t)nD + slot_of[v]] = v;
     const int64_t bins = (int64_t)m->n_alpha * m->n_t, cells = ecc_robust_map_plane_cells(m->n_alpha, m->n_t);
     m->map_valid = false;
-    m->map_weighted = weighted;
+    m->map_kind = kind;
     m->map_n_mapped = n_map;
     m->map_n_slots = nD;
     if (count == 0) {  // an empty list: nothing was sampled
@@ -131,7 +132,7 @@ ECC_EXPORT int ecc_metric_evaluate_robust_map(ecc_metric* m, int loss, float del
     if (rc) return rc;
     if ((int64_t)m->dtrs.size() < (int64_t)m->n_views) return fail(ECC_ERR_INVALID_ARGUMENT, "fewer Radon intermediates than projection matrices");
     const int64_t n = m->n_views;
-    return robust_map_call(m, robust_map_form(loss, delta, value, inlier_mass), /*weighted=*/false, nullptr, n * (n - 1) / 2, (int)n, views,
+    return robust_map_call(m, robust_map_form(loss, delta, value, inlier_mass), ECC_MAP_PLAIN, nullptr, n * (n - 1) / 2, (int)n, views,
                            n_mapped, hits, rejected, pair_terms);
 }
 
@@ -146,7 +147,7 @@ ECC_EXPORT int ecc_metric_evaluate_robust_map_pairs(ecc_metric* m, const int32_t
     if (rc) return rc;
     rc = check_index_list(idx4, n_pairs, m->n_views, (int)m->dtrs.size(), "index array contains invalid indices");
     if (rc) return rc;
-    return robust_map_call(m, robust_map_form(loss, delta, value, inlier_mass), /*weighted=*/false, idx4, n_pairs, (int)m->dtrs.size(), views,
+    return robust_map_call(m, robust_map_form(loss, delta, value, inlier_mass), ECC_MAP_PLAIN, idx4, n_pairs, (int)m->dtrs.size(), views,
                            n_mapped, hits, rejected, pair_terms);
 }
 
@@ -158,8 +159,19 @@ ECC_EXPORT int ecc_metric_robust_map_weights(ecc_metric* m, float min_hits, floa
     if (!(gain >= 0.0f) || !std::isfinite(gain)) return fail(ECC_ERR_INVALID_ARGUMENT, "gain must be finite and not negative");
     if (!m->map_valid || m->map_n_mapped < 1 || !m->map_planes_d.ptr)
         return fail(ECC_ERR_INVALID_ARGUMENT, "no robust map held: call ecc_metric_evaluate_robust_map first (refresh_dtrs and set_params drop it)");
-    if (m->map_weighted)
+    if (m->map_kind == ECC_MAP_WEIGHTED)
         return fail(ECC_ERR_INVALID_ARGUMENT, "the held map was made under line weights: its weights are ecc_metric_weighted_robust_map_weights'");
+    if (m->map_kind != ECC_MAP_PLAIN)
+        return fail(ECC_ERR_INVALID_ARGUMENT, "the held map was made in sigma units: it feeds ecc_metric_variance_robust_map_variances");
+    return robust_map_feedback(m, [&](const float* h, const float* r, float* slabs, int n_map) {
+        return ecc_launch_robust_map_weights(h, r, slabs, n_map, m->n_alpha, m->n_t, m->pitch, min_hits, gain, m->ctx->stream);
+    }, out);
+}
+
+// Everything of a feedback call behind its checks (ecc_robust_map.h): the three kinds' calls differ in their checks and launches alone.
+int ecc_internal::robust_map_feedback(ecc_metric* m, const std::function<hipError_t(const float*, const float*, float*, int)>& launch,
+                                      ecc_dtr** out)
+{
     ecc_ctx* ctx = m->ctx;
     const int rc = set_device(ctx);
     if (rc) return rc;
@@ -169,12 +181,11 @@ ECC_EXPORT int ecc_metric_robust_map_weights(ecc_metric* m, float min_hits, floa
     owner->device = ctx->device;
     HIP_TRY(hipMalloc((void**)&owner->ptr, (size_t)slab * (size_t)n_map * sizeof(float)));
     ecc_mark_busy(m);
-    HIP_TRY(ecc_launch_robust_map_weights(m->map_planes_d.ptr, m->map_planes_d.ptr + (size_t)n_map * bins, owner->ptr, n_map, m->n_alpha, m->n_t,
-                                          m->pitch, min_hits, gain, ctx->stream));
+    HIP_TRY(launch(m->map_planes_d.ptr, m->map_planes_d.ptr + (size_t)n_map * bins, owner->ptr, n_map));
     return make_weight_handles(ctx, owner, n_map, m->n_alpha, m->n_t, m->n_u, m->n_v, out);
 }
 
-// Debug: the fixed-point planes of the held map, of either kind, as the kernel left them -- every HITS plane, then every REJ plane,
+// Debug: the fixed-point planes of the held map, of any kind, as the kernel left them -- every HITS plane, then every REJ plane,
 // (n_alpha + 2) x pitch cells each in the slab's padded geometry -- so that a test can add and compare the integer sums themselves.
 ECC_EXPORT int ecc_debug_robust_map_fixed(ecc_metric* m, uint64_t* out, int64_t capacity)
 {

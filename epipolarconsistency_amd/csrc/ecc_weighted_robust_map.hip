@@ -46,7 +46,7 @@ ECC_EXPORT int ecc_metric_evaluate_weighted_robust_map(ecc_metric* m, int loss, 
     const int rc = weighted_robust_check(m, value, loss, delta);
     if (rc) return rc;
     const int64_t n = m->n_views;
-    return robust_map_call(m, weighted_robust_map_form(loss, delta, value, coverage, inlier_mass), /*weighted=*/true, nullptr, n * (n - 1) / 2,
+    return robust_map_call(m, weighted_robust_map_form(loss, delta, value, coverage, inlier_mass), ECC_MAP_WEIGHTED, nullptr, n * (n - 1) / 2,
                            (int)n, views, n_mapped, hits, rejected, pair_terms);
 }
 
@@ -63,7 +63,7 @@ ECC_EXPORT int ecc_metric_evaluate_weighted_robust_map_pairs(ecc_metric* m, cons
     rc = check_index_list(idx4, n_pairs, m->n_views, m->n_views,
                           "index array contains invalid indices (matrices and data intermediates lie in [0, n_views))");
     if (rc) return rc;
-    return robust_map_call(m, weighted_robust_map_form(loss, delta, value, coverage, inlier_mass), /*weighted=*/true, idx4, n_pairs, m->n_views,
+    return robust_map_call(m, weighted_robust_map_form(loss, delta, value, coverage, inlier_mass), ECC_MAP_WEIGHTED, idx4, n_pairs, m->n_views,
                            views, n_mapped, hits, rejected, pair_terms);
 }
 
@@ -73,22 +73,13 @@ ECC_EXPORT int ecc_metric_weighted_robust_map_weights(ecc_metric* m, float min_h
     if (!out) return fail(ECC_ERR_INVALID_ARGUMENT, "the output is null");
     if (!(min_hits >= 0.0f) || !std::isfinite(min_hits)) return fail(ECC_ERR_INVALID_ARGUMENT, "min_hits must be finite and not negative");
     if (!(gain >= 0.0f) || !std::isfinite(gain)) return fail(ECC_ERR_INVALID_ARGUMENT, "gain must be finite and not negative");
-    if (!m->map_valid || !m->map_weighted || m->map_n_mapped < 1 || !m->map_planes_d.ptr || m->map_n_slots != m->n_views ||
+    if (!m->map_valid || m->map_kind != ECC_MAP_WEIGHTED || m->map_n_mapped < 1 || !m->map_planes_d.ptr || m->map_n_slots != m->n_views ||
         (int64_t)m->dtrs.size() != 2 * (int64_t)m->n_views)
         return fail(ECC_ERR_INVALID_ARGUMENT,
                     "no weighted robust map held: call ecc_metric_evaluate_weighted_robust_map first (refresh_dtrs and set_params drop it)");
-    ecc_ctx* ctx = m->ctx;
-    const int rc = set_device(ctx);
-    if (rc) return rc;
-    const int n_map = m->map_n_mapped;
-    const int64_t slab = ecc_layout_floats(m->n_alpha, m->n_t), bins = (int64_t)m->n_alpha * m->n_t;
-    auto owner = std::make_shared<Slab>();
-    owner->device = ctx->device;
-    HIP_TRY(hipMalloc((void**)&owner->ptr, (size_t)slab * (size_t)n_map * sizeof(float)));
-    ecc_mark_busy(m);
     // W_v: the slab of dtr n_views + v, the handle's own; the mapped views: behind the plane table
-    HIP_TRY(ecc_launch_weighted_robust_map_weights(m->map_planes_d.ptr, m->map_planes_d.ptr + (size_t)n_map * bins, m->dtr_table_d.ptr + m->n_views,
-                                                   m->map_slot_d.ptr + m->map_n_slots, owner->ptr, n_map, m->n_alpha, m->n_t, m->pitch, min_hits,
-                                                   gain, ctx->stream));
-    return make_weight_handles(ctx, owner, n_map, m->n_alpha, m->n_t, m->n_u, m->n_v, out);
+    return robust_map_feedback(m, [&](const float* h, const float* r, float* slabs, int n_map) {
+        return ecc_launch_weighted_robust_map_weights(h, r, m->dtr_table_d.ptr + m->n_views, m->map_slot_d.ptr + m->map_n_slots, slabs, n_map,
+                                                      m->n_alpha, m->n_t, m->pitch, min_hits, gain, m->ctx->stream);
+    }, out);
 }

@@ -35,49 +35,21 @@
 // Both kernels run wholly on the frames of ecc_pair_forms.h: form_main_sums and form_reference_sums with every piece
 // below them.  VarianceRobustForm's trip is VarianceForm's 8 gathers and reciprocals followed by the studentised weights; five
 // per-lane float64 sums in trip order.  loss, delta and floor are launch-uniform kernel arguments and the loss a uniform select, not
-// a template parameter.  Plain vector loads and stores only: no atomics, no inline assembly, no LDS in the main kernels.
-// Not here (include/ecc_hip.h): base columns kept between calls; range, group and RCCL forms; the correlation cost; the maps of this
-// form; a covariance-aware model for derivative data.
+// a template parameter; the weight itself is ecc_studentised_weight.h's, shared with the map of this form
+// (variance_robust_map_kernel.hip).  Plain vector loads and stores only: no atomics, no inline assembly, no LDS in the main kernels.
+// Not here (include/ecc_hip.h): base columns kept between calls; range, group and RCCL forms; the correlation cost; a
+// covariance-aware model for derivative data.
 #include <hip/hip_runtime.h>
 #include <float.h>
 
 #include "ecc_layout.h"
 #include "ecc_pair_forms.h"
+#include "ecc_studentised_weight.h"
 
 namespace {
 
 // the five per-lane sums: the value, the weight mass, the mass the loss keeps, the squared studentised residuals, the sample count
 enum { VALUE, MASS, KEPT, RAW, COUNT, VARIANCE_ROBUST_SUMS };
-
-// the launch-uniform part of the weight, in scalar registers
-struct StudentisedLoss {
-    int loss;
-    float delta, inv_delta, floor;
-};
-
-// the two factors of a sample's weight f = om * w
-struct StudentisedWeight {
-    float om, f;
-};
-
-// om = 1 / max(V_a + V_b, floor) and f = om * w(|d| / sqrt(max(V_a + V_b, floor))) (`loss` is wave-uniform, the branch a scalar one)
-__device__ __forceinline__ StudentisedWeight studentised_weight(const StudentisedLoss& L, float va, float vb, float d)
-{
-    const float s = va + vb;
-    const float sc = s < L.floor ? L.floor : s;
-    const float om = 1.0f / sc;
-    const float a = fabsf(d);
-    float w;
-    if (L.loss == ECC_ROBUST_GEMAN_MCCLURE) {
-        const float q = a * L.inv_delta;
-        w = 1.0f / fmaf(q * om, q, 1.0f);
-    } else {
-        const float thr = L.delta * sqrtf(sc);
-        const float t = fminf(1.0f, thr / a);
-        w = L.loss == ECC_ROBUST_HUBER ? t * (2.0f - t) : t * t;
-    }
-    return {om, om * w};
-}
 
 // the trips of the three loop kinds (ecc_pair_forms.h): the 4 data gathers and, at the same taps of the variance copies, 4 more; the
 // residuals of the + and the - sample, their studentised weights, the sums

@@ -1178,8 +1178,8 @@ int ecc_metric_evaluate_weighted_robust_transforms(ecc_metric* m, int n_source, 
  * not finite and > 0: ECC_ERR_INVALID_ARGUMENT, then use_corr: ECC_ERR_UNSUPPORTED; list form: a bad tuple (pose form: a bad list;
  * transform form: n_source outside [1, n_views)).  After these checks n_pairs == 0 is ECC_OK with nothing written.  The calls change
  * nothing a later call can see.
- * Not built: kept base columns; range, group and RCCL forms; use_corr; the maps of this form; a covariance-aware model for
- * derivative data. */
+ * Not built: kept base columns; range, group and RCCL forms; use_corr; a covariance-aware model for derivative data.
+ * (Listed here before and built since: the maps of this form, ecc_metric_evaluate_variance_robust_map below.) */
 int ecc_metric_evaluate_variance_robust(ecc_metric* m, int loss, float delta, float floor, double* value, double* mean_weight,
                                         double* inlier_mass, float* pair_terms);
 int ecc_metric_evaluate_variance_robust_pairs(ecc_metric* m, const int32_t* idx4, int n_pairs, int loss, float delta, float floor,
@@ -1190,6 +1190,58 @@ int ecc_metric_evaluate_variance_robust_pose_deltas(ecc_metric* m, int n_poses, 
 int ecc_metric_evaluate_variance_robust_transforms(ecc_metric* m, int n_source, int n_transforms, const double* Ts, int loss, float delta,
                                                    float floor, double* values, double* mean_weights, double* inlier_masses, float* pair_terms);
 double ecc_host_variance_robust_scale(const float* pair_terms, int64_t n_pairs, double k);
+
+/* Where the robust loss rejects IN SIGMA UNITS (csrc/ecc_variance_robust_map.hip, csrc/variance_robust_map_kernel.hip):
+ * the map of ecc_metric_evaluate_variance_robust, and the held map as the next pass's variance fields.  This block supersedes the
+ * "Not built" sentence of the block above where it names the maps of that form.  A map of the raw-residual loss
+ * (ecc_metric_evaluate_robust_map) points at the lines that are known to be noisy; this one studentises first.
+ *
+ * ecc_metric_evaluate_variance_robust_map / _map_pairs take the metric (n_dtrs == 2 * n_views: the data, then the variance
+ * fields), loss, delta, floor, value, mean_weight, inlier_mass and pair_terms of ecc_metric_evaluate_variance_robust / _pairs and
+ * return THEIR BITS in them, the n_pairs x 4 rows {c, u, k, r} included.  Beside that, per +-kappa sample of a pair with the loss
+ * weight w of its studentised residual (w alone: t * (2 - t), t * t or 1 / fmaf(q * om, q, 1), never f = om * w), per view of the
+ * pair that is mapped and per cell of the sample's footprint in that view, with the float32 footprint products b of
+ * ecc_metric_evaluate_robust_map:
+ *     HITS[cell] += b          REJ[cell] += b * (1 - w)          (all float32)
+ * The deposits are in COUNT units: they are not multiplied by om, which carries the data's units and reaches 1 / floor.
+ * REJ / HITS is then the share of a bin's samples whose |z| exceeded delta, which has a known expectation under a correct noise
+ * model.  REJ deposits with w == 1.0f are skipped; no address depends on w.  The planes, their fixed point (quantum 2^-32, integer
+ * atomics: the same arguments give the same bits in any order), hits, rejected, views and n_mapped are those of
+ * ecc_metric_evaluate_robust_map, with `views` distinct DATA indices in [0, n_views) for both forms, n_mapped == 0: every view.  The
+ * metric holds the float planes in the same place and remembers which of the three kinds of map it holds;
+ * ecc_debug_robust_map_fixed serves all of them.
+ *   delta = +infinity      REJ is exactly 0 everywhere and HITS has the bits of ecc_metric_evaluate_robust_map's on the n-metric
+ *                          over the same data, whatever V is.
+ *   V == 0.5f, floor <= 1  the fixed-point sums are those of ecc_metric_evaluate_robust_map on the n-metric at the same loss and delta.
+ *   V and floor x 4, delta x 1/2   both planes keep their bits.
+ *   - Errors before anything is launched or written, in this order: those of ecc_metric_evaluate_variance_robust[_pairs] in their
+ *     order; then the views list's as for ecc_metric_evaluate_robust_map.  After them n_pairs == 0 is ECC_OK: planes of zeros, no map
+ *     held.
+ * Launches: ecc_metric_evaluate_robust_map's sequence with pairs_variance_robust_map_kernel (8 gathers per kappa step) and the sums of
+ * c, u and k.  A diagnostic, once per outer iteration.
+ *
+ * ecc_metric_variance_robust_map_variances: the next pass's variance fields from the held map, one intermediate per mapped view v in
+ * out[0 .. n_mapped), handles as ecc_metric_robust_map_weights returns them.  One elementwise launch, no wait; every padded element e
+ * of every slab is written.  With old = V_v[e] read from the CURRENT contents of intermediate n_views + v, h and r the held float
+ * planes at the bin that e replicates and half = 0.5f * floor (exact):
+ *     mu     = h < min_hits ? 1.0f : (float)fmax(0.0, 1.0 - (double)gain * ((double)r / (double)h))      ecc_metric_robust_map_weights' rule
+ *     factor = (mu * max_factor <= 1.0f) ? max_factor : 1.0f / mu                                        float32
+ *     out    = factor == 1.0f ? old : (old < half ? half : old) * factor                                 float32
+ * V / mu is the IRLS reading: a sample's effective variance is sigma^2 / w, and mu is the mean w that reached the bin.  The raise to
+ * half the floor lets a field of zeros (a clean view) be raised at all; two raised samples sum to the floor exactly.  A bin with
+ * factor == 1 keeps its bits: a map that rejected nothing, or max_factor == 1, returns V.
+ *   - Errors, ECC_ERR_INVALID_ARGUMENT, in this order: m or out NULL; floor not finite and > 0; min_hits, gain not finite and >= 0;
+ *     max_factor not finite and >= 1; no map held, or the held map is not one of these calls' (ecc_metric_robust_map_weights and
+ *     ecc_metric_weighted_robust_map_weights in turn refuse a map of this kind).
+ * Not built: pose-delta and transform batches of any map; range, group and RCCL forms; use_corr; a third plane of squared residuals
+ * (a per-bin excess-variance estimate in place of 1 / mu); an IRLS loop inside the library (the Python layer's refine_variances
+ * iterates the calls). */
+int ecc_metric_evaluate_variance_robust_map(ecc_metric* m, int loss, float delta, float floor, const int32_t* views, int n_mapped,
+        float* hits, float* rejected, double* value, double* mean_weight, double* inlier_mass, float* pair_terms);
+int ecc_metric_evaluate_variance_robust_map_pairs(ecc_metric* m, const int32_t* idx4, int n_pairs, int loss, float delta, float floor,
+        const int32_t* views, int n_mapped, float* hits, float* rejected,
+        double* value, double* mean_weight, double* inlier_mass, float* pair_terms);
+int ecc_metric_variance_robust_map_variances(ecc_metric* m, float floor, float min_hits, float gain, float max_factor, ecc_dtr** out);
 
 /* Multi-GPU building block: evaluate only pairs ij in [first, first+count) of the get_ij order
  * (ref: EpipolarConsistencyCommon.hxx:52-79); returns the partial sum (float64) -- the caller
