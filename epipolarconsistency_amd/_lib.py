@@ -90,6 +90,8 @@ SIGNATURES = {
     "ecc_metric_evaluate_pose_deltas": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "ecc_metric_set_pose_batching": (_i, [_vp, _i]),
     "ecc_metric_last_batched_poses": (_i, [_vp, C.POINTER(_i64)]),
+    "ecc_metric_set_form_incremental": (_i, [_vp, _i]),
+    "ecc_metric_last_form_base_pairs": (_i, [_vp, C.POINTER(_i64)]),
     "ecc_metric_evaluate_gradient": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ecc_metric_last_gradient_path": (_i, [_vp, C.POINTER(_i)]),
     "ecc_metric_evaluate_gram": (_i, [_vp, _i, _vp, _vp]),

@@ -853,6 +853,19 @@ class MetricRadonIntermediate:
     def last_batched_poses(self):
         return _last_count(_lib.lib().ecc_metric_last_batched_poses, self._h)
 
+    def setFormIncremental(self, enable=True):
+        """Not in the reference (ecc_metric_set_form_incremental, default off): the evaluate_{weighted, robust, weighted_robust,
+        variance, variance_robust}_pose_deltas calls keep their base columns on the device between calls and re-evaluate only the
+        pairs of views whose matrix changed since -- the optimiser pattern (set one view, probe).  Every result keeps the bits of
+        the call with the mode off; any change of the setting drops what is kept."""
+        check(_lib.lib().ecc_metric_set_form_incremental(self._h, 1 if enable else 0))
+        return self
+
+    def last_form_base_pairs(self):
+        """ecc_metric_last_form_base_pairs: base pairs the last such call evaluated -- n (n - 1) / 2 with the mode off or on a miss,
+        the pairs of the c refreshed views, 0 on a hit or with pose batching off."""
+        return _last_count(_lib.lib().ecc_metric_last_form_base_pairs, self._h)
+
     def evaluate_gradient(self, view, Ps_plus, Ps_minus, h, want_probes=False):
         """ecc_metric_evaluate_gradient: the metric at the current matrices and its central-difference gradient over p pose
         parameters of one view.  Ps_plus / Ps_minus: the view's 3x4 matrix at x + h[k] e_k and at x - h[k] e_k, p matrices each

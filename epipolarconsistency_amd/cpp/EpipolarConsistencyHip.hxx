@@ -675,6 +675,7 @@ class MetricRadonIntermediate : public Metric {
     int record_reuse = -1;    // -1: the library's default
     int small_eval = -1;      // -1: the library's default (on)
     int host_join = -1;       // -1: the library's default (on; a group's metrics: off)
+    int form_incremental = -1;  // -1: the library's default (off)
     ecc_metric* m_h;          // single-device metric, or the group's rank-0 metric (borrowed) when m_gh is set
     ecc_group_metric* m_gh;   // sharded over a group of devices (ecc_group_*), else null
     ecc_ctx* m_ctx;
@@ -724,6 +725,7 @@ class MetricRadonIntermediate : public Metric {
             if (record_reuse >= 0) detail::check(ecc_metric_set_record_reuse(m_h, record_reuse));
             if (small_eval >= 0) detail::check(ecc_metric_set_small_eval(m_h, small_eval));
             if (host_join >= 0) detail::check(ecc_metric_set_host_join(m_h, host_join));
+            if (form_incremental >= 0) detail::check(ecc_metric_set_form_incremental(m_h, form_incremental));
         }
     }
     void push_projections()
@@ -787,6 +789,18 @@ public:
     /// on the host for the moved views' launches and then queues the sum, instead of ordering it with an event on the device; the
     /// same launches, bit-identical results.  Single-device metrics only: a group's metrics keep the device-side order.
     MetricRadonIntermediate& setHostJoin(bool on = true) { host_join = on ? 1 : 0; push_params(); return *this; }
+    /// Not in the reference: ecc_metric_set_form_incremental (library default: off) -- the evaluate*PoseDeltas calls of the weighted,
+    /// robust, weighted-robust, variance and variance-robust forms keep their base columns between calls and re-evaluate only the
+    /// pairs of views whose matrix changed since; bit-identical results.  Every setter of this class pushes all parameters again
+    /// and so drops what is kept.  Single-device metrics only.
+    MetricRadonIntermediate& setFormIncremental(bool on = true) { form_incremental = on ? 1 : 0; push_params(); return *this; }
+    /// Base pairs the last such call evaluated (ecc_metric_last_form_base_pairs; 0 on a device group).
+    long long lastFormBasePairs() const
+    {
+        int64_t v = 0;
+        if (m_h && !m_gh) detail::check(ecc_metric_last_form_base_pairs(m_h, &v));
+        return (long long)v;
+    }
     /// Not in the reference: ecc_metric_evaluate_poses -- independent all-pairs evaluations of several sets of projection
     /// matrices (a sweep as in Gui/Visualization.h:78-98 plotCostFunction, the probes of a finite-difference gradient),
     /// each value bit-identical to setProjectionMatrices(poses[k]) + evaluate().  Poses that differ from the current matrices

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/ecc_hip.h"
+#include "ecc_form_base.h"
 #include "ecc_host_geometry.h"
 #include "ecc_layout.h"
 #include "ecc_view_changes.h"
@@ -80,6 +81,10 @@ extern "C" hipError_t ecc_launch_sum_form_poses(const float* base_cols, long lon
                                                 double* partial_d, double* out_host_dev, hipStream_t stream);
 extern "C" hipError_t ecc_launch_sum_form_transforms(const float* val_cols, long long col_stride, long long count, int K, int S, int slices,
                                                      double* partial_d, double* out_host_dev, hipStream_t stream);
+// the T columns of a pose grid of c changed views (M_d: device, ascending) to the all-pairs positions of kept base columns
+// (form_base_scatter_kernel.hip)
+extern "C" hipError_t ecc_launch_form_base_scatter(const float* vals, long long vals_stride, int n, int c, const int32_t* M_d, int T,
+                                                   float* base_cols, long long base_stride, hipStream_t stream);
 extern "C" hipError_t ecc_launch_dilate_max(const float* src, float* dst, int64_t stride, int n_img, int n_u, int n_v, int radius,
                                             hipStream_t stream);
 extern "C" hipError_t ecc_launch_clip_min(const float* lengths, int64_t lengths_stride, float* dst, int64_t dst_stride, int n_img,
@@ -450,6 +455,14 @@ struct ecc_metric {
     // sigma units, deposits in count units); map_slot_d is the plane table (map_n_slots entries), then the mapped intermediates
     EccMapKind map_kind = ECC_MAP_PLAIN;
     int map_n_slots = 0;
+    // ecc_metric_set_form_incremental (ecc_form_call.h): the T base columns of the last *_pose_deltas call of a form
+    // family, col_stride apart as that call's columns are in gram_values_d, with the form, the parameters and the matrices they belong
+    // to (ecc_form_base.h); the all-pairs, list, map and Gram calls keep to gram_values_d and neither see nor disturb them.  Dropped
+    // (ecc_drop_form_base) wherever cache.valid is dropped for a data or parameter reason, and by a change of n_views.
+    int form_incremental = 0;
+    ecc_internal::Kept<ecc_form_base::Key> form_base;
+    DeviceArray<float> form_base_d;
+    int64_t last_form_base_pairs = 0;  // base pairs the last *_pose_deltas call of a form family evaluated (ecc_metric_last_form_base_pairs)
     // ecc_debug_step_stamps: host clock (seconds, steady) at fixed points of the last set_projections / synchronous evaluation
     double stamps[ECC_STEP_STAMPS] = {0};
 };
@@ -459,6 +472,8 @@ inline void ecc_mark_busy(ecc_metric* m)
     m->quiet = false;
     ++m->queue_seq;
 }
+
+inline void ecc_drop_form_base(ecc_metric* m) { m->form_base.valid = false; }
 
 inline void ecc_stamp(ecc_metric* m, int k)
 {

@@ -996,6 +996,7 @@ ECC_EXPORT int ecc_debug_set_poly_tolerance(ecc_metric* m, float tol_bins)
     m->economise_tol = tol_bins;
     m->rec.valid = false;    // the kept records and values were made with the old tolerance
     m->cache.valid = false;
+    ecc_drop_form_base(m);
     return ECC_OK;
 }
 

@@ -12,7 +12,9 @@
 //                    The metric's kept records, kept values and pose-batch values are not touched (a list stages its tuples in the
 //                    pose batch's index scratch).
 // form_pose_deltas   K poses that each replace a few views of the current matrices (the lists of ecc_metric_evaluate_pose_deltas):
-//   base columns     all pairs at the current matrices (form_columns: the all-pairs call's own launches), once per call
+//   base columns     all pairs at the current matrices (form_columns: the all-pairs call's own launches), once per call -- or, under
+//                    ecc_metric_set_form_incremental, kept between calls in the metric's own buffer and refreshed for the pairs of the
+//                    views that changed since (form_base_kept, ecc_form_base.h)
 //   per batch        (which poses: ecc_pose_batches.h) pose_list_kernel (index grid, E1 of the extended matrices), k01_kernel over
 //                    the n x Q grid into the pose batch's records, the form's pair launch over it with the base's parameters (the
 //                    sampling mode and wave split of an all-pairs evaluation; EccPairParams::n_views stays n: the weight copy of data
@@ -48,6 +50,11 @@ struct PairForm {
     std::function<hipError_t(ecc_metric* m, const EccPairParams& p, float* values, int64_t col_stride)> launch;
     // result k of the call from the totals of the summed columns over `count` pairs
     std::function<void(const double* totals, int64_t count, int64_t k)> finish;
+    // which form it is and the parameters its columns depend on, for the key of kept base columns alone (ecc_form_base.h): the
+    // drivers still never ask
+    int kind = ecc_form_base::NONE;
+    int loss = 0;
+    float delta = 0.f, floor = 0.f;
 };
 
 // ecc_weighted.hip: T = S = 2, columns {c, u}; values[k] = sum c / sum u, coverages[k] (coverages nullable) = sum u / count
@@ -120,26 +127,25 @@ inline int form_call_all_pairs(ecc_metric* m, const PairForm& f, float* pair_ter
     return form_call(m, f, nullptr, n * (n - 1) / 2, pair_terms);
 }
 
-// One batch: poses with off[0] = 0 ... off[K] = Q columns over the base matrices `base`, whose columns are in m->gram_values_d
-// (base_c).  sums[S k + col], S = f.S: the sum of column col of pose k over all pairs.
-inline int form_pose_batch(ecc_metric* m, const PairForm& f, const double* base, const ColumnCall& base_c, int K, const int32_t* off,
-                           const int32_t* views, const double* moved_Ps, double* sums)
+// A pose grid up to and including its pair launch: poses with off[0] = 0 ... off[K] = Q columns over the base matrices `base`, under
+// the parameters base_p of the base's record launch.  The grid's T columns are in m->pose_values_d, *vals_stride apart, once the
+// stream gets there; `words` result words (none: 0) are reserved in the pinned block, *out / *out_dev their addresses.
+inline int form_pose_grid(ecc_metric* m, const PairForm& f, const double* base, const EccPairParams& base_p, int K, const int32_t* off,
+                          const int32_t* views, const double* moved_Ps, int words, volatile uint64_t** out, double** out_dev,
+                          int64_t* vals_stride)
 {
     ecc_ctx* ctx = m->ctx;
-    const int64_t n = m->n_views, n_pairs = n * (n - 1) / 2;
+    const int64_t n = m->n_views;
     const int Q = off[K];
     const int64_t entries = n * (int64_t)Q;
-    const int64_t vals_stride = (std::max<int64_t>(entries, 1) + 3) & ~(int64_t)3;
-    volatile uint64_t* out = nullptr;
-    double* out_dev = nullptr;
-    const int words = f.S * K;
-    int rc = stage_pose_grid(m, base, K, off, views, moved_Ps, words, &out, &out_dev);
-    if (!rc) rc = m->pose_values_d.ensure(f.T * vals_stride, ctx->stream);
-    if (!rc) rc = m->pose_partial_d.ensure((int64_t)words * ecc_sum::SLICES, ctx->stream);
+    *vals_stride = (std::max<int64_t>(entries, 1) + 3) & ~(int64_t)3;
+    int rc = stage_pose_grid(m, base, K, off, views, moved_Ps, words, out, out_dev);
+    if (!rc) rc = m->pose_values_d.ensure(f.T * *vals_stride, ctx->stream);
+    if (!rc && words > 0) rc = m->pose_partial_d.ensure((int64_t)words * ecc_sum::SLICES, ctx->stream);
     if (rc) return rc;
     HIP_TRY(launch_pose_list(m, K, Q, words));
     if (entries > 0) {
-        EccPairParams p = base_c.p;  // the sampling mode of an all-pairs evaluation; n_views stays n
+        EccPairParams p = base_p;  // the sampling mode of an all-pairs evaluation; n_views stays n
         p.PinvTs = m->pose_PinvTs_d.ptr;
         p.Cs = m->pose_Cs_d.ptr;
         p.indices = m->pose_idx_d.ptr;
@@ -147,17 +153,124 @@ inline int form_pose_batch(ecc_metric* m, const PairForm& f, const double* base,
         p.first = 0;
         p.count = entries;
         HIP_TRY(ecc_launch_k01(&p, ctx->stream));
-        HIP_TRY(f.launch(m, p, m->pose_values_d.ptr, vals_stride));
+        HIP_TRY(f.launch(m, p, m->pose_values_d.ptr, *vals_stride));
     }
+    return ECC_OK;
+}
+
+// One batch: poses with off[0] = 0 ... off[K] = Q columns over the base matrices `base`, whose columns are at base_cols --
+// m->gram_values_d, or the kept columns of ecc_metric_set_form_incremental -- base_c.col_stride apart.  sums[S k + col], S = f.S:
+// the sum of column col of pose k over all pairs.
+inline int form_pose_batch(ecc_metric* m, const PairForm& f, const double* base, const ColumnCall& base_c, const float* base_cols, int K,
+                           const int32_t* off, const int32_t* views, const double* moved_Ps, double* sums)
+{
+    ecc_ctx* ctx = m->ctx;
+    const int64_t n = m->n_views, n_pairs = n * (n - 1) / 2;
+    const int Q = off[K];
+    int64_t vals_stride = 0;
+    volatile uint64_t* out = nullptr;
+    double* out_dev = nullptr;
+    const int words = f.S * K;
+    const int rc = form_pose_grid(m, f, base, base_c.p, K, off, views, moved_Ps, words, &out, &out_dev, &vals_stride);
+    if (rc) return rc;
     arm_pose_results(out, words);
     const int slices = ecc_sum::slices(n_pairs, m->sum_scratch_d.ptr != nullptr);  // the all-pairs call's choice
     if (f.S == 2)
-        HIP_TRY(ecc_launch_sum_weighted_poses(m->gram_values_d.ptr, base_c.col_stride, n_pairs, (int)n, Q, m->pose_lists_d.ptr, K,
+        HIP_TRY(ecc_launch_sum_weighted_poses(base_cols, base_c.col_stride, n_pairs, (int)n, Q, m->pose_lists_d.ptr, K,
                                               m->pose_values_d.ptr, vals_stride, slices, m->pose_partial_d.ptr, out_dev, ctx->stream));
     else  // all f.S columns in one walk of the pose's entries
-        HIP_TRY(ecc_launch_sum_form_poses(m->gram_values_d.ptr, base_c.col_stride, n_pairs, (int)n, Q, m->pose_lists_d.ptr, K,
+        HIP_TRY(ecc_launch_sum_form_poses(base_cols, base_c.col_stride, n_pairs, (int)n, Q, m->pose_lists_d.ptr, K,
                                           m->pose_values_d.ptr, vals_stride, f.S, slices, m->pose_partial_d.ptr, out_dev, ctx->stream));
     return wait_pose_results(ctx, out, words, sums);
+}
+
+// What kept base columns of form f under the record launch p belong to, beside the matrices.
+inline ecc_form_base::Key form_base_key(const ecc_metric* m, const PairForm& f, const EccPairParams& p)
+{
+    using ecc_form_base::bits_of;
+    ecc_form_base::Key k;
+    k.kind = f.kind;
+    k.T = f.T;
+    k.S = f.S;
+    k.loss = f.loss;
+    k.delta = bits_of(f.delta);
+    k.floor = bits_of(f.floor);
+    k.mode = p.reference_arithmetic ? ECC_SAMPLING_REFERENCE : (p.poly ? ECC_SAMPLING_POLYNOMIAL : ECC_SAMPLING_PER_SAMPLE);
+    k.radius = bits_of(p.object_radius_mm);  // the radius the launch resolved: the automatic one follows view 0
+    k.dkappa = bits_of(p.dkappa_user);
+    k.tol = bits_of(p.economise_tol);
+    k.use_corr = p.use_corr;
+    k.n_views = m->n_views;
+    k.n_dtrs = (int)m->dtrs.size();
+    return k;
+}
+
+// The base columns of a pose-delta call under ecc_metric_set_form_incremental: in m->form_base_d, c->col_stride
+// apart, once the stream gets there; c->p as form_columns leaves it.  ecc_form_base::decide says what is evaluated:
+//   miss      form_columns' launches, into the kept buffer; the key and the matrices are taken (never under ECC_SAMPLING_REFERENCE)
+//   hit       nothing; E1 if the device geometry is behind the matrices, as every column call makes sure
+//   refresh   ONE pose grid -- the changed views at their current matrices over the current matrices, form_pose_grid -- and
+//             form_base_scatter_kernel from its T columns into the kept ones; the changed views' matrices are taken
+// The kept columns are invalid while they are rewritten and valid once everything is queued, as evaluate_cached keeps cache.valid.
+inline int form_base_kept(ecc_metric* m, const PairForm& f, const double* Pcur, ColumnCall* c)
+{
+    namespace fb = ecc_form_base;
+    ecc_ctx* ctx = m->ctx;
+    const int64_t n = m->n_views, n_pairs = n * (n - 1) / 2;
+    int rc = set_device(ctx);
+    if (rc) return rc;
+    c->count = n_pairs;
+    c->col_stride = (n_pairs + 3) & ~(int64_t)3;
+    if (!m->quads_decided && n_pairs >= 32768) decide_quad_copies(m);  // (as column_call_begin: in front of the parameters)
+    rc = fill_pair_params(m, &c->p, n_pairs, /*need_e1=*/false);
+    if (rc) return rc;
+    const fb::Key key = form_base_key(m, f, c->p);
+    std::vector<int> changed;
+    std::vector<int32_t> views;
+    std::vector<double> moved;
+    const fb::Decision d = fb::decide(
+        m->form_base.valid, m->form_base.key, m->form_base.Ps.data(), key, Pcur, fb::limit(n),
+        [&](const std::vector<int>& ch) {
+            views.assign(ch.begin(), ch.end());
+            moved.resize(12 * ch.size());
+            for (size_t a = 0; a < ch.size(); ++a) std::memcpy(&moved[12 * a], Pcur + 12 * (size_t)ch[a], sizeof(double) * 12);
+            float kept_radius;
+            std::memcpy(&kept_radius, &m->form_base.key.radius, sizeof(kept_radius));
+            return pose_keeps_radius(m, (double)kept_radius, (int)ch.size(), views.data(), moved.data());
+        },
+        &changed);
+    m->form_base.valid = false;  // until everything below is queued
+    m->last_form_base_pairs = fb::base_pairs(d, n, (int64_t)changed.size());
+    if (d == fb::MISS) {
+        rc = column_call_begin(m, nullptr, n_pairs, /*T=*/0, f.S, c, [&] { return m->form_base_d.ensure((int64_t)f.T * c->col_stride, ctx->stream); }, no_more);
+        if (rc) return rc;
+        HIP_TRY(f.launch(m, c->p, m->form_base_d.ptr, c->col_stride));
+        if (fb::may_keep(key)) {
+            m->form_base.take(0, n_pairs, (int)n, key, Pcur);
+            m->form_base.valid = true;
+        }
+        return ECC_OK;
+    }
+    c->p.first = 0;
+    c->p.count = n_pairs;
+    rc = ensure_e1(m);
+    if (rc) return rc;
+    if (d == fb::REFRESH) {
+        const int cv = (int)changed.size();
+        const int32_t off[2] = {0, cv};
+        int64_t vals_stride = 0;
+        volatile uint64_t* out = nullptr;
+        double* out_dev = nullptr;
+        rc = form_pose_grid(m, f, Pcur, c->p, 1, off, views.data(), moved.data(), /*words=*/0, &out, &out_dev, &vals_stride);
+        if (rc) return rc;
+        // (the changed views on the device: pose_list_kernel's copy of the lists, behind the two offsets of the one pose)
+        HIP_TRY(ecc_launch_form_base_scatter(m->pose_values_d.ptr, vals_stride, (int)n, cv, m->pose_lists_d.ptr + 2, f.T, m->form_base_d.ptr,
+                                             c->col_stride, ctx->stream));
+        HIP_TRY(wait_stream_spin(ctx->stream));  // the call's first batch writes its own grid into the pinned block this one was read from
+        m->form_base.update(changed, Pcur);
+    }
+    m->form_base.valid = true;
+    return ECC_OK;
 }
 
 // The batched poses of a call; what the batch does not take goes into not_batched.
@@ -172,8 +285,14 @@ inline int form_pose_deltas_batched(ecc_metric* m, const PairForm& f, int n_pose
     double base_radius = 0.0;
     ecc_metric_get_object_radius(m, &base_radius);
     ColumnCall base_c;
-    int rc = form_columns(m, f, nullptr, n_pairs, &base_c);  // once per call
+    int rc;
+    if (m->form_incremental) rc = form_base_kept(m, f, base.data(), &base_c);
+    else {
+        rc = form_columns(m, f, nullptr, n_pairs, &base_c);  // once per call
+        m->last_form_base_pairs = n_pairs;
+    }
     if (rc) return rc;
+    const float* base_cols = m->form_incremental ? m->form_base_d.ptr : m->gram_values_d.ptr;
     std::vector<double> sums;
     const int64_t max_cols = std::max<int64_t>(ECC_POSE_BATCH_MAX_ENTRIES / n, ECC_POSE_BATCH_MAX_MOVED);
     rc = ecc_pose_batches::pack(
@@ -181,7 +300,8 @@ inline int form_pose_deltas_batched(ecc_metric* m, const PairForm& f, int n_pose
         [&](int c, const int32_t* vk, const double* Pk) { return pose_keeps_radius(m, base_radius, c, vk, Pk); },
         [&](const ecc_pose_batches::Batch& b) -> int {
             sums.resize(f.S * b.pose.size());
-            const int e = form_pose_batch(m, f, base.data(), base_c, (int)b.pose.size(), b.off.data(), b.views.data(), b.Ps.data(), sums.data());
+            const int e = form_pose_batch(m, f, base.data(), base_c, base_cols, (int)b.pose.size(), b.off.data(), b.views.data(), b.Ps.data(),
+                                          sums.data());
             if (e) return e;
             for (size_t q = 0; q < b.pose.size(); ++q) f.finish(&sums[f.S * q], n_pairs, b.pose[q]);
             m->last_batched_poses += (int64_t)b.pose.size();
@@ -203,6 +323,7 @@ inline int form_pose_deltas(ecc_metric* m, const PairForm& f, int n_poses, const
     int rc = set_device(m->ctx);
     if (rc) return rc;
     m->last_batched_poses = 0;
+    m->last_form_base_pairs = 0;  // (with batching off the call computes no base columns)
     std::vector<int> rest;
     if (m->pose_batching) {
         rc = form_pose_deltas_batched(m, f, n_poses, off, views, moved_Ps, &rest);

@@ -162,6 +162,7 @@ ECC_EXPORT int ecc_metric_refresh_dtrs(ecc_metric* m, int first, int count)
     if (count == 0) return ECC_OK;
     m->cache.valid = false;
     m->map_valid = false;  // the held robust map belongs to the old contents
+    ecc_drop_form_base(m);  // (any range: the kept base columns read the data and the weight or variance copies alike)
     int rc = set_device(m->ctx);
     if (rc) return rc;
     const int64_t paired_floats = (int64_t)(m->n_alpha + 1) * m->pitch * 2;
@@ -270,6 +271,7 @@ ECC_EXPORT int ecc_metric_set_projections(ecc_metric* m, const double* Ps, int n
     const int slot = (int)(g & 1);
     std::memcpy(m->Ps_h[slot].host, Ps, sizeof(double) * 12 * (size_t)n_views);
     m->set_generation = g;
+    if (n_views != m->n_views) ecc_drop_form_base(m);
     m->n_views = n_views;
     m->P_first.assign(Ps, Ps + 12);
     // E1 itself is launched by whoever needs PinvTs / Cs next (ensure_e1): an evaluation that finds most matrices
@@ -304,6 +306,7 @@ ECC_EXPORT int ecc_metric_set_params(ecc_metric* m, double object_radius_mm, dou
     m->dkappa = dkappa;
     m->use_corr = use_corr;
     m->cache.valid = false;
+    ecc_drop_form_base(m);
     m->map_valid = false;  // the held robust map belongs to the old parameters
     return ECC_OK;
 }
@@ -314,6 +317,7 @@ ECC_EXPORT int ecc_metric_set_sampling(ecc_metric* m, int mode)
     if (mode < ECC_SAMPLING_AUTO || mode > ECC_SAMPLING_REFERENCE) return fail(ECC_ERR_INVALID_ARGUMENT, "unknown sampling mode");
     m->sampling = mode;
     m->cache.valid = false;
+    ecc_drop_form_base(m);
     return ECC_OK;
 }
 
@@ -322,6 +326,22 @@ ECC_EXPORT int ecc_metric_set_incremental(ecc_metric* m, int enable)
     if (!m) return fail(ECC_ERR_INVALID_ARGUMENT, "metric is null");
     m->incremental = enable ? 1 : 0;
     m->cache.valid = false;
+    return ECC_OK;
+}
+
+// The base columns of the form families' pose-delta calls kept between calls (ecc_form_call.h: form_base_kept).
+ECC_EXPORT int ecc_metric_set_form_incremental(ecc_metric* m, int enable)
+{
+    if (!m) return fail(ECC_ERR_INVALID_ARGUMENT, "metric is null");
+    m->form_incremental = enable ? 1 : 0;
+    ecc_drop_form_base(m);
+    return ECC_OK;
+}
+
+ECC_EXPORT int ecc_metric_last_form_base_pairs(const ecc_metric* m, int64_t* pairs)
+{
+    if (!m || !pairs) return fail(ECC_ERR_INVALID_ARGUMENT, "null argument");
+    *pairs = m->last_form_base_pairs;
     return ECC_OK;
 }
 
@@ -335,7 +355,7 @@ ECC_EXPORT int ecc_metric_device_bytes(const ecc_metric* m, int64_t* paired_byte
                           m->records_d.bytes() + m->cache_values_d.bytes() + m->pose_PinvTs_d.bytes() + m->pose_Cs_d.bytes() +
                           m->pose_idx_d.bytes() + m->pose_values_d.bytes() + m->pose_records_d.bytes() + m->pose_partial_d.bytes() +
                           m->pose_lists_d.bytes() + m->transform_radii_d.bytes() + m->sum_scratch_d.bytes() + m->sum_d.bytes() +
-                          m->map_fixed_d.bytes() + m->map_planes_d.bytes() + m->map_slot_d.bytes();
+                          m->map_fixed_d.bytes() + m->map_planes_d.bytes() + m->map_slot_d.bytes() + m->form_base_d.bytes();
     if (paired_bytes) *paired_bytes = m->paired_d.bytes();
     if (quad_bytes) *quad_bytes = m->quads_d.bytes();
     if (other_bytes) *other_bytes = other;

@@ -48,7 +48,8 @@ PairForm robust_form(int loss, float delta, double* values, double* inlier_masse
                 // would reward pushing samples into the tails
                 values[k] = totals[0] / (double)count;
                 if (inlier_masses) inlier_masses[k] = totals[1] / (double)count;
-            }};
+            },
+            ecc_form_base::ROBUST, loss, delta, 0.f};
 }
 }  // namespace ecc_internal
 

@@ -50,7 +50,8 @@ PairForm variance_form(float floor, double* values, double* mean_weights)
                 const bool none = totals[1] == 0.0;
                 values[k] = none ? 0.0 : totals[0] / totals[1];
                 if (mean_weights) mean_weights[k] = none ? 0.0 : totals[1] / (double)count;
-            }};
+            },
+            ecc_form_base::VARIANCE, 0, 0.f, floor};
 }
 }  // namespace ecc_internal
 

@@ -52,7 +52,8 @@ PairForm variance_robust_form(int loss, float delta, float floor, double* values
                 values[k] = none ? 0.0 : totals[0] / totals[1];
                 if (mean_weights) mean_weights[k] = none ? 0.0 : totals[1] / (double)count;
                 if (inlier_masses) inlier_masses[k] = none ? 0.0 : totals[2] / totals[1];
-            }};
+            },
+            ecc_form_base::VARIANCE_ROBUST, loss, delta, floor};
 }
 
 }  // namespace ecc_internal

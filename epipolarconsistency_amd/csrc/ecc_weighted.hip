@@ -40,7 +40,8 @@ PairForm weighted_form(double* values, double* coverages)
                 const bool none = totals[1] == 0.0;
                 values[k] = none ? 0.0 : totals[0] / totals[1];
                 if (coverages) coverages[k] = none ? 0.0 : totals[1] / (double)count;
-            }};
+            },
+            ecc_form_base::WEIGHTED, 0, 0.f, 0.f};
 }
 }  // namespace ecc_internal
 

@@ -45,7 +45,8 @@ PairForm weighted_robust_form(int loss, float delta, double* value, double* cove
                 value[k] = none ? 0.0 : totals[0] / totals[1];
                 if (coverage) coverage[k] = none ? 0.0 : totals[1] / (double)count;
                 if (inlier_mass) inlier_mass[k] = none ? 0.0 : totals[2] / totals[1];
-            }};
+            },
+            ecc_form_base::WEIGHTED_ROBUST, loss, delta, 0.f};
 }
 
 }  // namespace ecc_internal

@@ -1191,6 +1191,46 @@ int ecc_metric_evaluate_variance_robust_transforms(ecc_metric* m, int n_source, 
                                                    float floor, double* values, double* mean_weights, double* inlier_masses, float* pair_terms);
 double ecc_host_variance_robust_scale(const float* pair_terms, int64_t n_pairs, double k);
 
+/* The form batches' base columns kept between pose-delta calls (opt-in, default off; not in the reference; csrc/ecc_form_base.h,
+ * csrc/ecc_form_call.h, csrc/form_base_scatter_kernel.hip).  This block supersedes the "Not built" sentences of the
+ * weighted, robust, weighted-robust, variance and variance-robust blocks above where they name kept base columns: they are built
+ * here, for these five calls.
+ * ecc_metric_evaluate_weighted_pose_deltas, _robust_pose_deltas, _weighted_robust_pose_deltas, _variance_pose_deltas and
+ * _variance_robust_pose_deltas begin every call with the form's T columns over ALL n (n - 1) / 2 pairs of the current matrices, although
+ * their caller -- a pose optimiser: set one view, probe -- changed one view since its previous call, or none.  With the mode on the
+ * metric keeps those columns in a buffer of its own (T columns of n (n - 1) / 2 float32; ecc_metric_device_bytes counts it under
+ * other_bytes; the all-pairs, list, map, transform and Gram calls use other scratch and neither see nor disturb it), together with
+ * what they belong to: the form, T and S; loss, delta and floor bitwise, as the form has them; the sampling mode the call resolved
+ * and the scalar parameters of its launch (the object radius it resolved, dkappa, the polynomial tolerance, use_corr); n_views and
+ * n_dtrs; the n x 12 matrices.  The next of the five calls, in this order:
+ *   miss     nothing is kept; one of these fields other than the matrices differs (another form is a miss: ONE form's columns are
+ *            kept at a time); the resolved mode is ECC_SAMPLING_REFERENCE; more than min(ECC_POSE_BATCH_MAX_MOVED, n_views / 4) views
+ *            differ bitwise from the kept matrices; view 0 differs and the automatic object radius moved with it.  Everything is
+ *            evaluated as with the mode off, into the kept buffer, and the key and the matrices are taken.  Under
+ *            ECC_SAMPLING_REFERENCE -- chosen, or resolved by ECC_SAMPLING_AUTO for up to ECC_SAMPLING_AUTO_REFERENCE_PAIRS pairs --
+ *            NOTHING IS EVER KEPT: that mode reads the callers' slabs, which are current without ecc_metric_refresh_dtrs.
+ *   hit      no view differs: no record launch and no pair launch for the base.
+ *   refresh  1 <= c <= the limit views differ: ONE pose grid of c columns (the changed views at their current matrices over the
+ *            current matrices: the launches of a batch of one pose) and one copy launch from its T columns to the pairs' all-pairs
+ *            positions in the kept columns.  A grid entry has the bits of the all-pairs launch for the same two matrices -- the
+ *            contract of the batches themselves -- so the refreshed columns have the bits of a full evaluation.
+ * Then the call proceeds as with the mode off, reading the kept columns: the batches, their segmented sums, the sequential route for
+ * what the batches do not take.  EVERY VALUE A CALL RETURNS HAS THE BITS OF THE SAME CALL WITH THE MODE OFF
+ * (tests/test_gpu_form_incremental.py).  With the mode off nothing changes: the same launches with the same arguments and scratch.
+ * The kept columns are dropped by ecc_metric_set_form_incremental itself (any call of it), ecc_metric_refresh_dtrs (any non-empty
+ * range), ecc_metric_set_params, ecc_metric_set_sampling, ecc_debug_set_poly_tolerance and a change of n_views in
+ * ecc_metric_set_projections.  As with every metric here, slab contents changed WITHOUT ecc_metric_refresh_dtrs are not seen by the
+ * polynomial and per-sample modes, kept columns or not.
+ * ecc_metric_last_form_base_pairs: how many BASE pairs the last *_pose_deltas call of any of the five forms evaluated --
+ * n (n - 1) / 2 with the mode off or on a miss, c (n - 1) - c (c - 1) / 2 when c views were refreshed, 0 on a hit, and 0 when the call
+ * computed no base columns at all (ecc_metric_set_pose_batching(m, 0)); a call that returns before its lists are looked at
+ * (n_poses < 1, an argument error) leaves the count as it was.
+ * Errors: m == NULL, and pairs == NULL for the counter: ECC_ERR_INVALID_ARGUMENT.
+ * Not built: the kept columns for the all-pairs form calls, the index-list, transform and map calls and ecc_metric_evaluate_gradient;
+ * more than one kept form at a time; range, group and RCCL forms; a default-on or automatic mode. */
+int ecc_metric_set_form_incremental(ecc_metric* m, int enable);
+int ecc_metric_last_form_base_pairs(const ecc_metric* m, int64_t* pairs);
+
 /* Where the robust loss rejects IN SIGMA UNITS (csrc/ecc_variance_robust_map.hip, csrc/variance_robust_map_kernel.hip):
  * the map of ecc_metric_evaluate_variance_robust, and the held map as the next pass's variance fields.  This block supersedes the
  * "Not built" sentence of the block above where it names the maps of that form.  A map of the raw-residual loss
