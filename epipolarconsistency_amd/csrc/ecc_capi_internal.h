@@ -553,6 +553,18 @@ inline void set_channel_strides(const ecc_metric* m, Params* g)
     g->quad_channel_bytes = n * m->quad_floats * (int64_t)sizeof(float);
 }
 
+// The planes of the metric's map call, for the three map forms (g: any parameter struct of ecc_robust_map.h): the fixed-point
+// planes, the plane table, a plane's cells (ecc_robust_map_plane_cells: one per float of a slab) and the REJ planes behind all
+// HITS planes.
+template <class Params>
+inline void set_map_planes(const ecc_metric* m, Params* g)
+{
+    g->planes = m->map_fixed_d.ptr;
+    g->slot_of = m->map_slot_d.ptr;
+    g->plane_cells = ecc_layout_floats(m->n_alpha, m->n_t);
+    g->rej_cells = (int64_t)m->map_n_mapped * g->plane_cells;
+}
+
 // launch(stream) on the context's stream between its timing events (ecc_ctx_enable_timing).
 template <class Launch>
 inline hipError_t launch_timed(ecc_ctx* ctx, Launch&& launch)

@@ -1,10 +1,12 @@
 // ecc_pair_forms.h -- the loop skeleton shared by the pair-form kernels (gram_kernel.hip, view_coeff_kernel.hip,
-// view_hessian_kernel.hip, weighted_kernel.hip, robust_kernel.hip), stated once.
+// view_hessian_kernel.hip, weighted_kernel.hip, variance_kernel.hip, and through ecc_loss_forms.h robust_kernel.hip,
+// weighted_robust_kernel.hip, variance_robust_kernel.hip and the three map kernels), stated once.
 //
 // A FORM of the pair metric is pairs_kernel's evaluation of one pair per wave -- the record in scalar registers, the dispatch over
 // the record's degree and the slab size, the four sample positions of a kappa step, per-lane float64 sums in trip order, the wave
 // tree -- with its own gathers and products behind the four positions.  The frames below own everything up to the four taps of a
-// kappa step; a form is a small struct in its kernel file that owns what is gathered there and what is added.  Its members:
+// kappa step; a form is a small struct in its kernel file that owns what is gathered there and what is added (the forms under a
+// robust loss, which an evaluation kernel and its map kernel share, are templates in ecc_loss_forms.h).  Its members:
 //   poly_begin(sv0, sv1, rel_sign, w06_dkappa)                before a polynomial loop: what the form derives from the loop's uniforms
 //   poly_trip(sv0, sv1, t0p, t1p, t0m, t1m, rel_sign, w06_dkappa)    one kappa step of a polynomial loop: SampleTaps, UNSIGNED samples
 //   poly_end(rel_sign)                                        after a polynomial loop

@@ -1,7 +1,9 @@
 // ecc_robust_map.h -- what the three map kernels (robust_map_kernel.hip, weighted_robust_map_kernel.hip,
 // variance_robust_map_kernel.hip) and their host files (ecc_robust_map.hip, ecc_weighted_robust_map.hip,
 // ecc_variance_robust_map.hip) share: the parameters of the map launches, the geometry of the planes, the
-// deposits (for the kernel files) and the launch sequence of a map call (for the host files).
+// deposits, the deposit policy MapDeposits of the loss forms (ecc_loss_forms.h), the feedback kernels' rule and the map launches'
+// argument check (for the kernel files) and the launch sequence of a map call (for the host files) (DESIGN.md 4.24, 4.25, 4.31,
+// 4.33).
 //
 // The map of a view is two planes, HITS and REJ, of unsigned 64-bit fixed point with quantum 2^-32.  On the device a plane has the
 // geometry of the view's slab (ecc_layout.h): (n_alpha + 2) rows of `pitch` cells, cell (row, bin) for the padded element
@@ -156,6 +158,96 @@ struct MapPlanes {
         deposit_footprint(hits, rej_cells, r0 * pitch + b0, r1 * pitch + b0, r0 * pitch + b1, r1 * pitch + b1, fx, fy, w, mu);
     }
 };
+
+// The deposit policy of a map kernel: the base a loss form (ecc_loss_forms.h) takes in NoMap's place.  The hooks run behind the
+// sums of a trip with the trip's four taps, the loss weights w of the + and the - sample and the factor mu of their deposits (the
+// literal 1.0f for the maps in count units: it reaches deposit_footprint as a constant).  A sample is deposited into both views of
+// its pair, each with its own footprint.
+struct MapDeposits : MapPlanes {
+    unsigned long long *hits0, *hits1;  // the HITS plane of the pair's two views, null: not mapped (wave-uniform)
+
+    template <class G>
+    __device__ __forceinline__ void map_begin(const G& g, const EccPairParams& p, int iD0, int iD1)
+    {
+        const auto plane_of = [&g](int iD) -> unsigned long long* {
+            const int slot = __builtin_amdgcn_readfirstlane(g.slot_of[iD]);
+            return slot < 0 ? nullptr : g.planes + (long long)slot * g.plane_cells;
+        };
+        hits0 = plane_of(iD0);
+        hits1 = plane_of(iD1);
+        rej_cells = g.rej_cells;
+        pitch = (unsigned)p.pitch;
+        last_cell = (unsigned)(g.plane_cells - 1);
+    }
+
+    // a polynomial loop's taps: the byte offset inside the row-paired copy is the cell's
+    __device__ __forceinline__ void map_poly(const SampleTap t0p, const SampleTap t1p, const SampleTap t0m, const SampleTap t1m, float w_p,
+                                             float w_m, float mu_p, float mu_m) const
+    {
+        if (hits0) {
+            deposit_at(hits0, t0p.off >> 3, t0p.fx, t0p.fy, w_p, mu_p);
+            deposit_at(hits0, t0m.off >> 3, t0m.fx, t0m.fy, w_m, mu_m);
+        }
+        if (hits1) {
+            deposit_at(hits1, t1p.off >> 3, t1p.fx, t1p.fy, w_p, mu_p);
+            deposit_at(hits1, t1m.off >> 3, t1m.fx, t1m.fy, w_m, mu_m);
+        }
+    }
+
+    // an exact loop's taps: the offset inside the copy of the layout PITCH4, decoded
+    template <int PITCH4>
+    __device__ __forceinline__ void map_exact(const SlabView sv0, const SlabView sv1, const LineTap t0p, const LineTap t1p, const LineTap t0m,
+                                              const LineTap t1m, float w_p, float w_m, float mu_p, float mu_m) const
+    {
+        if (hits0) {
+            deposit_at(hits0, cell_of_offset<PITCH4>(line_tap_offset(t0p, sv0)), t0p.fx, t0p.fy, w_p, mu_p);
+            deposit_at(hits0, cell_of_offset<PITCH4>(line_tap_offset(t0m, sv0)), t0m.fx, t0m.fy, w_m, mu_m);
+        }
+        if (hits1) {
+            deposit_at(hits1, cell_of_offset<PITCH4>(line_tap_offset(t1p, sv1)), t1p.fx, t1p.fy, w_p, mu_p);
+            deposit_at(hits1, cell_of_offset<PITCH4>(line_tap_offset(t1m, sv1)), t1m.fx, t1m.fy, w_m, mu_m);
+        }
+    }
+
+    // the reference loop's taps: the clamped cells of the plain sampler
+    __device__ __forceinline__ void map_plain(const EccPairParams& p, const PlainTap t0p, const PlainTap t1p, const PlainTap t0m,
+                                              const PlainTap t1m, float w_p, float w_m, float mu_p, float mu_m) const
+    {
+        if (hits0) {
+            deposit_plain(hits0, p, t0p, w_p, mu_p);
+            deposit_plain(hits0, p, t0m, w_m, mu_m);
+        }
+        if (hits1) {
+            deposit_plain(hits1, p, t1p, w_p, mu_p);
+            deposit_plain(hits1, p, t1m, w_m, mu_m);
+        }
+    }
+};
+
+// What the three feedback kernels share: the padded element e of view `view`'s slab -> the bin it replicates -> the mean loss
+// weight of the samples that reached the bin, max(0, 1 - gain * REJ / HITS) on the held float planes, every operation an IEEE
+// float64 one; 1.0f where fewer than min_hits reached it.
+__device__ __forceinline__ float map_mean_weight(const float* __restrict__ hits, const float* __restrict__ rejected, long long e, long long view,
+                                                 int n_alpha, int n_t, int pitch, float min_hits, float gain)
+{
+    const long long bins = (long long)n_alpha * n_t;
+    const int row = (int)(e / pitch), col = (int)(e - (long long)row * pitch);
+    const int i = min(max(row - 1, 0), n_alpha - 1), j = min(max(col - 1, 0), n_t - 1);
+    const long long bin = view * bins + (long long)j * n_alpha + i;
+    const float h = hits[bin], r = rejected[bin];
+    float mu = 1.0f;
+    if (!(h < min_hits)) mu = (float)fmax(0.0, 1.0 - (double)gain * ((double)r / (double)h));
+    return mu;
+}
+
+// the argument check the three map launch functions share, behind the loss's own (ecc_loss_forms.h): the planes and their table
+// there, the REJ planes behind all HITS planes, a plane of the launch's padded geometry and addressable by an unsigned cell
+template <class G>
+inline bool map_launch_ok(const EccPairParams& p, const G& g)
+{
+    return !(!g.planes || !g.slot_of || g.rej_cells < g.plane_cells || g.plane_cells != ecc_robust_map_plane_cells(p.n_alpha, p.n_t) ||
+             g.plane_cells >= ((int64_t)1 << 31));
+}
 
 }  // namespace
 #endif

@@ -1,5 +1,5 @@
-// ecc_robust_weight.h -- the IRLS weight of a residual under a robust loss, stated once for the kernels that take one
-// (robust_kernel.hip, weighted_robust_kernel.hip).  Every loss is rho(d) = w(d) d^2 with w in (0, 1], one float32 operation per line,
+// ecc_robust_weight.h -- the IRLS weight of a residual under a robust loss, stated once for the forms that take one (RobustForm
+// and FieldLossForm under LineWeightRule, ecc_loss_forms.h: the robust and weighted-robust kernel files and their maps).  Every loss is rho(d) = w(d) d^2 with w in (0, 1], one float32 operation per line,
 // nothing contracted but the fmaf, the division the IEEE one (the head of robust_kernel.hip has the table).
 #ifndef ECC_ROBUST_WEIGHT_H
 #define ECC_ROBUST_WEIGHT_H

@@ -1,6 +1,6 @@
 // ecc_studentised_weight.h -- the weight of one sample under inverse-variance weights and a robust loss in sigma units, stated once
-// for variance_robust_kernel.hip (which sums om and f) and variance_robust_map_kernel.hip (which also deposits 1 - w)
-// (DESIGN.md 4.30, 4.31).  Device code only; every line one float32 operation:
+// for variance_robust_kernel.hip (which sums om and f) and variance_robust_map_kernel.hip (which also deposits 1 - w): both take it
+// through FieldLossForm under StudentisedRule, ecc_loss_forms.h.  Device code only; every line one float32 operation:
 //   s   = V_a + V_b
 //   sc  = s < floor ? floor : s
 //   om  = 1.0f / sc                       the correctly rounded IEEE division

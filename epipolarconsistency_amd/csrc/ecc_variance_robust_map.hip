@@ -30,10 +30,7 @@ PairForm variance_robust_map_form(int loss, float delta, float floor, double* va
         g.loss = loss;
         g.delta = delta;
         g.inv_delta = (float)(1.0 / (double)delta);  // formed here, on the host, in float64 (as variance_robust_form does)
-        g.planes = m->map_fixed_d.ptr;
-        g.slot_of = m->map_slot_d.ptr;
-        g.plane_cells = ecc_robust_map_plane_cells(m->n_alpha, m->n_t);
-        g.rej_cells = (int64_t)m->map_n_mapped * g.plane_cells;
+        set_map_planes(m, &g);
         return launch_timed(m->ctx, [&](hipStream_t s) { return ecc_launch_pairs_variance_robust_map(&p, &g, s); });
     };
     return f;

@@ -20,8 +20,9 @@
 //   r = (float)(raw / count), the mean squared raw residual: no loss and no delta in it (ecc_host_robust_scale takes delta from it),
 // a pair whose loops ran no trip (count == 0) has {0, 1, 0}; three columns, c and u summed by sum_gram_kernel (ecc_robust.hip).
 // Both kernels run wholly on the frames of ecc_pair_forms.h: form_main_sums and form_reference_sums with every piece
-// below them.  RobustForm's trip gathers the 4 data footprints of a kappa step, forms the two residuals and their weights, and adds the
-// value term, the weight mass, the raw squares and 2.0 to four per-lane float64 sums in trip order.  loss and delta are launch-uniform
+// below them.  The trips are RobustForm<EccRobustParams, NoMap>'s (ecc_loss_forms.h, shared with robust_map_kernel.hip): a trip gathers
+// the 4 data footprints of a kappa step, forms the two residuals and their weights, and adds the value term, the weight mass, the raw
+// squares and 2.0 to four per-lane float64 sums in trip order; store_robust there makes the columns.  loss and delta are launch-uniform
 // kernel arguments and the loss a uniform select (a scalar branch around one division), not a template parameter: three times the
 // instantiations of every loop for the same registers.  Plain vector loads and stores only: no atomics, no inline
 // assembly.
@@ -32,88 +33,9 @@
 #include <float.h>
 
 #include "ecc_layout.h"
-#include "ecc_pair_forms.h"
-#include "ecc_robust_weight.h"
+#include "ecc_loss_forms.h"
 
 namespace {
-
-// the four per-lane sums: the value, the weight mass, the raw squares, the sample count
-enum { VALUE, MASS, RAW, COUNT, ROBUST_SUMS };
-
-// (RobustLoss, the launch-uniform part of the loss, and robust_weight, w(d), are in ecc_robust_weight.h: weighted_robust_kernel.hip
-// takes the same ones)
-
-// the trips of the three loop kinds (ecc_pair_forms.h): 4 gathers, the residuals of the + and the - sample, their weights, the sums
-struct RobustForm : PairFormDefaults {
-    const EccRobustParams& g;
-    double (&acc)[ROBUST_SUMS];
-    RobustLoss L;         // the launch-uniform loss, in scalar registers
-    GlobalFloats d0, d1;  // the reference loop's slabs
-
-    __device__ __forceinline__ RobustForm(const EccRobustParams& g, double (&acc)[ROBUST_SUMS]) : g(g), acc(acc) {}
-
-    __device__ __forceinline__ void begin(const EccPairParams&, int, int)
-    {
-        L = {__builtin_amdgcn_readfirstlane(g.loss), uniformf(g.delta), uniformf(g.inv_delta)};
-    }
-
-    // the sums of a trip beside its value
-    __device__ __forceinline__ void add(float value, float w_p, float w_m, float dp, float dm)
-    {
-        acc[VALUE] += (double)value;
-        acc[MASS] += (double)(w_p + w_m);
-        acc[RAW] += (double)(dp * dp) + (double)(dm * dm);
-        acc[COUNT] += 2.0;
-    }
-
-    __device__ __forceinline__ void poly_trip(const SlabView sv0, const SlabView sv1, const SampleTap t0p, const SampleTap t1p,
-                                              const SampleTap t0m, const SampleTap t1m, float rel_sign, float w06_dkappa)
-    {
-        const float v0p = sample_tap_value(sv0.origin, t0p), v1p = sample_tap_value(sv1.origin, t1p);
-        const float v0m = sample_tap_value(sv0.origin, t0m), v1m = sample_tap_value(sv1.origin, t1m);
-        const float dp = fmaf(v1p, rel_sign, v0p), dm = fmaf(v1m, rel_sign, v0m);
-        const float w_p = robust_weight(L, dp), w_m = robust_weight(L, dm);
-        add(fmaf(w_p * dp, dp, (w_m * dm) * dm) * w06_dkappa, w_p, w_m, dp, dm);
-    }
-
-    template <bool DERIV, int PITCH4>
-    __device__ __forceinline__ void exact_trip(const SlabView, const SlabView, const LineTap t0p, const LineTap t1p, const LineTap t0m,
-                                               const LineTap t1m, float w06, float dkappa)
-    {
-        const auto tap = [](const LineTap& t) { return line_tap_finish<DERIV>(line_footprint((GlobalBytes)t.ptr, 0u), t); };
-        const float v0p = tap(t0p), v1p = tap(t1p), v0m = tap(t0m), v1m = tap(t1m);
-        const float dp = v0p - v1p, dm = v0m - v1m;
-        const float w_p = robust_weight(L, dp), w_m = robust_weight(L, dm);
-        add((((w_p * dp) * dp + (w_m * dm) * dm) * w06) * dkappa, w_p, w_m, dp, dm);  // ref: ...RadonIntermediate.cu:112,269,254
-    }
-
-    __device__ __forceinline__ void reference_begin(const EccPairParams& p, int iD0, int iD1)
-    {
-        d0 = (GlobalFloats)p.slabs[iD0];
-        d1 = (GlobalFloats)p.slabs[iD1];
-        begin(p, iD0, iD1);
-    }
-
-    __device__ __forceinline__ void reference_trip(const EccPairParams& p, bool deriv, const PlainTap t0p, const PlainTap t1p,
-                                                   const PlainTap t0m, const PlainTap t1m, float w06, float dkappa)
-    {
-        const float v0p = plain_tap_value(t0p, d0, p.pitch, p.n_alpha, p.n_t, deriv), v1p = plain_tap_value(t1p, d1, p.pitch, p.n_alpha, p.n_t, deriv);
-        const float v0m = plain_tap_value(t0m, d0, p.pitch, p.n_alpha, p.n_t, deriv), v1m = plain_tap_value(t1m, d1, p.pitch, p.n_alpha, p.n_t, deriv);
-        const float dp = v0p - v1p, dm = v0m - v1m;
-        const float w_p = robust_weight(L, dp), w_m = robust_weight(L, dm);
-        const float consistency = ((w_p * dp) * dp + (w_m * dm) * dm) * w06;  // ref: ...RadonIntermediate.cu:112,254
-        add(consistency * dkappa, w_p, w_m, dp, dm);                          // ref: ...RadonIntermediate.cu:269
-    }
-};
-
-// The pair's three entries from the wave's sums (lane 0): c into column 0, u into column 1, r into column 2.
-__device__ __forceinline__ void store_robust(const EccRobustParams& g, long long local, const double (&acc)[ROBUST_SUMS])
-{
-    const bool any = acc[COUNT] > 0.0;
-    g.values[local] = (float)acc[VALUE];  // pair_value<false>; no trip: 0
-    g.values[g.col_stride + local] = any ? (float)(acc[MASS] / acc[COUNT]) : 1.0f;
-    g.values[2 * g.col_stride + local] = any ? (float)(acc[RAW] / acc[COUNT]) : 0.0f;
-}
 
 // Registers: the 4 gathers of a kappa step as in pairs_kernel, 8 accumulator registers; tests/test_robust_abi.py pins
 // the plan and what was built.
@@ -121,7 +43,7 @@ template <bool DERIV>
 __global__ __launch_bounds__(PK_MAIN_THREADS) void pairs_robust_kernel(EccPairParams p, EccRobustParams g)
 {
     double acc[ROBUST_SUMS] = {0.0, 0.0, 0.0, 0.0};
-    RobustForm form(g, acc);
+    RobustForm<EccRobustParams, NoMap> form(g, acc);
     long long local;
     if (form_main_sums<DERIV>(p, form, acc, local)) store_robust(g, local, acc);
 }
@@ -131,7 +53,7 @@ template <int SPLIT>
 __global__ __launch_bounds__(PK_THREADS) void pairs_robust_reference_kernel(EccPairParams p, EccRobustParams g)
 {
     double acc[ROBUST_SUMS] = {0.0, 0.0, 0.0, 0.0};
-    RobustForm form(g, acc);
+    RobustForm<EccRobustParams, NoMap> form(g, acc);
     long long local;
     if (form_reference_sums<SPLIT>(p, form, acc, local)) store_robust(g, local, acc);
 }
@@ -144,9 +66,7 @@ __global__ __launch_bounds__(PK_THREADS) void pairs_robust_reference_kernel(EccP
 extern "C" hipError_t ecc_launch_pairs_robust(const EccPairParams* p, const EccRobustParams* g, hipStream_t stream)
 {
     if (p->count <= 0) return hipSuccess;
-    if (p->use_corr || p->record_slots || p->skip_enabled || !g->values || g->col_stride < p->count || (g->col_stride & 3) ||
-        g->loss < ECC_ROBUST_HUBER || g->loss > ECC_ROBUST_GEMAN_MCCLURE || !(g->delta > 0.f))
-        return hipErrorInvalidValue;
+    if (!loss_launch_ok(*p, *g)) return hipErrorInvalidValue;
     return launch_pair_form(*p, *g, stream, pairs_robust_reference_kernel<4>, pairs_robust_reference_kernel<1>, pairs_robust_kernel<true>,
                             pairs_robust_kernel<false>);
 }

@@ -33,138 +33,40 @@
 // bits and u is 1.0f; both give pairs_kernel's bits; all V and the floor x 4 with delta x 1/2 leave thr and q * om * q as they are
 // and quarter om, so every column is a quarter of itself, exactly.
 // Both kernels run wholly on the frames of ecc_pair_forms.h: form_main_sums and form_reference_sums with every piece
-// below them.  VarianceRobustForm's trip is VarianceForm's 8 gathers and reciprocals followed by the studentised weights; five
-// per-lane float64 sums in trip order.  loss, delta and floor are launch-uniform kernel arguments and the loss a uniform select, not
-// a template parameter; the weight itself is ecc_studentised_weight.h's, shared with the map of this form
-// (variance_robust_map_kernel.hip).  Plain vector loads and stores only: no atomics, no inline assembly, no LDS in the main kernels.
+// below them.  The trips are FieldLossForm<EccVarianceRobustParams, StudentisedRule, NoMap>'s (ecc_loss_forms.h, shared with
+// variance_robust_map_kernel.hip and, under another rule, the weighted-robust files): the 8 gathers of VarianceForm followed by the
+// studentised weights; five per-lane float64 sums in trip order; store_field_loss there makes the columns.  loss, delta and floor are
+// launch-uniform kernel arguments and the loss a uniform select, not a template parameter; the weight itself is
+// ecc_studentised_weight.h's.  Plain vector loads and stores only: no atomics, no inline assembly, no LDS in the main kernels.
 // Not here (include/ecc_hip.h): base columns kept between calls; range, group and RCCL forms; the correlation cost; a
 // covariance-aware model for derivative data.
 #include <hip/hip_runtime.h>
 #include <float.h>
 
 #include "ecc_layout.h"
-#include "ecc_pair_forms.h"
-#include "ecc_studentised_weight.h"
+#include "ecc_loss_forms.h"
 
 namespace {
-
-// the five per-lane sums: the value, the weight mass, the mass the loss keeps, the squared studentised residuals, the sample count
-enum { VALUE, MASS, KEPT, RAW, COUNT, VARIANCE_ROBUST_SUMS };
-
-// the trips of the three loop kinds (ecc_pair_forms.h): the 4 data gathers and, at the same taps of the variance copies, 4 more; the
-// residuals of the + and the - sample, their studentised weights, the sums
-struct VarianceRobustForm : PairFormDefaults {
-    const EccVarianceRobustParams& g;
-    double (&acc)[VARIANCE_ROBUST_SUMS];
-    StudentisedLoss L;              // the launch-uniform loss and floor, in scalar registers
-    GlobalBytes w0, w1;             // the variance copies of the loop's two views (wave-uniform)
-    GlobalFloats d0, d1, rw0, rw1;  // the reference loop's slabs: data and variances
-
-    __device__ __forceinline__ VarianceRobustForm(const EccVarianceRobustParams& g, double (&acc)[VARIANCE_ROBUST_SUMS]) : g(g), acc(acc) {}
-
-    __device__ __forceinline__ void begin(const EccPairParams&, int, int)
-    {
-        L = {__builtin_amdgcn_readfirstlane(g.loss), uniformf(g.delta), uniformf(g.inv_delta), uniformf(g.floor)};
-    }
-
-    // the sums of a trip beside its value
-    __device__ __forceinline__ void add(float value, const StudentisedWeight p, const StudentisedWeight m, float dp, float dm)
-    {
-        acc[VALUE] += (double)value;
-        acc[MASS] += (double)(p.om + m.om);
-        acc[KEPT] += (double)(p.f + m.f);
-        acc[RAW] += (double)(p.om * (dp * dp)) + (double)(m.om * (dm * dm));
-        acc[COUNT] += 2.0;
-    }
-
-    __device__ __forceinline__ void poly_begin(const SlabView sv0, const SlabView sv1, float, float)
-    {
-        w0 = sv0.origin + g.paired_channel_bytes, w1 = sv1.origin + g.paired_channel_bytes;
-    }
-
-    __device__ __forceinline__ void poly_trip(const SlabView sv0, const SlabView sv1, const SampleTap t0p, const SampleTap t1p,
-                                              const SampleTap t0m, const SampleTap t1m, float rel_sign, float w06_dkappa)
-    {
-        const float v0p = sample_tap_value(sv0.origin, t0p), v1p = sample_tap_value(sv1.origin, t1p);
-        const float v0m = sample_tap_value(sv0.origin, t0m), v1m = sample_tap_value(sv1.origin, t1m);
-        const float s0p = sample_tap_value(w0, t0p), s1p = sample_tap_value(w1, t1p);  // unsigned, whatever the folds
-        const float s0m = sample_tap_value(w0, t0m), s1m = sample_tap_value(w1, t1m);
-        const float dp = fmaf(v1p, rel_sign, v0p), dm = fmaf(v1m, rel_sign, v0m);
-        const StudentisedWeight p = studentised_weight(L, s0p, s1p, dp), m = studentised_weight(L, s0m, s1m, dm);
-        add(fmaf(p.f * dp, dp, (m.f * dm) * dm) * w06_dkappa, p, m, dp, dm);
-    }
-
-    template <int PITCH4>
-    __device__ __forceinline__ void exact_begin(const SlabView sv0, const SlabView sv1)
-    {
-        w0 = sv0.origin + channel_bytes<PITCH4>(g), w1 = sv1.origin + channel_bytes<PITCH4>(g);
-    }
-
-    template <bool DERIV, int PITCH4>
-    __device__ __forceinline__ void exact_trip(const SlabView sv0, const SlabView sv1, const LineTap t0p, const LineTap t1p, const LineTap t0m,
-                                               const LineTap t1m, float w06, float dkappa)
-    {
-        const unsigned o0p = line_tap_offset(t0p, sv0), o1p = line_tap_offset(t1p, sv1);
-        const unsigned o0m = line_tap_offset(t0m, sv0), o1m = line_tap_offset(t1m, sv1);
-        const float v0p = line_tap_finish<DERIV>(line_footprint(sv0.origin, o0p), t0p), v1p = line_tap_finish<DERIV>(line_footprint(sv1.origin, o1p), t1p);
-        const float v0m = line_tap_finish<DERIV>(line_footprint(sv0.origin, o0m), t0m), v1m = line_tap_finish<DERIV>(line_footprint(sv1.origin, o1m), t1m);
-        const float s0p = line_tap_finish<false>(line_footprint(w0, o0p), t0p), s1p = line_tap_finish<false>(line_footprint(w1, o1p), t1p);
-        const float s0m = line_tap_finish<false>(line_footprint(w0, o0m), t0m), s1m = line_tap_finish<false>(line_footprint(w1, o1m), t1m);
-        const float dp = v0p - v1p, dm = v0m - v1m;
-        const StudentisedWeight p = studentised_weight(L, s0p, s1p, dp), m = studentised_weight(L, s0m, s1m, dm);
-        add((((p.f * dp) * dp + (m.f * dm) * dm) * w06) * dkappa, p, m, dp, dm);  // ref: ...RadonIntermediate.cu:112,269,254
-    }
-
-    __device__ __forceinline__ void reference_begin(const EccPairParams& p, int iD0, int iD1)
-    {
-        d0 = (GlobalFloats)p.slabs[iD0], d1 = (GlobalFloats)p.slabs[iD1];
-        rw0 = (GlobalFloats)p.slabs[(long long)p.n_views + iD0], rw1 = (GlobalFloats)p.slabs[(long long)p.n_views + iD1];
-        begin(p, iD0, iD1);
-    }
-
-    __device__ __forceinline__ void reference_trip(const EccPairParams& p, bool deriv, const PlainTap t0p, const PlainTap t1p,
-                                                   const PlainTap t0m, const PlainTap t1m, float w06, float dkappa)
-    {
-        const float v0p = plain_tap_value(t0p, d0, p.pitch, p.n_alpha, p.n_t, deriv), v1p = plain_tap_value(t1p, d1, p.pitch, p.n_alpha, p.n_t, deriv);
-        const float v0m = plain_tap_value(t0m, d0, p.pitch, p.n_alpha, p.n_t, deriv), v1m = plain_tap_value(t1m, d1, p.pitch, p.n_alpha, p.n_t, deriv);
-        const float s0p = plain_tap_value(t0p, rw0, p.pitch, p.n_alpha, p.n_t, false), s1p = plain_tap_value(t1p, rw1, p.pitch, p.n_alpha, p.n_t, false);
-        const float s0m = plain_tap_value(t0m, rw0, p.pitch, p.n_alpha, p.n_t, false), s1m = plain_tap_value(t1m, rw1, p.pitch, p.n_alpha, p.n_t, false);
-        const float dp = v0p - v1p, dm = v0m - v1m;
-        const StudentisedWeight wp = studentised_weight(L, s0p, s1p, dp), wm = studentised_weight(L, s0m, s1m, dm);
-        const float consistency = ((wp.f * dp) * dp + (wm.f * dm) * dm) * w06;  // ref: ...RadonIntermediate.cu:112,254
-        add(consistency * dkappa, wp, wm, dp, dm);                              // ref: ...RadonIntermediate.cu:269
-    }
-};
-
-// The pair's four entries from the wave's sums (lane 0): c, u, k, r into columns 0 .. 3.
-__device__ __forceinline__ void store_variance_robust(const EccVarianceRobustParams& g, long long local, const double (&acc)[VARIANCE_ROBUST_SUMS])
-{
-    const bool any = acc[COUNT] > 0.0;
-    g.values[local] = (float)acc[VALUE];  // pair_value<false>; no trip: 0
-    g.values[g.col_stride + local] = any ? (float)(acc[MASS] / acc[COUNT]) : 1.0f;
-    g.values[2 * g.col_stride + local] = any ? (float)(acc[KEPT] / acc[COUNT]) : 1.0f;
-    g.values[3 * g.col_stride + local] = any ? (float)(acc[RAW] / acc[COUNT]) : 0.0f;
-}
 
 // Registers: pairs_weighted_robust_kernel's live values plus the temporaries of two square roots and two more
 // divisions, the loss and the floor in four scalar registers; tests/test_variance_robust_abi.py pins the plan and what was built.
 template <bool DERIV>
 __global__ __launch_bounds__(PK_MAIN_THREADS) void pairs_variance_robust_kernel(EccPairParams p, EccVarianceRobustParams g)
 {
-    double acc[VARIANCE_ROBUST_SUMS] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    VarianceRobustForm form(g, acc);
+    double acc[FIELD_LOSS_SUMS] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    FieldLossForm<EccVarianceRobustParams, StudentisedRule, NoMap> form(g, acc);
     long long local;
-    if (form_main_sums<DERIV>(p, form, acc, local)) store_variance_robust(g, local, acc);
+    if (form_main_sums<DERIV>(p, form, acc, local)) store_field_loss(g, local, acc);
 }
 
 // ---- ECC_SAMPLING_REFERENCE -------------------------------------------------------------------------
 template <int SPLIT>
 __global__ __launch_bounds__(PK_THREADS) void pairs_variance_robust_reference_kernel(EccPairParams p, EccVarianceRobustParams g)
 {
-    double acc[VARIANCE_ROBUST_SUMS] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    VarianceRobustForm form(g, acc);
+    double acc[FIELD_LOSS_SUMS] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    FieldLossForm<EccVarianceRobustParams, StudentisedRule, NoMap> form(g, acc);
     long long local;
-    if (form_reference_sums<SPLIT>(p, form, acc, local)) store_variance_robust(g, local, acc);
+    if (form_reference_sums<SPLIT>(p, form, acc, local)) store_field_loss(g, local, acc);
 }
 
 }  // namespace
@@ -177,9 +79,7 @@ __global__ __launch_bounds__(PK_THREADS) void pairs_variance_robust_reference_ke
 extern "C" hipError_t ecc_launch_pairs_variance_robust(const EccPairParams* p, const EccVarianceRobustParams* g, hipStream_t stream)
 {
     if (p->count <= 0) return hipSuccess;
-    if (p->use_corr || p->record_slots || p->skip_enabled || !g->values || g->col_stride < p->count || (g->col_stride & 3) ||
-        g->loss < ECC_ROBUST_HUBER || g->loss > ECC_ROBUST_GEMAN_MCCLURE || !(g->delta > 0.f))
-        return hipErrorInvalidValue;
+    if (!loss_launch_ok(*p, *g)) return hipErrorInvalidValue;
     if (!(g->floor > 0.0f) || !(g->floor <= FLT_MAX)) return hipErrorInvalidValue;
     return launch_pair_form(*p, *g, stream, pairs_variance_robust_reference_kernel<4>, pairs_variance_robust_reference_kernel<1>,
                             pairs_variance_robust_kernel<true>, pairs_variance_robust_kernel<false>);

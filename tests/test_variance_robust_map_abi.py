@@ -81,14 +81,24 @@ def test_python_layer_binds_the_calls():
 
 
 def test_the_studentised_weight_is_stated_once():
-    """both kernel files take the weight from ecc_studentised_weight.h; neither states it again."""
+    """the weight is defined once in all of csrc/, in ecc_studentised_weight.h; no .hip file and not the forms
+    header (ecc_loss_forms.h), through which both kernel files take it, states its arithmetic again."""
     csrc = os.path.join(PKG, "csrc")
+    texts = {}
+    for name in sorted(os.listdir(csrc)):
+        if name.endswith((".hip", ".h", ".cpp")):
+            with open(os.path.join(csrc, name)) as f:
+                texts[name] = f.read()
+    definition = "StudentisedWeight studentised_weight("
+    assert {name: t.count(definition) for name, t in texts.items() if definition in t} == {"ecc_studentised_weight.h": 1}
+    for name, text in texts.items():
+        if name.endswith(".hip") or name == "ecc_loss_forms.h":
+            code = text.split("#include <hip/hip_runtime.h>")[-1] if name.endswith(".hip") else text
+            assert "sqrtf(sc)" not in code, name
     for name in ("variance_robust_kernel.hip", "variance_robust_map_kernel.hip"):
-        with open(os.path.join(csrc, name)) as f:
-            text = f.read()
-        assert '#include "ecc_studentised_weight.h"' in text and "sqrtf(sc)" not in text.split("#include <hip/hip_runtime.h>")[1], name
-    with open(os.path.join(csrc, "ecc_studentised_weight.h")) as f:
-        assert f.read().count("StudentisedWeight studentised_weight(") == 1
+        assert '#include "ecc_loss_forms.h"' in texts[name] and definition not in texts[name], name
+    forms = texts["ecc_loss_forms.h"]
+    assert '#include "ecc_studentised_weight.h"' in forms and "studentised_weight(L, " in forms
 
 
 # ---- resources ---------------------------------------------------------------------------------------------------------------

@@ -7,6 +7,7 @@ import ctypes as C
 import importlib.util
 import inspect
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -135,19 +136,50 @@ def test_source_list_and_flags():
     """The new files are in the build's lists; the kernel file is built without the SLP vectoriser, like its siblings."""
     from epipolarconsistency_amd import build
     assert "weighted_robust_kernel.hip" in build.SOURCES and "ecc_weighted_robust.hip" in build.SOURCES
-    assert "ecc_robust_weight.h" in build.HEADERS
+    assert "ecc_robust_weight.h" in build.HEADERS and "ecc_loss_forms.h" in build.HEADERS
     assert build.PER_SOURCE_FLAGS.get("weighted_robust_kernel.hip") == ["-fno-slp-vectorize"]
 
 
-def test_robust_weight_is_stated_once():
-    """robust_weight lives in ecc_robust_weight.h; both kernel files include it and neither restates it."""
+LOSS_KERNEL_FILES = ("robust_kernel.hip", "robust_map_kernel.hip", "weighted_robust_kernel.hip", "weighted_robust_map_kernel.hip",
+                     "variance_robust_kernel.hip", "variance_robust_map_kernel.hip")
+
+
+def _csrc_texts():
     csrc = os.path.join(PKG, "csrc")
-    with open(os.path.join(csrc, "ecc_robust_weight.h")) as f:
-        assert f.read().count("float robust_weight(") == 1
-    for name in ("robust_kernel.hip", "weighted_robust_kernel.hip"):
-        with open(os.path.join(csrc, name)) as f:
-            text = f.read()
-        assert '#include "ecc_robust_weight.h"' in text and "float robust_weight(" not in text and "robust_weight(L, dp)" in text, name
+    texts = {}
+    for name in sorted(os.listdir(csrc)):
+        if name.endswith((".hip", ".h", ".cpp")):
+            with open(os.path.join(csrc, name)) as f:
+                texts[name] = f.read()
+    return texts
+
+
+def test_robust_weight_is_stated_once():
+    """robust_weight is defined once in all of csrc/, in ecc_robust_weight.h; none of the six loss kernel files restates it, they
+    take it through the forms header (ecc_loss_forms.h), which includes ecc_robust_weight.h and calls it."""
+    texts = _csrc_texts()
+    assert {name: t.count("float robust_weight(") for name, t in texts.items() if "float robust_weight(" in t} == {"ecc_robust_weight.h": 1}
+    for name in LOSS_KERNEL_FILES:
+        assert "float robust_weight(" not in texts[name] and '#include "ecc_loss_forms.h"' in texts[name], name
+    forms = texts["ecc_loss_forms.h"]
+    assert '#include "ecc_robust_weight.h"' in forms and "robust_weight(L, dp)" in forms and "robust_weight(L, d)" in forms
+
+
+def test_the_trips_are_stated_once():
+    """none of the six loss kernel files states a trip; the forms header states each of the three once per form
+    template (RobustForm, FieldLossForm); the deposits are called from ecc_robust_map.h alone, so a map kernel can differ from its
+    evaluation in the deposits only."""
+    texts = _csrc_texts()
+    trips = ("poly_trip(", "exact_trip(", "reference_trip(")
+    for name in LOSS_KERNEL_FILES:
+        for trip in trips:
+            assert trip not in texts[name], (name, trip)
+    forms = texts["ecc_loss_forms.h"]
+    templates = re.findall(r"\ntemplate <[^>]*>\nstruct (\w+Form) ", forms)
+    assert templates == ["RobustForm", "FieldLossForm"], templates
+    for trip in trips:
+        assert forms.count(trip) == len(templates), (trip, forms.count(trip))
+    assert sorted(name for name, t in texts.items() if "deposit_at(" in t) == ["ecc_robust_map.h"]
 
 
 # ---- resources ---------------------------------------------------------------------------------------------------------------
