@@ -125,6 +125,11 @@ SIGNATURES = {
     "ecc_metric_evaluate_variance_robust_map": (_i, [_vp, _i, C.c_float, C.c_float, _vp, _i, _vp, _vp, _pd, _pd, _pd, _vp]),
     "ecc_metric_evaluate_variance_robust_map_pairs": (_i, [_vp, _vp, _i, _i, C.c_float, C.c_float, _vp, _i, _vp, _vp, _pd, _pd, _pd, _vp]),
     "ecc_metric_variance_robust_map_variances": (_i, [_vp, C.c_float, C.c_float, C.c_float, C.c_float, _vp]),
+    "ecc_metric_evaluate_residual_histogram": (_i, [_vp, C.c_float, _i, _vp]),
+    "ecc_metric_evaluate_residual_histogram_pairs": (_i, [_vp, _vp, _i, C.c_float, _i, _vp]),
+    "ecc_metric_evaluate_variance_residual_histogram": (_i, [_vp, C.c_float, C.c_float, _i, _vp]),
+    "ecc_metric_evaluate_variance_residual_histogram_pairs": (_i, [_vp, _vp, _i, C.c_float, C.c_float, _i, _vp]),
+    "ecc_host_histogram_quantile": (_d, [_vp, _i, _d, _d]),
     "ecc_metric_evaluate_weighted_robust": (_i, [_vp, _i, C.c_float, _pd, _pd, _pd, _vp]),
     "ecc_metric_evaluate_weighted_robust_pairs": (_i, [_vp, _vp, _i, _i, C.c_float, _pd, _pd, _pd, _vp]),
     "ecc_host_weighted_robust_scale": (_d, [_vp, _i64, _d]),

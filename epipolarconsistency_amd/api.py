@@ -1142,6 +1142,44 @@ class MetricRadonIntermediate:
         return _scalar_form_call(_lib.lib().ecc_metric_evaluate_variance_robust, self._h, (), (int(loss), float(delta), float(floor)), 3,
                                  _n_all_pairs(self._Ps), 4, want_pairs)
 
+    def _histogram_call(self, fn, lead, extra, n_bins):
+        """fn(handle, *lead, *extra, n_bins, counts) -> counts, (n_views, n_bins) uint64, written completely."""
+        n = 0 if self._Ps is None else len(self._Ps)
+        counts = np.zeros((max(n, 1), max(int(n_bins), 1)), np.uint64)  # (no matrices, a bad n_bins: the library reports it)
+        check(fn(self._h, *lead, *extra, int(n_bins), C.c_void_p(counts.ctypes.data)))
+        return counts[:n]
+
+    def evaluate_residual_histogram(self, width, n_bins=256):
+        """ecc_metric_evaluate_residual_histogram: how the per-sample residuals of evaluate_robust are distributed, per view, from
+        one pair launch -- before any delta exists.  Every +-kappa sample of every pair i < j, with evaluate_robust's positions and
+        residual d in the metric's sampling mode, is counted in bin min(int(|d| / width), n_bins - 1) of row i AND of row j.
+        width > 0 in the units of the data (float32); n_bins a multiple of 64 in [64, 1024]; the last bin is the overflow bin (NaN
+        lands there).  Returns counts, (n_views, n_bins) uint64: a row's sum is that view's sample count, the sum of all cells twice
+        the samples.  Integer sums on the device: the same call gives the same bits.  histogram_quantile reads a quantile off a row
+        or a sum of rows, sample_robust_scale a delta.  The current matrices and everything the metric keeps stay."""
+        return self._histogram_call(_lib.lib().ecc_metric_evaluate_residual_histogram, (), (float(width),), n_bins)
+
+    def evaluate_residual_histogram_pairs(self, idx4, width, n_bins=256):
+        """ecc_metric_evaluate_residual_histogram_pairs: evaluate_residual_histogram over an index list of (P0, P1, D0, D1) tuples;
+        D0 and D1 lie in [0, n_views) and name the two rows a tuple's samples are counted in.  The sampling mode resolves from the
+        list's length; a pair listed twice counts twice; an empty list gives zeros."""
+        idx = _idx4_list(idx4)
+        return self._histogram_call(_lib.lib().ecc_metric_evaluate_residual_histogram_pairs, (_ptr(idx), len(idx)), (float(width),), n_bins)
+
+    def evaluate_variance_residual_histogram(self, floor, width, n_bins=256):
+        """ecc_metric_evaluate_variance_residual_histogram: evaluate_residual_histogram in sigma units, on a 2 * n_views metric as
+        evaluate_variance_robust takes it -- the binned quantity is |z| = |d| / sqrt(max(V_i + V_j, floor)), width counts sigmas.
+        The share of a row below 1 (and 2, 3) is the calibration check of the variance fields: 68 % (95 %, 99.7 %) for Gaussian noise
+        of the stated variance.  V = 0.5 everywhere and floor <= 1: the bits of evaluate_residual_histogram on the data alone."""
+        return self._histogram_call(_lib.lib().ecc_metric_evaluate_variance_residual_histogram, (), (float(floor), float(width)), n_bins)
+
+    def evaluate_variance_residual_histogram_pairs(self, idx4, floor, width, n_bins=256):
+        """ecc_metric_evaluate_variance_residual_histogram_pairs: evaluate_variance_residual_histogram over an index list as
+        evaluate_variance_robust_pairs takes it."""
+        idx = _idx4_list(idx4)
+        return self._histogram_call(_lib.lib().ecc_metric_evaluate_variance_residual_histogram_pairs, (_ptr(idx), len(idx)),
+                                    (float(floor), float(width)), n_bins)
+
     def evaluate_variance_robust_map(self, loss, delta, floor, views=None, want_pairs=False):
         """ecc_metric_evaluate_variance_robust_map: evaluate_variance_robust(loss, delta, floor) on a 2 * n_views metric -- the same
         bits in value, mean_weight, inlier_mass and pairs -- and WHERE the loss rejected, in sigma units: per mapped view a HITS
@@ -1940,6 +1978,54 @@ def variance_robust_scale(pair_terms, k=1.0):
     if rows.ndim != 2 or rows.shape[1] != 4:
         raise ValueError("pair_terms must be (n_pairs, 4) rows {c, u, k, r}")
     return float(_lib.lib().ecc_host_variance_robust_scale(C.c_void_p(rows.ctypes.data) if len(rows) else None, len(rows), float(k)))
+
+
+def histogram_quantile(counts, width, q):
+    """ecc_host_histogram_quantile: the q-quantile (q in [0, 1]) of the binned quantity from the counts of
+    evaluate_residual_histogram at the same width -- one row, or any (..., n_bins) array, whose rows are added first.  Linear
+    interpolation inside the bin where the cumulative count crosses q x total; inf when that is the overflow bin (take a larger
+    width); 0.0 for no samples; nan for q outside [0, 1]."""
+    c = np.asarray(counts)
+    if c.ndim < 1 or c.shape[-1] < 1:
+        raise ValueError("counts must be (n_bins,) or (..., n_bins)")
+    row = np.ascontiguousarray(c.reshape(-1, c.shape[-1]).sum(axis=0, dtype=np.uint64))
+    return float(_lib.lib().ecc_host_histogram_quantile(C.c_void_p(row.ctypes.data), len(row), float(width), float(q)))
+
+
+def sample_robust_scale(metric, q=0.5, k=1.4826, n_bins=256, floor=None, first_width=None):
+    """A scale delta for evaluate_robust from the SAMPLES: k x the q-quantile of |d| over all samples of all pairs (the defaults:
+    1.4826 x the median absolute residual, the Gaussian-consistent MAD).  robust_scale takes delta from per-pair rms figures, which
+    the outliers themselves pull up; the loss is applied per sample.  floor: None for a metric as evaluate_robust takes it; a
+    variance floor for a 2 * n_views metric, delta then counts sigmas (evaluate_variance_robust).  The first bin width spreads
+    4 x robust_scale (variance_robust_scale) of the delta = inf rows over the bins (first_width: the caller's own first width
+    instead, and no delta = inf call); while the quantile lies in the overflow bin the width doubles, at most 32 times, then
+    RuntimeError (NaN data, which stays in the overflow bin, with a q that reaches it).  The answer is exact to within one bin of
+    the last width.  q in [0, 1], else ValueError before anything is launched.  Returns 0.0 when every residual is zero."""
+    q, k = float(q), float(k)
+    if not 0.0 <= q <= 1.0:
+        raise ValueError("sample_robust_scale: q must lie in [0, 1]")
+    if floor is None:
+        histogram = lambda w: metric.evaluate_residual_histogram(w, n_bins)
+    else:
+        histogram = lambda w: metric.evaluate_variance_residual_histogram(floor, w, n_bins)
+    if first_width is None:
+        if floor is None:
+            first = robust_scale(metric.evaluate_robust(_lib.LOSS_TRUNCATED, float("inf"), want_pairs=True)[-1])
+        else:
+            first = variance_robust_scale(metric.evaluate_variance_robust(_lib.LOSS_TRUNCATED, float("inf"), floor, want_pairs=True)[-1])
+        if not first > 0.0:
+            return 0.0
+        width = float(np.float32(4.0 * first / int(n_bins)))
+    else:
+        width = float(np.float32(first_width))
+        if not (width > 0.0 and np.isfinite(width)):
+            raise ValueError("sample_robust_scale: first_width must be finite and > 0")
+    for _ in range(33):
+        value = histogram_quantile(histogram(width), width, q)
+        if np.isfinite(value):
+            return k * value
+        width *= 2.0
+    raise RuntimeError("sample_robust_scale: the quantile stayed in the overflow bin after 32 doublings of the bin width")
 
 
 def refine_line_weights(ctx, Ps, data, weights=None, loss=_lib.LOSS_TRUNCATED, k=0.5, passes=2, min_hits=1.0, gain=1.0, sampling="auto"):

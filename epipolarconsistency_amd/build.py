@@ -12,9 +12,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libecc_hip.so")
-SOURCES = ["radon_kernel.hip", "ramp_kernel.hip", "preprocess_kernel.hip", "direct_kernel.hip", "direct_list_kernel.hip", "pairs_kernel.hip", "sum_kernel.hip", "small_eval_kernel.hip", "small_poses_kernel.hip", "gram_kernel.hip", "view_coeff_kernel.hip", "view_hessian_kernel.hip", "weighted_kernel.hip", "weighted_poses_kernel.hip", "weighted_transforms_kernel.hip", "form_sums_kernel.hip", "form_base_scatter_kernel.hip", "robust_kernel.hip", "weighted_robust_kernel.hip", "robust_map_kernel.hip", "weighted_robust_map_kernel.hip", "variance_kernel.hip", "variance_robust_kernel.hip", "variance_robust_map_kernel.hip", "line_weights_kernel.hip", "geometry_kernel.hip", "ecc_capi.hip", "ecc_radon_api.hip", "ecc_metric_api.hip", "ecc_preprocess_api.hip", "ecc_direct_api.hip", "ecc_direct_lists.hip", "ecc_evaluate.hip", "ecc_poses.hip", "ecc_gradient.hip", "ecc_gram.hip", "ecc_view_coeff.hip", "ecc_view_hessian.hip", "ecc_weighted.hip", "ecc_weighted_poses.hip", "ecc_transforms.hip", "ecc_weighted_transforms.hip", "ecc_robust.hip", "ecc_robust_batches.hip", "ecc_weighted_robust.hip", "ecc_weighted_robust_batches.hip", "ecc_line_weights.hip", "ecc_robust_map.hip", "ecc_weighted_robust_map.hip", "ecc_variance.hip", "ecc_variance_robust.hip", "ecc_variance_robust_map.hip",
+SOURCES = ["radon_kernel.hip", "ramp_kernel.hip", "preprocess_kernel.hip", "direct_kernel.hip", "direct_list_kernel.hip", "pairs_kernel.hip", "sum_kernel.hip", "small_eval_kernel.hip", "small_poses_kernel.hip", "gram_kernel.hip", "view_coeff_kernel.hip", "view_hessian_kernel.hip", "weighted_kernel.hip", "weighted_poses_kernel.hip", "weighted_transforms_kernel.hip", "form_sums_kernel.hip", "form_base_scatter_kernel.hip", "robust_kernel.hip", "weighted_robust_kernel.hip", "robust_map_kernel.hip", "weighted_robust_map_kernel.hip", "variance_kernel.hip", "variance_robust_kernel.hip", "variance_robust_map_kernel.hip", "residual_histogram_kernel.hip", "line_weights_kernel.hip", "geometry_kernel.hip", "ecc_capi.hip", "ecc_radon_api.hip", "ecc_metric_api.hip", "ecc_preprocess_api.hip", "ecc_direct_api.hip", "ecc_direct_lists.hip", "ecc_evaluate.hip", "ecc_poses.hip", "ecc_gradient.hip", "ecc_gram.hip", "ecc_view_coeff.hip", "ecc_view_hessian.hip", "ecc_weighted.hip", "ecc_weighted_poses.hip", "ecc_transforms.hip", "ecc_weighted_transforms.hip", "ecc_robust.hip", "ecc_robust_batches.hip", "ecc_weighted_robust.hip", "ecc_weighted_robust_batches.hip", "ecc_line_weights.hip", "ecc_robust_map.hip", "ecc_weighted_robust_map.hip", "ecc_variance.hip", "ecc_variance_robust.hip", "ecc_variance_robust_map.hip", "ecc_residual_histogram.hip",
            "ecc_exchange.cpp", "ecc_group.cpp", "ecc_rccl.cpp"]  # .cpp: host-only code (no device code), still built by hipcc for the HIP headers
-HEADERS = ["ecc_layout.h", "ecc_host_geometry.h", "ecc_sampling.h", "ecc_worker_pool.h", "ecc_pose_diff.h", "ecc_view_changes.h", "ecc_form_base.h", "ecc_sum_order.h", "ecc_pose_scatter.h", "ecc_transform_grid.h", "ecc_slab_tile.h", "ecc_direct_lines.h", "ecc_direct_internal.h", "ecc_direct_lists_host.h", "ecc_extremum_tile.h", "ecc_pairs_device.h", "ecc_pair_forms.h", "ecc_robust_weight.h", "ecc_studentised_weight.h", "ecc_loss_forms.h", "ecc_robust_map.h", "ecc_capi_internal.h", "ecc_column_call.h", "ecc_pose_batches.h", "ecc_form_call.h", "ecc_variance_host.h", "ecc_variance_robust_host.h", os.path.join("..", "..", "include", "ecc_hip.h")]
+HEADERS = ["ecc_layout.h", "ecc_host_geometry.h", "ecc_sampling.h", "ecc_worker_pool.h", "ecc_pose_diff.h", "ecc_view_changes.h", "ecc_form_base.h", "ecc_sum_order.h", "ecc_pose_scatter.h", "ecc_transform_grid.h", "ecc_slab_tile.h", "ecc_direct_lines.h", "ecc_direct_internal.h", "ecc_direct_lists_host.h", "ecc_extremum_tile.h", "ecc_pairs_device.h", "ecc_pair_forms.h", "ecc_robust_weight.h", "ecc_studentised_weight.h", "ecc_loss_forms.h", "ecc_robust_map.h", "ecc_residual_histogram.h", "ecc_capi_internal.h", "ecc_column_call.h", "ecc_pose_batches.h", "ecc_form_call.h", "ecc_variance_host.h", "ecc_variance_robust_host.h", "ecc_histogram_host.h", os.path.join("..", "..", "include", "ecc_hip.h")]
 # radon_kernel.hip: the SLP vectoriser packs the two samples of the derivative pair into v_pk_*_f32 pairs, which
 # cost two issue slots each on gfx950 (no gain, scripts/micro/valu_rate.hip) plus ~12 v_mov per iteration to
 # arrange operands -- scalar code is ~15 % faster there; the pair kernel gains 7 % the same way (0.548 -> 0.512 ms).
@@ -35,6 +35,7 @@ PER_SOURCE_FLAGS = {"radon_kernel.hip": ["-fno-slp-vectorize"], "pairs_kernel.hi
                     "variance_kernel.hip": ["-fno-slp-vectorize"],
                     "variance_robust_kernel.hip": ["-fno-slp-vectorize"],
                     "variance_robust_map_kernel.hip": ["-fno-slp-vectorize"],
+                    "residual_histogram_kernel.hip": ["-fno-slp-vectorize"],
                     "direct_kernel.hip": ["-fno-slp-vectorize"],
                     "direct_list_kernel.hip": ["-fno-slp-vectorize"]}  # (the same walker, built the same way)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-fvisibility=hidden",

@@ -690,6 +690,12 @@ class MetricRadonIntermediate : public Metric {
         detail::assignIfPresent(rejected, k * bins);
         return k;
     }
+    // the table of a histogram call: n_views rows of n_bins counts (at least one cell: a bad n_bins is the library's to report)
+    void sizeHistogram(int n_bins, std::vector<uint64_t>& counts) const
+    {
+        const size_t cells = Ps.size() * (size_t)(n_bins > 0 ? n_bins : 0);
+        counts.assign(cells ? cells : 1, (uint64_t)0);
+    }
     static float* dataOrNull(std::vector<float>* v) { return (v && !v->empty()) ? v->data() : 0x0; }
     static double* dataOrNull(std::vector<double>* v) { return (v && !v->empty()) ? v->data() : 0x0; }
     static const int32_t* dataOrNull(const std::vector<int32_t>& v) { return v.empty() ? 0x0 : v.data(); }
@@ -1427,6 +1433,59 @@ public:
         std::vector<ecc_dtr*> hs(m_map_planes ? m_map_planes : 1, (ecc_dtr*)0x0);
         detail::check(ecc_metric_variance_robust_map_variances(m_h, floor, min_hits, gain, max_factor, hs.data()));
         return ownMapWeights(hs);
+    }
+
+    /// Not in the reference: ecc_metric_evaluate_residual_histogram -- how the per-sample residuals of evaluateRobust are distributed,
+    /// per view, from one pair launch, before any delta exists.  counts is resized to n_views x n_bins, row-major: every +-kappa sample
+    /// of the pair i < j is counted in bin min(int(|d| / width), n_bins - 1) of row i AND of row j; the last bin is the overflow bin.
+    /// n_bins: a multiple of 64 in [64, 1024].  Integer sums on the device: the same call gives the same bits (ecc_hip.h).
+    /// histogramQuantile reads a quantile off a row.  Single device only.
+    void evaluateResidualHistogram(float width, int n_bins, std::vector<uint64_t>& counts)
+    {
+        if (m_gh) throw std::runtime_error("evaluateResidualHistogram: not available on a device group");
+        sizeHistogram(n_bins, counts);
+        detail::check(ecc_metric_evaluate_residual_histogram(m_h, width, n_bins, counts.data()));
+    }
+
+    /// Not in the reference: ecc_metric_evaluate_residual_histogram_pairs -- evaluateResidualHistogram over an index list of
+    /// (P0, P1, D0, D1) tuples (4 ints per tuple); D0, D1 in [0, n_views) name the two rows a tuple's samples are counted in.
+    /// Single device only.
+    void evaluateResidualHistogramPairs(const std::vector<int>& indices, float width, int n_bins, std::vector<uint64_t>& counts)
+    {
+        if (m_gh) throw std::runtime_error("evaluateResidualHistogramPairs: not available on a device group");
+        const std::vector<int32_t> idx = detail::widenTuples("evaluateResidualHistogramPairs", indices);
+        sizeHistogram(n_bins, counts);
+        detail::check(ecc_metric_evaluate_residual_histogram_pairs(m_h, dataOrNull(idx), (int)(idx.size() / 4), width, n_bins, counts.data()));
+    }
+
+    /// Not in the reference: ecc_metric_evaluate_variance_residual_histogram -- evaluateResidualHistogram in sigma units on the
+    /// 2 * n_views metric of evaluateVarianceRobust: the binned quantity is |d| / sqrt(max(V_i + V_j, floor)), width counts sigmas.
+    /// The share of a row below 1 is the calibration check of the variance fields (ecc_hip.h).  Single device only.
+    void evaluateVarianceResidualHistogram(float floor, float width, int n_bins, std::vector<uint64_t>& counts)
+    {
+        if (m_gh) throw std::runtime_error("evaluateVarianceResidualHistogram: not available on a device group");
+        sizeHistogram(n_bins, counts);
+        detail::check(ecc_metric_evaluate_variance_residual_histogram(m_h, floor, width, n_bins, counts.data()));
+    }
+
+    /// Not in the reference: ecc_metric_evaluate_variance_residual_histogram_pairs -- evaluateVarianceResidualHistogram over an index
+    /// list as evaluateVarianceRobustPairs takes it.  Single device only.
+    void evaluateVarianceResidualHistogramPairs(const std::vector<int>& indices, float floor, float width, int n_bins,
+                                                std::vector<uint64_t>& counts)
+    {
+        if (m_gh) throw std::runtime_error("evaluateVarianceResidualHistogramPairs: not available on a device group");
+        const std::vector<int32_t> idx = detail::widenTuples("evaluateVarianceResidualHistogramPairs", indices);
+        sizeHistogram(n_bins, counts);
+        detail::check(ecc_metric_evaluate_variance_residual_histogram_pairs(m_h, dataOrNull(idx), (int)(idx.size() / 4), floor, width, n_bins,
+                                                                            counts.data()));
+    }
+
+    /// ecc_host_histogram_quantile: the q-quantile of the binned quantity from `row` (n_bins counts: one row of a histogram, or the
+    /// caller's sum of rows) at the width the counts were made with; +infinity when it lies in the overflow bin, 0.0 for an empty
+    /// row, NaN for q outside [0, 1].  Touches no device.
+    static double histogramQuantile(const std::vector<uint64_t>& row, double width, double q)
+    {
+        return ecc_host_histogram_quantile(row.empty() ? 0x0 : row.data(), (int)row.size(), width, q);
     }
 
     /// Not in the reference: ecc_metric_evaluate_robust_pose_deltas -- evaluatePoseDeltas under the per-sample robust loss of

@@ -455,6 +455,8 @@ struct ecc_metric {
     // sigma units, deposits in count units); map_slot_d is the plane table (map_n_slots entries), then the mapped intermediates
     EccMapKind map_kind = ECC_MAP_PLAIN;
     int map_n_slots = 0;
+    // ecc_metric_evaluate_residual_histogram (ecc_residual_histogram.hip): the n_views x n_bins table of a call, zeroed per call
+    DeviceArray<unsigned long long> histogram_d;
     // ecc_metric_set_form_incremental (ecc_form_call.h): the T base columns of the last *_pose_deltas call of a form
     // family, col_stride apart as that call's columns are in gram_values_d, with the form, the parameters and the matrices they belong
     // to (ecc_form_base.h); the all-pairs, list, map and Gram calls keep to gram_values_d and neither see nor disturb them.  Dropped

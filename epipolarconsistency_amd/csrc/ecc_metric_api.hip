@@ -355,7 +355,8 @@ ECC_EXPORT int ecc_metric_device_bytes(const ecc_metric* m, int64_t* paired_byte
                           m->records_d.bytes() + m->cache_values_d.bytes() + m->pose_PinvTs_d.bytes() + m->pose_Cs_d.bytes() +
                           m->pose_idx_d.bytes() + m->pose_values_d.bytes() + m->pose_records_d.bytes() + m->pose_partial_d.bytes() +
                           m->pose_lists_d.bytes() + m->transform_radii_d.bytes() + m->sum_scratch_d.bytes() + m->sum_d.bytes() +
-                          m->map_fixed_d.bytes() + m->map_planes_d.bytes() + m->map_slot_d.bytes() + m->form_base_d.bytes();
+                          m->map_fixed_d.bytes() + m->map_planes_d.bytes() + m->map_slot_d.bytes() + m->form_base_d.bytes() +
+                          m->histogram_d.bytes();
     if (paired_bytes) *paired_bytes = m->paired_d.bytes();
     if (quad_bytes) *quad_bytes = m->quads_d.bytes();
     if (other_bytes) *other_bytes = other;

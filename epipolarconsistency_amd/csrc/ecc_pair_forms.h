@@ -299,17 +299,19 @@ __device__ __forceinline__ bool form_reference_sums(const EccPairParams& p, Form
 }
 
 // ---- 7. the host's choice of kernel ------------------------------------------------------------------------
-// The reference kernel for four waves or for one wave per pair, else the main kernel for derivative or plain data.
+// The reference kernel for four waves or for one wave per pair, else the main kernel for derivative or plain data.  lds_bytes: the
+// dynamic LDS of a workgroup, for the forms that size theirs by the launch (residual_histogram_kernel.hip).
 template <class G>
 hipError_t launch_pair_form(const EccPairParams& p, const G& g, hipStream_t stream, void (*ref4)(EccPairParams, G),
-                            void (*ref1)(EccPairParams, G), void (*main_deriv)(EccPairParams, G), void (*main_plain)(EccPairParams, G))
+                            void (*ref1)(EccPairParams, G), void (*main_deriv)(EccPairParams, G), void (*main_plain)(EccPairParams, G),
+                            size_t lds_bytes = 0)
 {
     if (p.reference_arithmetic) {
-        if (p.reference_split > 1) hipLaunchKernelGGL(ref4, dim3((unsigned)p.count), dim3(PK_THREADS), 0, stream, p, g);
-        else hipLaunchKernelGGL(ref1, dim3((unsigned)((p.count + 3) / 4)), dim3(PK_THREADS), 0, stream, p, g);
+        if (p.reference_split > 1) hipLaunchKernelGGL(ref4, dim3((unsigned)p.count), dim3(PK_THREADS), lds_bytes, stream, p, g);
+        else hipLaunchKernelGGL(ref1, dim3((unsigned)((p.count + 3) / 4)), dim3(PK_THREADS), lds_bytes, stream, p, g);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL(p.is_derivative ? main_deriv : main_plain, main_pairs_grid(p.count), dim3(PK_MAIN_THREADS), 0, stream, p, g);
+    hipLaunchKernelGGL(p.is_derivative ? main_deriv : main_plain, main_pairs_grid(p.count), dim3(PK_MAIN_THREADS), lds_bytes, stream, p, g);
     return hipGetLastError();
 }
 

@@ -1283,6 +1283,60 @@ int ecc_metric_evaluate_variance_robust_map_pairs(ecc_metric* m, const int32_t* 
         double* value, double* mean_weight, double* inlier_mass, float* pair_terms);
 int ecc_metric_variance_robust_map_variances(ecc_metric* m, float floor, float min_hits, float gain, float max_factor, ecc_dtr** out);
 
+/* The distribution of the per-sample residual, per view, from one pair launch (csrc/ecc_residual_histogram.hip,
+ * csrc/residual_histogram_kernel.hip, csrc/ecc_histogram_host.h).  Every robust call above takes a scale delta, and
+ * ecc_host_robust_scale can only propose one from per-pair figures, which the outliers themselves pull up; the maps say where a loss
+ * rejected at a delta somebody already chose.  These calls count the samples themselves, before any delta exists: delta from sample
+ * quantiles ("1.48 x the median absolute residual", "reject the worst 5 %"), a per-view tail share that names the view with the
+ * instrument, and in sigma units the calibration check of a variance model (the share of |z| below 1).
+ *
+ * counts is n_views x n_bins, row-major, and is WRITTEN COMPLETELY.  Row v holds every +-kappa sample of every evaluated pair that has
+ * v as one of its two DATA indices (the list forms: D0 and D1, both in [0, n_views)): a sample counts once in each of its pair's two
+ * rows.  A row's sum is that view's sample count, the sum over all cells 2 x the samples.  Counts are integers, added with integer
+ * atomics: the same arguments give the same bits in any launch order.
+ *
+ * ecc_metric_evaluate_residual_histogram / _pairs take whatever metric ecc_metric_evaluate_robust / _pairs take.  Positions, kappa
+ * range, sampling mode and the residual d of a sample are that call's, in every loop class.  Per sample, every line one float32
+ * operation:
+ *     a   = fabsf(d)
+ *     x   = a * inv_width                                      inv_width = (float)(1.0 / (double)width), formed on the host
+ *     bin = x < (float)(n_bins - 1) ? (int)x : n_bins - 1      NaN and +inf land in the last bin: the last bin is the OVERFLOW bin
+ * so bin k < n_bins - 1 holds the samples with k <= |d| * inv_width < k + 1.  Doubling width halves inv_width exactly: the bins of
+ * width 2 w are pairs of the bins of width w, bit for bit.
+ *
+ * ecc_metric_evaluate_variance_residual_histogram / _pairs take ecc_metric_evaluate_variance_robust's metric (n_dtrs == 2 * n_views:
+ * the data, then the variance fields) and bin the STUDENTISED residual with that call's own statements: s = V_i + V_j from the
+ * UNSIGNED samples at the data's taps, sc = s < floor ? floor : s, a = fabsf(d) / sqrtf(sc) (the correctly rounded division and
+ * root), then x and bin as above; width counts sigmas.  floor as for ecc_metric_evaluate_variance.
+ *   V == 0.5f, floor <= 1          the counts of the raw form on the n-metric over the same data, bit for bit.
+ *   V and floor x 4, width x 1/2   the counts keep their bits.
+ *   - width: finite and > 0, and so must inv_width be.  n_bins: a multiple of 64 with 64 <= n_bins <= 1024.
+ *   - Errors before anything is launched or written, in this order: ECC_ERR_INVALID_ARGUMENT for m NULL; counts NULL; a bad width
+ *     or n_bins; the list forms' n_pairs < 0 or (n_pairs > 0 and idx4 NULL); no projection matrices; fewer than two views; the
+ *     variance forms' n_dtrs != 2 * n_views or bad floor (the raw forms: fewer intermediates than matrices, behind use_corr as for
+ *     ecc_metric_evaluate_robust); ECC_ERR_UNSUPPORTED for use_corr; ECC_ERR_INVALID_ARGUMENT for list indices out of range.
+ *     After them n_pairs == 0 is ECC_OK: counts is all zeros.
+ * Launches: a column-form call's without value columns -- E1 if needed, k01_kernel, the memset of the table, ONE pair launch
+ * (pairs_residual_histogram_kernel or pairs_variance_residual_histogram_kernel, in ECC_SAMPLING_REFERENCE their reference kernels)
+ * between the timing events, the copy of the table, one wait.  Each wave counts into a private sub-histogram in LDS and adds its
+ * non-zero bins to the pair's two rows when its pair is done: one LDS atomic per sample (measured at 400 views: 0.82 to 0.98 x
+ * pairs_robust_kernel's time, min 0.811 and max 0.977 over the windows).
+ * The current matrices and everything the metric keeps stay.
+ *
+ * ecc_host_histogram_quantile (host only, no device): the q-quantile of the binned quantity from one row of counts, or from the
+ * caller's sum of rows, at the width the counts were made with.  Linear interpolation inside the bin where the cumulative count
+ * crosses q x total: (k + (q total - below) / counts[k]) * width.  +infinity when the crossing lies in the overflow bin (widen and
+ * call again); 0.0 for an empty row, for counts NULL or n_bins < 1; NaN for q outside [0, 1] or a width that is not finite and > 0.
+ *
+ * Not built: pose-delta and transform batches; the form under line weights (counts would not be integers); range, group and RCCL
+ * forms; use_corr. */
+int ecc_metric_evaluate_residual_histogram(ecc_metric* m, float width, int n_bins, uint64_t* counts);
+int ecc_metric_evaluate_residual_histogram_pairs(ecc_metric* m, const int32_t* idx4, int n_pairs, float width, int n_bins, uint64_t* counts);
+int ecc_metric_evaluate_variance_residual_histogram(ecc_metric* m, float floor, float width, int n_bins, uint64_t* counts);
+int ecc_metric_evaluate_variance_residual_histogram_pairs(ecc_metric* m, const int32_t* idx4, int n_pairs, float floor, float width, int n_bins,
+        uint64_t* counts);
+double ecc_host_histogram_quantile(const uint64_t* counts, int n_bins, double width, double q);   /* host only */
+
 /* Multi-GPU building block: evaluate only pairs ij in [first, first+count) of the get_ij order
  * (ref: EpipolarConsistencyCommon.hxx:52-79); returns the partial sum (float64) -- the caller
  * all-reduces {sum, count}.  pair_values (host, nullable) receives `count` floats. */
